@@ -83,7 +83,12 @@ def parse():
                     'update_quant_range over the distilled batches; "" disables')
     ap.add_argument('--pcie', default='mobilenet_v2', help='CPU-resident model through the drop-in entry points; "" disables')
     ap.add_argument('--lazy-steps', type=int, default=6, help='timed steps of the opt-in lazy-scale formulation; 0 disables')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default='', help='write what the last timed step computed to DIR/<name>.npy '
+                    '(dump_outputs); "" disables')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -127,6 +132,49 @@ def make_unit(protos):
     le = dfq.build_le_plan_batch([(g, r) for (_, g, _, r) in nets], TARG)
     bc = dfq.build_bc_plan_batch([(g, b) for (_, g, b, _) in nets], TARG)
     return dict(nets=nets, le=le, bc=bc, plan_build_ms=(time.perf_counter() - t0) * 1e3)
+
+
+DUMP_SAMPLE = 1 << 19             # --dump-outputs: weights (biases) sampled over the whole batch
+DUMP_LIMIT = 64 << 20             # bytes written by --dump-outputs at most
+
+
+def dump_outputs(path, unit, net_sweeps):
+    """`--dump-outputs DIR`: what a caller of the timed path holds after its last step -- the weights and biases of the step's
+    batch, equalised and bias-corrected in place -- as .npy files, layers in graph order, flattened:
+      weights_net0, biases_net0                  every weight / bias of the batch's first network (float32)
+      weights_sample, biases_sample              a fixed seeded sample of the whole batch's weights / biases (float32) ...
+      weights_sample_index, biases_sample_index  ... and its flat indices into [network, layers] (float64)
+      le_sweeps                                  the equalisation sweeps each network ran (float64)
+    The networks are seeded (prepare), so two builds run with the same arguments can be compared array by array."""
+    import numpy as np
+    graphs = [g for (_, g, _, _) in unit['nets']]
+
+    def flat(graph, attr):
+        return torch.cat([getattr(m, attr).detach().reshape(-1) for m in graph.values()
+                          if type(m) in TARG and getattr(m, attr) is not None])
+    arrays = {'le_sweeps': np.asarray(net_sweeps, dtype=np.float64)}
+    for attr, name in (('weight', 'weights'), ('bias', 'biases')):
+        first = flat(graphs[0], attr)
+        per_net, total = first.numel(), first.numel() * len(graphs)
+        if total <= DUMP_SAMPLE:
+            idx = np.arange(total)
+        else:
+            idx = np.unique(np.random.default_rng(0).integers(0, total, size=DUMP_SAMPLE))
+        picked = []
+        for n, graph in enumerate(graphs):
+            local = idx[(idx >= n * per_net) & (idx < (n + 1) * per_net)] - n * per_net
+            vals = first if n == 0 else flat(graph, attr)
+            picked.append(vals[torch.from_numpy(local).to(vals.device)].cpu().numpy())
+        arrays[name + '_net0'] = first.cpu().numpy()
+        arrays[name + '_sample'] = np.concatenate(picked)
+        arrays[name + '_sample_index'] = idx.astype(np.float64)
+    arrays = {k: (v if v.dtype == np.float64 else v.astype(np.float32)) for k, v in arrays.items()}
+    size = sum(v.nbytes for v in arrays.values())
+    if size > DUMP_LIMIT:
+        raise SystemExit('bench.py: --dump-outputs would write {:.1f} MB (limit {:.0f} MB)'.format(size / 2 ** 20, DUMP_LIMIT / 2 ** 20))
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), v)
 
 
 def pass_bytes(le, bc, sweeps):
@@ -777,6 +825,9 @@ def main():
     for u in units[args.warmup:]:
         u['bc'].status()
     ms_per_step = elapsed * 1e3 / args.steps
+    if rank == 0 and args.dump_outputs:
+        last = units[-1]
+        dump_outputs(args.dump_outputs, last, [r['sweeps'] for r in last['le'].query_all()[0]])
 
     # where a step's time goes: the two halves of one unit on an otherwise idle GPU (one stream)
     br_units = [make_unit(protos) for _ in range(3)]

@@ -93,3 +93,91 @@ def test_bench_line_contract_single_rank():
     assert lz['sweeps'] == d['config']['le_sweeps'] and lz['sweeps_given'] and d['value_lazy_scale'] == lz['value'] > 0
     assert abs(lz['roofline']['frac'] - lz['roofline']['achieved'] / lz['roofline']['peak']) < 1e-12
     assert 'reference' in c          # the committed reference-CPU record (null for nets it was not measured on)
+
+
+DUMP_FILES = {'le_sweeps', 'weights_net0', 'biases_net0', 'weights_sample', 'weights_sample_index', 'biases_sample',
+              'biases_sample_index'}
+
+
+def test_bench_dumps_what_its_last_timed_step_computed(tmp_path):
+    """`--dump-outputs DIR` (dry run on the emulator, a batch of two tiny nets): two runs with the same arguments write the same
+    arrays, float32 / float64 only, and what they hold is the calibrated batch -- weights bit-identical to the numpy oracle's
+    LE + BC of the same seeds, biases within the BC tolerance."""
+    import numpy as np
+    import torch.nn as nn
+    sys.path.insert(0, ROOT)
+    from dfq_amd import synthetic
+    from oracle import dfq_oracle as orc
+    from oracle import graphspec
+
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
+        env.pop(k, None)
+    legs_off = ['--cpu-seconds', '0', '--no-roofline', '--others', '', '--act-shape', '', '--sharded', '', '--distill', '',
+                '--pcie', '', '--lazy-steps', '0', '--steps', '3']
+    dirs = [str(tmp_path / d) for d in ('a', 'b')]
+    procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, 'tests', 'emu', 'dryrun.py')] + legs_off + ['--dump-outputs', d],
+                              env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for d in dirs]
+    outs = [p.communicate(timeout=600) for p in procs]
+    for p, (out, err) in zip(procs, outs):
+        assert p.returncode == 0, err[-2000:]
+    d = json.loads([l for l in outs[0][0].splitlines() if l.startswith('{"metric"')][0])
+    assert d['steps'] == 3 and d['ms_per_step'] > 0
+
+    dumps = []
+    for path in dirs:
+        assert {f[:-4] for f in os.listdir(path)} == DUMP_FILES
+        arrays = {n: np.load(os.path.join(path, n + '.npy')) for n in DUMP_FILES}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        dumps.append(arrays)
+    for n in DUMP_FILES:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
+    got = dumps[0]
+    assert got['le_sweeps'].tolist() == d['config']['le_sweeps']
+
+    # the oracle on the same two networks (bench.prepare: seeds 0 and 1, BN folded, relations kept whole)
+    targ = [nn.Conv2d, nn.Linear]
+    want_w, want_b, sweeps = [], [], []
+    for seed in (0, 1):
+        _, graph, bottoms = synthetic.build('tiny_mobile', seed=seed)
+        spec = graphspec.from_torch(graph, bottoms, targ)
+        orc.merge_batchnorm(spec)
+        n, _ = orc.cross_layer_equalization(spec, orc.create_relation(spec))
+        orc.bias_correction(spec)
+        sweeps.append(n)
+        keys = [k for k in graph if type(graph[k]) in targ]
+        want_w.append(np.concatenate([spec.nodes[k].weight.reshape(-1) for k in keys]))
+        want_b.append(np.concatenate([spec.nodes[k].bias.reshape(-1) for k in keys if spec.nodes[k].bias is not None]))
+    assert got['le_sweeps'].tolist() == sweeps
+    # a batch of two tiny nets is smaller than the sample: the "sample" is every weight / bias of the batch, in order
+    assert np.array_equal(got['weights_sample_index'], np.arange(2 * want_w[0].size))
+    assert np.array_equal(got['biases_sample_index'], np.arange(2 * want_b[0].size))
+    assert np.array_equal(got['weights_net0'].view(np.int32), want_w[0].astype(np.float32).view(np.int32))
+    assert np.array_equal(got['weights_sample'].view(np.int32), np.concatenate(want_w).astype(np.float32).view(np.int32))
+    assert np.abs(got['biases_net0'] - want_b[0]).max() <= 1e-5
+    assert np.abs(got['biases_sample'] - np.concatenate(want_b)).max() <= 1e-5
+
+
+def test_bench_dump_samples_a_large_batch_at_fixed_places(monkeypatch, tmp_path):
+    """A batch larger than the sample: a fixed seeded set of sorted, distinct places, each holding the weight it names."""
+    import numpy as np
+    import torch
+    import torch.nn as nn
+    sys.path.insert(0, ROOT)
+    import bench
+    from dfq_amd import synthetic
+    monkeypatch.setattr(bench, 'DUMP_SAMPLE', 1000)
+    nets = [synthetic.build('tiny_mobile', seed=s) for s in range(3)]
+    unit = {'nets': [(m, g, b, None) for (m, g, b) in nets]}
+    flat = [torch.cat([m.weight.detach().reshape(-1) for m in g.values() if type(m) in (nn.Conv2d, nn.Linear)]).numpy()
+            for (_, g, _) in nets]
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), unit, [1, 2, 3])
+    load = lambda d, n: np.load(str(tmp_path / d / (n + '.npy')))     # noqa: E731
+    for n in DUMP_FILES:
+        assert np.array_equal(load('a', n), load('b', n)), n
+    idx = load('a', 'weights_sample_index')
+    assert 900 < idx.size <= 1000 and np.all(np.diff(idx) > 0) and idx[-1] < 3 * flat[0].size
+    assert np.array_equal(load('a', 'weights_sample'), np.concatenate(flat)[idx.astype(np.int64)])
+    assert np.array_equal(load('a', 'weights_net0'), flat[0]) and load('a', 'le_sweeps').tolist() == [1, 2, 3]
