@@ -52,6 +52,22 @@
 // leaves up to D-1 pending factors: le_flush_kernel applies them (launched at the end of every enqueue call, gated per
 // network on its sweep count) and le_hold_reset_kernel sets the remembered factors back to 1.
 //
+// Lazy sweeps (batched plans with D > 1; DFQ_LE_LAZY_DW=0: off).  Between two stores a deferred layer is still read every sweep,
+// only for its |dW| term of that sweep's verdict.  A lazy sweep does not read it: its tiles do their per-channel duties only
+// (solve, remembered factor, forwarded statistics, the [O1] vectors) -- tiles without any leave at once -- and leave 0 partials,
+// so the convergence launch sums a lower bound `lb` of diff_tmp (graph order, +0.0 for the deferred layers: the terms are >= 0 and
+// IEEE addition is monotone).  lb > converge_thres with `count` unable to reach converge_count proves "go on" whatever the missing
+// terms are; the sweep's other layer means are kept.  The missing terms come from the next sweep that reads the deferred layers:
+// the storing one (k % D == D-1), or an eager one -- chosen where the predicted bound lb^2 / lb_prev falls to DFQ_LE_LAZY_MARGIN
+// x converge_thres (default 1.5) or the count bound needs the exact verdict.  Its tiles, taking the stored value through the
+// remembered factors one rounding at a time, meet every term |fl(t h_j) - t| of the window's earlier sweeps on the way and leave
+// them, per wave and sweep, in the window arrays; the convergence launch then replays the reference's (diff, count) steps of those
+// sweeps in order with their full sums.  A lazy sweep whose bound does not prove "go on" is decided by le_resolve_kernel, launched
+// behind every convergence launch: one workgroup per such network recomputes the same partials from the stored elements
+// (replay_oneway), decides exactly, and the network reads in every later sweep of the run.  Where an enqueue call ends the same
+// kernel resolves the networks' lazy sweeps before le_flush_kernel stores.  4 (D + 1) / D -> 8 / D bytes per deferred element and
+// sweep, every value and the loop state bit-identical.
+//
 // Convergence (dfq.py:105-115): every element is written exactly once per sweep, by a pass that has
 // its pre-sweep value in a register, so each tile leaves float64 partials of sum|W - W_prev|; they are
 // reduced in a fixed order by a one-workgroup control kernel that also advances the reference's
@@ -159,6 +175,8 @@ struct LeLayerDiff {
     int32_t partial_begin;   // -1: layer untouched by any relation (contributes exactly 0)
     int32_t n_partials;
     double n_elems;
+    int32_t oneway;          // a deferred (one-way-scaled) layer: its |dW| sum may come late (lazy sweeps)
+    int32_t pad_;
 };
 
 // one working workgroup of a launch: which relation (index into the descriptor table), which tile of it, which
@@ -337,6 +355,35 @@ __device__ __forceinline__ void vstore(gfloat* p, const float (&x)[VEC]) {
     }
 }
 
+// Lazy sweeps (see "Lazy sweeps" in the header comment): where a reading tile of a deferred layer leaves the |dW| partials of
+// the skipped sweeps of its window -- one per wave and skipped sweep, in the per-phase window arrays.  NoWin: nowhere (le_sweep_kernel,
+// plans without lazy sweeps).
+struct NoWin {
+    __device__ __forceinline__ void clear(int) const {}
+    __device__ __forceinline__ void add(int, double) const {}
+    __device__ __forceinline__ void emit(int) const {}
+};
+// bits of LeRelDev::defer a level launch adds for one workgroup (the descriptor's own bits: 1 = W1, 2 = W2 is deferred)
+constexpr int kDeferLazy = 4;       // a lazy sweep: this deferred tile reads no element
+constexpr int kDeferWin = 8;        // a lazy plan: a reading deferred tile leaves the window's partials
+
+// The value of a deferred element in sweep j of its window and the one it becomes: t = v taken through the remembered factors
+// h(0) .. h(j-1) one rounding at a time, nv = fl(t * h(j)) -- what the tile of sweep j computed (row_tile, col_tile, replay_oneway).
+template <int VEC, class H>
+__device__ __forceinline__ void window_step(const float (&v)[VEC], int j, H h, float (&t)[VEC], float (&nv)[VEC]) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) t[k] = v[k];
+#pragma unroll
+    for (int i = 0; i < kHoldMax; ++i) {
+        if (i < j) {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) t[k] = t[k] * h(i, k);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) nv[k] = t[k] * h(j, k);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Tiles.  Written once for VEC = 1 (any geometry) and VEC = 4 (rows that are a multiple of 4
 // floats: every 1x1 / linear / dense conv layer of the benchmark networks): a thread then moves
@@ -351,10 +398,13 @@ __device__ __forceinline__ void vstore(gfloat* p, const float (&x)[VEC]) {
 // is known to be satisfied; `mid()` is called right after the tile's own statistics requests have been issued -- the
 // sweep kernel requests the NEXT tile's data there, so that waiting for the statistics does not wait for that data
 // (vector memory returns in order).
-template <int VEC, bool PRE, class Mid, class Dep>
+// R.defer & kDeferLazy (deferred W1 only): the tile does its per-row duties and reads no element; R.defer & kDeferWin: a reading
+// tile of a deferred W1 leaves the partials of the window's skipped sweeps through `win`
+template <int VEC, bool PRE, class Mid, class Dep, class Win = NoWin>
 __device__ __forceinline__ double row_tile(const LeRelDev& R, const LeParams& p, int tile, int cur, const Dep& dep, bool ready,
                                            float (&v_in)[kSlotsVec4][VEC], Mid mid,
-                                           float* sh_s, uint32_t* sh_slot, int* sh_g, float* sh_pinv, uint32_t* sh_rs, int* sh_flag, const LeTrace& tr) {
+                                           float* sh_s, uint32_t* sh_slot, int* sh_g, float* sh_pinv, uint32_t* sh_rs, int* sh_flag, const LeTrace& tr,
+                                           Win win = Win()) {
     constexpr int NV = (VEC == 4) ? kSlotsVec4 : kSlotsVec1;   // vectors per thread
     float v_own[NV][VEC];                                      // (an array of the caller used here when !PRE tripled the registers)
     float (&v)[NV][VEC] = *(PRE ? &v_in : &v_own);
@@ -373,7 +423,8 @@ __device__ __forceinline__ double row_tile(const LeRelDev& R, const LeParams& p,
     const int jl = lane_on ? jl_raw : 0;
     const int pos = p0 + (lane_on ? (tid - jl_raw * npv) * VEC : 0);
     const int n_own = lane_on ? small_div(nr - jl + JL - 1, JL) : 0;   // rows this thread owns (<= NV by plan)
-    const int n_max = min(NV, small_div(nr + JL - 1, JL));             // register slots in use (block-uniform)
+    const bool lazy = (R.defer & kDeferLazy) != 0;
+    const int n_max = lazy ? 0 : min(NV, small_div(nr + JL - 1, JL));  // register slots in use (block-uniform)
     gfloat* const w = (gfloat*)R.w1 + ((int64_t)r0 * R.row_len + pos);
     const bool fused = R.w1_interior != 0;     // the column rescale of the previous relation is applied here too
     // local_r1 (plan: VEC == 4, fused, the tile spans FULL rows): the tile takes the row ranges of t = fl(w / s_prev) itself -- a
@@ -541,6 +592,8 @@ __device__ __forceinline__ double row_tile(const LeRelDev& R, const LeParams& p,
     stamp(tr, 4);
 
     double acc = 0.0;
+    const bool wsum = defer && (R.defer & kDeferWin) != 0;     // the window's earlier sweeps (lazy plans), see below
+    if (wsum) win.clear(phase);
     int ci[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; ++k) ci[k] = emit ? (small_div(pos + k, R.khkw1) - i0) : 0;
@@ -577,6 +630,8 @@ __device__ __forceinline__ double row_tile(const LeRelDev& R, const LeParams& p,
         } else {
             // the stored value is `phase` sweeps old: take it through the remembered factors (one rounding each, as the
             // skipped stores would have), then this sweep's
+            // (each of those roundings is the one sweep j of the window performed: its |dW| term is |t' - t|, which a lazy plan
+            // collects here for the sweeps that read nothing)
             float t[VEC];
 #pragma unroll
             for (int k = 0; k < VEC; ++k) t[k] = v[u][k];
@@ -584,8 +639,12 @@ __device__ __forceinline__ double row_tile(const LeRelDev& R, const LeParams& p,
             for (int j = 0; j < kHoldMax; ++j) {
                 if (j < phase) {
                     const float h = sh_pinv[j * kTileRowsMax + r];
+                    float tn[VEC];
 #pragma unroll
-                    for (int k = 0; k < VEC; ++k) t[k] = t[k] * h;
+                    for (int k = 0; k < VEC; ++k) tn[k] = t[k] * h;
+                    if (wsum) win.add(j, slot_abs_diff<VEC>(ok, tn, t));
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k) t[k] = tn[k];
                 }
             }
 #pragma unroll
@@ -616,6 +675,7 @@ __device__ __forceinline__ double row_tile(const LeRelDev& R, const LeParams& p,
             atomicMax(&sh_slot[2 * (cur_g + ci[k]) + 1], enc_ord(cmx[k]));
         }
     }
+    if (wsum) win.emit(phase);
     stamp(tr, 5);
     if (emit) {
         __syncthreads();
@@ -636,10 +696,12 @@ __device__ __forceinline__ double row_tile(const LeRelDev& R, const LeParams& p,
 
 // col tile: W2[r0:r0+nr, p0:p0+np] *= 1/s[input channel]   (+ row stats of the new values)
 // G = pow2 >= np/VEC lanes share a row; 256/G rows are in flight per register slot.
-template <int VEC, bool PRE, class Mid, class Dep>
+// kDeferLazy, kDeferWin, `win`: as in row_tile, for a deferred W2
+template <int VEC, bool PRE, class Mid, class Dep, class Win = NoWin>
 __device__ __forceinline__ double col_tile(const LeRelDev& R, const LeParams& p, int tile, int cur, const Dep& dep, bool ready,
                                            float (&v_in)[kSlotsVec4][VEC], Mid mid,
-                                           float* sh_inv, uint32_t* sh_row, int* sh_tab, float* sh_hold, int* sh_flag, const LeTrace& tr) {
+                                           float* sh_inv, uint32_t* sh_row, int* sh_tab, float* sh_hold, int* sh_flag, const LeTrace& tr,
+                                           Win win = Win()) {
     constexpr int NV = (VEC == 4) ? kSlotsVec4 : kSlotsVec1;
     float v_own[NV][VEC];
     float (&v)[NV][VEC] = *(PRE ? &v_in : &v_own);
@@ -659,7 +721,8 @@ __device__ __forceinline__ double col_tile(const LeRelDev& R, const LeParams& p,
     const int ln = tid - grp * G;
     const bool lane_on = ln < npv;
     const int pos = p0 + min(ln, npv - 1) * VEC;
-    const int n_max = min(NV, (nr + n_rowslots - 1) >> (8 - lgG));     // register slots in use (block-uniform)
+    const bool lazy = (R.defer & kDeferLazy) != 0;
+    const int n_max = lazy ? 0 : min(NV, (nr + n_rowslots - 1) >> (8 - lgG));     // register slots in use (block-uniform)
     const int nxt = cur ^ 1;
     const bool stat_only = R.w2_interior != 0;              // the write happens in the next relation's row pass
     const bool emit = R.out_rows != nullptr && !(kAblate & 4);
@@ -754,10 +817,12 @@ __device__ __forceinline__ double col_tile(const LeRelDev& R, const LeParams& p,
     __syncthreads();
     stamp(tr, 4);
 
-    double acc = 0.0;
     int ci[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; ++k) ci[k] = small_div(pos + k, R.khkw) - i0;
+    double acc = 0.0;
+    const bool wsum = defer && (R.defer & kDeferWin) != 0;     // the window's earlier sweeps (lazy plans, see row_tile)
+    if (wsum) win.clear(phase);
 #pragma unroll
     for (int u = 0; u < NV; ++u) {
         if (u >= n_max) continue;
@@ -781,8 +846,12 @@ __device__ __forceinline__ double col_tile(const LeRelDev& R, const LeParams& p,
             for (int j = 0; j < kHoldMax; ++j) {
                 if (j < phase) {
                     const float* tab = hold_tab(j) + t0;
+                    float tn[VEC];
 #pragma unroll
-                    for (int k = 0; k < VEC; ++k) t[k] = t[k] * tab[ci[k]];
+                    for (int k = 0; k < VEC; ++k) tn[k] = t[k] * tab[ci[k]];
+                    if (wsum) win.add(j, slot_abs_diff<VEC>(ok, tn, t));
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k) t[k] = tn[k];
                 }
             }
 #pragma unroll
@@ -810,6 +879,7 @@ __device__ __forceinline__ double col_tile(const LeRelDev& R, const LeParams& p,
             }
         }
     }
+    if (wsum) win.emit(phase);
     stamp(tr, 5);
     if (emit) {
         __syncthreads();
@@ -946,9 +1016,10 @@ __device__ __forceinline__ uint32_t fetch_words(const void* base, int n_words, i
 }
 #include "dfq_le_cf.hpp"
 
-constexpr size_t kLevelSmem = sizeof(float) * (2 * kSlotMax + 2 * kSlotMax + kTileRowsMax + 2 * kTileRowsMax + 1);   // le_level_kernel's shared memory
+constexpr size_t kLevelSmem = sizeof(float) * (2 * kSlotMax + 2 * kSlotMax + kTileRowsMax + 2 * kTileRowsMax + 2) +   // le_level_kernel's shared memory
+                              sizeof(double) * kHoldMax * kBlock;
 constexpr int kDescWords = (int)(sizeof(LeRelDev) / 4);
-static_assert(sizeof(LeRelDev) % 4 == 0 && kDescWords + 1 <= kWave, "descriptor must fit one wave-wide load");
+static_assert(sizeof(LeRelDev) % 4 == 0 && kDescWords + 2 <= kWave, "descriptor and two state words must fit one wave-wide load");
 
 // One launch = any contiguous slice of the sweep's workgroup table: the whole sweep (default) or one dependency
 // level (DFQ_LE_MERGED=0).  `sweep` = sweeps since the last restart (parity = sweep & 1).
@@ -994,6 +1065,7 @@ struct LevelArgs {
     LeTrace tr;
     const LeLeanRef* lean;
     int64_t part_stride;
+    double* win;            // lazy plans: the window arrays of the deferred layers' partials ([defer - 1] x part_stride), else null
 };
 #if defined(__HIP_DEVICE_COMPILE__)
 __device__ __forceinline__ const LevelArgs DFQ_CONSTANT_AS& cold(const LevelArgs&) {
@@ -1011,6 +1083,25 @@ struct LeDepCold {
     __device__ __forceinline__ unsigned long long* err() const { return cold(a).err; }
     __device__ __forceinline__ int naps() const { return cold(a).p.poll_naps; }
     __device__ __forceinline__ int limit() const { return cold(a).p.spin_limit; }
+};
+// the window partials of a deferred tile of le_level_kernel: window array j, the slot of the tile's own partials, one per wave (the
+// same butterfly order); the slot is formed from values the kernel keeps anyway
+// Each thread keeps its running sums in LDS words of its own (sh[j kBlock + tid], no barrier): next to the tile's registers three
+// more float64 accumulators took le_level_kernel past its register budget.
+struct LevelWin {
+    const LevelArgs& a;
+    const int32_t& base;    // the relation's partial_base
+    const int32_t& tile;    // the tile's index in the relation (row tiles first)
+    double* sh;
+    __device__ __forceinline__ void clear(int n) const { for (int j = 0; j < n; ++j) sh[j * kBlock + threadIdx.x] = 0.0; }
+    __device__ __forceinline__ void add(int j, double x) const { sh[j * kBlock + threadIdx.x] += x; }
+    __device__ __forceinline__ void emit(int n) const {
+        for (int j = 0; j < n; ++j) {
+            const double t = wave_sum(sh[j * kBlock + threadIdx.x]);
+            if (threadIdx.x % kWave == 0)
+                cold(a).win[(int64_t)j * cold(a).part_stride + (int64_t)(base + tile) * (kBlock / kWave) + threadIdx.x / kWave] = t;
+        }
+    }
 };
 template <bool kTrace>
 __global__ __launch_bounds__(kBlock, DFQ_LE_MIN_WAVES) void le_level_kernel(LevelArgs a) {
@@ -1032,6 +1123,7 @@ __global__ __launch_bounds__(kBlock, DFQ_LE_MIN_WAVES) void le_level_kernel(Leve
     float* const sh_p = (float*)(sh_g + kTileRowsMax);          // [kSlotMax] row tile of an interior layer: 1/s of the previous relation
     uint32_t* const sh_rs = (uint32_t*)(sh_p + kSlotMax);       // [2 kTileRowsMax] row tile that takes its rows' statistics itself (local_r1)
     int& sh_flag = *(int*)(sh_rs + 2 * kTileRowsMax);           // outcome of the dependency wait
+    double* const sh_w = (double*)(sh_rs + 2 * kTileRowsMax + 2);  // [kHoldMax][kBlock] a deferred tile's window sums (LevelWin)
     const int lane = threadIdx.x % kWave;
     // one 16-byte load of the workgroup's entry, then ONE wave-wide load that fetches the descriptor
     // (lanes 0..kDescWords-1) and the loop state of the network (lane kDescWords) together; v_readlane
@@ -1050,8 +1142,9 @@ __global__ __launch_bounds__(kBlock, DFQ_LE_MIN_WAVES) void le_level_kernel(Leve
     }
     uint32_t word = 0u;
     {
-        const guint* src = (lane < kDescWords) ? (const guint*)(table + rel) + lane : (const guint*)&state[net].done;
-        if (lane <= kDescWords) word = *src;
+        const guint* src = (lane < kDescWords) ? (const guint*)(table + rel) + lane
+                         : (lane == kDescWords) ? (const guint*)&state[net].done : (const guint*)&state[net].lazy;
+        if (lane <= kDescWords + 1) word = *src;
     }
     // Only the fields the tile's side reads are broadcast into scalar registers (the others stay zero constants): the whole
     // descriptor is 57 of the ~100 scalar registers a wave has, and every field beyond the budget costs a spill move per use.
@@ -1064,6 +1157,7 @@ __global__ __launch_bounds__(kBlock, DFQ_LE_MIN_WAVES) void le_level_kernel(Leve
     DFQ_TAKE(n_row_tiles); DFQ_TAKE(n_col_tiles); DFQ_TAKE(partial_base); DFQ_TAKE(counter_idx);
     DFQ_TAKE(dep_idx); DFQ_TAKE(dep_tiles); DFQ_TAKE(r1); DFQ_TAKE(r2); DFQ_TAKE(stat_stride); DFQ_TAKE(hold); DFQ_TAKE(defer); DFQ_TAKE(o1);
     const uint32_t done = __builtin_amdgcn_readlane(word, kDescWords);
+    const uint32_t lazy_net = __builtin_amdgcn_readlane(word, kDescWords + 1);
     const LeRelDev& R = desc.R;
     const int cur = sweep & 1;
     if (done || tile >= R.n_row_tiles + R.n_col_tiles) return;   // uniform
@@ -1085,14 +1179,32 @@ __global__ __launch_bounds__(kBlock, DFQ_LE_MIN_WAVES) void le_level_kernel(Leve
         if ((int)desc.R.cdep_idx >= 0) { desc.R.dep_idx = desc.R.cdep_idx; desc.R.dep_tiles = desc.R.cdep_tiles; }   // (see LeRelDev::local_r1)
     }
 #undef DFQ_TAKE
-    if (!col_side) {
+    // a lazy sweep of the network (the convergence launch of the sweep before chose it; never a storing sweep): the tiles of its
+    // deferred layers read no element, and the ones without per-channel duties -- a row tile that does not own its rows' [O1]
+    // vectors, a column tile that holds no group's first row -- have nothing to do at all
+    const bool own_defer = (R.defer & (col_side ? 2 : 1)) != 0 && cold(a).win != nullptr;
+    const bool lazy = own_defer && lazy_net != 0u && (sweep & (p.defer - 1)) != p.defer - 1;
+    if (own_defer) desc.R.defer = (desc.R.defer & 3) | (lazy ? kDeferLazy : kDeferWin);
+    bool idle = false;
+    if (lazy && !col_side) {
+        idle = tile != small_div(tile, R.rt_slabs) * R.rt_slabs;
+    } else if (lazy) {
+        const int ct = tile - R.n_row_tiles;
+        const int r0 = small_div(ct, R.ct_slabs) * R.ct_rows;
+        const int nr = min(R.ct_rows, R.o2 - r0);
+        idle = r0 > 0 && small_div(r0 + nr - 1, R.go) == small_div(r0 - 1, R.go);     // no multiple of go in [r0, r0 + nr)
+    }
+    const LevelWin win{a, R.partial_base, tile, sh_w};
+    if (idle) {
+        acc = 0.0;
+    } else if (!col_side) {
         if (R.rt_vec == 0) acc = dep_wait(R, dep, &sh_flag) ? short_tile<0>(R, p, tile, cur) : kTileAbandoned;
-        else if (R.rt_vec == 4) { float v[kSlotsVec4][4]; acc = row_tile<4, false>(R, p, tile, cur, dep, false, v, nothing, sh_f, sh_u, sh_g, sh_p, sh_rs, &sh_flag, tr); }
-        else { float v[kSlotsVec4][1]; acc = row_tile<1, false>(R, p, tile, cur, dep, false, v, nothing, sh_f, sh_u, sh_g, sh_p, sh_rs, &sh_flag, tr); }
+        else if (R.rt_vec == 4) { float v[kSlotsVec4][4]; acc = row_tile<4, false>(R, p, tile, cur, dep, false, v, nothing, sh_f, sh_u, sh_g, sh_p, sh_rs, &sh_flag, tr, win); }
+        else { float v[kSlotsVec4][1]; acc = row_tile<1, false>(R, p, tile, cur, dep, false, v, nothing, sh_f, sh_u, sh_g, sh_p, sh_rs, &sh_flag, tr, win); }
     } else {
         if (R.ct_vec == 0) acc = dep_wait(R, dep, &sh_flag) ? short_tile<1>(R, p, tile - R.n_row_tiles, cur) : kTileAbandoned;
-        else if (R.ct_vec == 4) { float v[kSlotsVec4][4]; acc = col_tile<4, false>(R, p, tile - R.n_row_tiles, cur, dep, false, v, nothing, sh_f, sh_u, sh_g, sh_p, &sh_flag, tr); }
-        else { float v[kSlotsVec4][1]; acc = col_tile<1, false>(R, p, tile - R.n_row_tiles, cur, dep, false, v, nothing, sh_f, sh_u, sh_g, sh_p, &sh_flag, tr); }
+        else if (R.ct_vec == 4) { float v[kSlotsVec4][4]; acc = col_tile<4, false>(R, p, tile - R.n_row_tiles, cur, dep, false, v, nothing, sh_f, sh_u, sh_g, sh_p, &sh_flag, tr, win); }
+        else { float v[kSlotsVec4][1]; acc = col_tile<1, false>(R, p, tile - R.n_row_tiles, cur, dep, false, v, nothing, sh_f, sh_u, sh_g, sh_p, &sh_flag, tr, win); }
     }
     stamp(tr, 6);
     if (acc < 0.0) return;          // abandoned wait (uniform): nothing was stored, the counter is not bumped
@@ -1109,7 +1221,8 @@ __global__ __launch_bounds__(kBlock, DFQ_LE_MIN_WAVES) void le_level_kernel(Leve
     }
     // one partial per wave (fixed butterfly order -> deterministic), no workgroup barrier
     const double t = wave_sum(acc);
-    if (lane == 0) partials[(int64_t)(R.partial_base + tile) * (kBlock / kWave) + threadIdx.x / kWave] = t;
+    const int64_t slot = (int64_t)(R.partial_base + tile) * (kBlock / kWave) + threadIdx.x / kWave;
+    if (lane == 0) partials[slot] = t;
     stamp(tr, 7);
 }
 
@@ -1497,10 +1610,218 @@ __global__ __launch_bounds__(kBlock) void le_bootstrap_kernel(const LeRelDev* __
     }
 }
 
+// The |dW| partials of deferred tiles for the sweeps 0 .. last of their window (phases), recomputed from the stored elements and
+// the remembered factors by ONE workgroup of kCtlBlock threads: thread `it % kBlock` of tile `it / kBlock` takes the registers
+// row_tile / col_tile give their thread, in the same slots, adds the same terms in the same order (window_step, slot_abs_diff)
+// and its wave leaves the same butterfly sum in the same slot of window array j.  (Waves never straddle two tiles: kCtlBlock is
+// a multiple of kBlock.)  Used where a verdict is uncertain (le_control_kernel) and where a call ends (le_resolve_kernel).
+struct LeOneway {
+    int32_t rel;        // index in the level-sorted descriptor table
+    int32_t side;       // 0: W1 (row tiles), 1: W2 (column tiles)
+};
+__device__ __forceinline__ void replay_oneway(const LeRelDev* __restrict__ rels, const LeOneway* __restrict__ ow, int n_ow, int last,
+                              double* __restrict__ win, int64_t part_stride) {
+    constexpr int NV = kSlotsVec4;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(win), "+v"(ow));
+#endif
+    for (int e = 0; e < n_ow; ++e) {
+        // (the descriptor through a vector address: its fields in vector registers -- next to the convergence launch's own
+        // values they would not fit the scalar file)
+        int rel = ow[e].rel, side = ow[e].side;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(rel), "+v"(side));
+#endif
+        const LeRelDev& R = rels[rel];
+        const bool col = side != 0;
+        const int n_tiles = col ? R.n_col_tiles : R.n_row_tiles;
+        const int vec = col ? R.ct_vec : R.rt_vec;
+        for (int it = (int)threadIdx.x; it < n_tiles * kBlock; it += kCtlBlock) {
+            const int tile = it / kBlock, tid = it % kBlock;
+            const int slot = (R.partial_base + (col ? R.n_row_tiles : 0) + tile) * (kBlock / kWave) + tid / kWave;
+            // geometry of the thread (row_tile / col_tile)
+            int n_max, row0, pos, rstep, rstride, first, n_own = 0, lane_on = 1, nr;
+            int ci[4] = {0, 0, 0, 0};
+            int go = 1, gi = 0, i0 = 0;
+            const float* w;
+            if (!col) {
+                const int rblk = small_div(tile, R.rt_slabs);
+                const int slab = tile - rblk * R.rt_slabs;
+                row0 = rblk * R.rt_rows;
+                nr = min(R.rt_rows, R.o1 - row0);
+                const int p0 = slab * R.rt_cols;
+                const int np = min(R.rt_cols, R.row_len - p0);
+                const int npv = np / vec;
+                const int JL = small_div(kBlock, npv);
+                const int jl_raw = small_div(tid, npv);
+                lane_on = jl_raw < JL;
+                const int jl = lane_on ? jl_raw : 0;
+                pos = p0 + (lane_on ? (tid - jl_raw * npv) * vec : 0);
+                n_own = lane_on ? small_div(nr - jl + JL - 1, JL) : 0;
+                n_max = min(NV, small_div(nr + JL - 1, JL));
+                rstep = JL; rstride = R.row_len;
+                w = R.w1 + ((int64_t)row0 * R.row_len + pos);
+                first = jl;
+            } else {
+                const int rblk = small_div(tile, R.ct_slabs);
+                const int slab = tile - rblk * R.ct_slabs;
+                row0 = rblk * R.ct_rows;
+                nr = min(R.ct_rows, R.o2 - row0);
+                const int row_len2 = R.i2g * R.khkw;
+                const int p0 = slab * R.ct_cols;
+                const int np = min(R.ct_cols, row_len2 - p0);
+                const int npv = np / vec;
+                int G = 1, lgG = 0;
+                while (G < npv) { G <<= 1; ++lgG; }
+                const int n_rowslots = kBlock >> lgG;
+                const int grp = tid >> lgG;
+                const int ln = tid - grp * G;
+                lane_on = ln < npv;
+                pos = p0 + min(ln, npv - 1) * vec;
+                n_max = min(NV, (nr + n_rowslots - 1) >> (8 - lgG));
+                rstep = n_rowslots; rstride = row_len2;
+                w = R.w2 + ((int64_t)row0 * row_len2 + pos);
+                i0 = small_div(p0, R.khkw);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) ci[k] = (k < vec) ? small_div(pos + k, R.khkw) - i0 : 0;
+                go = R.go; gi = R.gi;
+                first = grp;
+            }
+            float v[NV][4];
+#pragma unroll
+            for (int u = 0; u < NV; ++u) {
+                const int r = min(first + u * rstep, nr - 1);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v[u][k] = (u < n_max && k < vec) ? w[(int64_t)r * rstride + k] : 0.0f;
+            }
+            for (int j = 0; j <= last; ++j) {
+                double aw = 0.0;
+#pragma unroll
+                for (int u = 0; u < NV; ++u) {
+                    if (u >= n_max) continue;
+                    const int r_raw = first + u * rstep;
+                    const int r = min(r_raw, nr - 1);
+                    const bool ok = col ? (lane_on && r_raw < nr) : (u < n_own);
+                    if (!col) {
+                        const float* hold = R.hold;
+                        const int64_t c = row0 + r;
+                        auto h = [&](int i, int) { return hold[(int64_t)(2 * i) * R.o1 + c]; };
+                        if (vec == 4) {
+                            float t[4], nv[4];
+                            window_step<4>(v[u], j, h, t, nv);
+                            aw += slot_abs_diff<4>(ok, nv, t);
+                        } else {
+                            float x[1] = {v[u][0]}, t[1], nv[1];
+                            window_step<1>(x, j, h, t, nv);
+                            aw += slot_abs_diff<1>(ok, nv, t);
+                        }
+                    } else {
+                        const int64_t cg = (int64_t)small_div(row0 + r, go) * gi + i0;
+                        const float* hold = R.hold + R.o1;
+                        auto h = [&](int i, int k) { return hold[(int64_t)(2 * i) * R.o1 + cg + ci[k]]; };
+                        if (vec == 4) {
+                            float t[4], nv[4];
+                            window_step<4>(v[u], j, h, t, nv);
+                            aw += slot_abs_diff<4>(ok, nv, t);
+                        } else {
+                            float x[1] = {v[u][0]}, t[1], nv[1];
+                            window_step<1>(x, j, h, t, nv);
+                            aw += slot_abs_diff<1>(ok, nv, t);
+                        }
+                    }
+                }
+                const double tsum = wave_sum(aw);
+                if (threadIdx.x % kWave == 0) win[(int64_t)j * part_stride + slot] = tsum;
+            }
+        }
+    }
+}
+
+// the sum of one layer's per-wave partials: lane-strided, eight loads in flight per lane, the wave's butterfly -- the order in
+// which every mean of the convergence test is formed (`ld(i)` = the layer's i-th partial)
+template <class Ld>
+__device__ __forceinline__ double layer_sum(Ld ld, int n_l, int lane) {
+    double s = 0.0;
+    for (int i = lane; i < n_l; i += 8 * kWave) {
+        double x[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) x[u] = (i + u * kWave < n_l) ? ld(i + u * kWave) : 0.0;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += x[u];
+    }
+    return wave_sum(s);
+}
+
 struct LeNetDesc {           // one network of a (possibly batched) plan
     int32_t layer_begin, n_layers;     // its targ layers, in graph order, in the layer table
     int32_t tile_begin, n_tiles;       // its contiguous range of tile slots in the partial array
 };
+
+// Lazy sweeps of a plan (see "Lazy sweeps" in the header comment): what the convergence launch and le_resolve_kernel need
+struct LeLazy {
+    int32_t on;             // 0: every sweep reads (DFQ_LE_LAZY_DW=0, defer 1, ...)
+    int32_t defer;
+    double kappa;           // eager when the predicted bound lb^2 / lb_prev falls to kappa x threshold (0: never predicted)
+    double* win;            // [defer - 1] x part_stride partials of the deferred tiles, per phase
+    int64_t part_stride;
+    double* mean_win;       // [defer - 1] x n_layers_all layer means of the lazy sweeps, per phase
+    int64_t n_layers_all;
+    const LeRelDev* rels;   // level-sorted descriptors
+    const LeOneway* ow;     // the deferred sides of every network, network after network
+    const int32_t* ow_begin;   // [n_nets + 1]
+};
+
+// the mode of sweep `next`: lazy unless it stores anyway, the run is latched or logged, the count bound needs its exact verdict
+// (`count_hi` = exact count + unresolved sweeps) or the predicted bound comes near the threshold
+__device__ __forceinline__ int le_next_lazy(const LeLazy& lz, bool latched, bool logged, double lb_prev, int next, int count_hi, double lb,
+                                            double thres, int cc) {
+    if (!lz.on || latched || logged) return 0;
+    if ((next & (lz.defer - 1)) == lz.defer - 1) return 0;
+    if (count_hi + 1 >= cc) return 0;
+    if (lz.kappa > 0.0) {
+        const double pred = lb_prev > 0.0 ? lb * (lb / lb_prev) : lb;
+        if (pred <= lz.kappa * thres) return 0;
+    }
+    return 1;
+}
+
+// the exact (diff, count) steps of `n` unresolved sweeps j0, j0 + 1, ... of one network: the deferred layers' means from the window
+// arrays, the others as the lazy sweep kept them, summed in graph order; log entries and the last diff_tmp as the eager loop
+// leaves them.  All threads of the workgroup; the results are valid in thread 0.
+__device__ __forceinline__ void resolve_window(const LeLazy& lz, const LeLayerDiff* __restrict__ layers, const LeLayerDiff* sh_layer, double* sh_m,
+                               const LeNetDesc& nd, int n_layers, int j0, int n, double* log, int log_cap, double& diff, int& count,
+                               double& last) {
+    const int tid = threadIdx.x, lane = tid % kWave, wave = tid / kWave;
+    const int waves_per_tile = kBlock / kWave;
+    for (int q = 0; q < n; ++q) {
+        const int j = j0 + q, pj = j & (lz.defer - 1);
+        const double* kept = lz.mean_win + (int64_t)pj * lz.n_layers_all + nd.layer_begin;
+        const double* part = lz.win + (int64_t)pj * lz.part_stride;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(kept), "+v"(part));      // (vector registers: see replay_oneway)
+#endif
+        __syncthreads();
+        for (int l = wave; l < n_layers; l += kCtlBlock / kWave) {
+            const LeLayerDiff L = sh_layer[l];
+            double m = kept[l];
+            if (L.oneway) {
+                const int64_t base = (int64_t)L.partial_begin * waves_per_tile;
+                const double s = layer_sum([&](int i) { return part[base + i]; }, L.n_partials * waves_per_tile, lane);
+                m = (double)(float)(s / L.n_elems);
+            }
+            if (lane == 0) sh_m[l] = m;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double dt = 0.0;
+            for (int l = 0; l < n_layers; ++l) dt += sh_m[l];
+            if (fabs(diff - dt) > 1e-9) { count = 0; diff = dt; }
+            else { count += 1; }
+            last = dt;
+            if (log && j < log_cap) log[j] = dt;
+        }
+    }
+}
 
 // dfq.py:105-115 on the device.  One 16-wave workgroup per network: its per-wave partials and layer
 // table are staged into LDS with every load in flight at once, wave w then reduces layers w, w+16,
@@ -1518,9 +1839,10 @@ __global__ __launch_bounds__(kCtlBlock) void le_control_kernel(const LeLayerDiff
                                                                int converge_count, int max_sweeps, int uni_layers, int uni_tiles,
                                                                int n_clear, const LeCfSeg* __restrict__ cf_segs,
                                                                const LeCfRel* __restrict__ cf_rels, const int32_t* __restrict__ cf_map,
-                                                               LeParams cf_p, int cf_k0, int cf_group) {
+                                                               LeParams cf_p, int cf_k0, int cf_group, LeLazy lz) {
     __shared__ double sh_part[kCtlStage];
     __shared__ double sh_mean[1024];
+    __shared__ double sh_mean2[1024];              // the means of an unresolved sweep (resolve_window)
     __shared__ LeLayerDiff sh_layer[1024];
     const int tid = threadIdx.x;
     const int lane = tid % kWave;
@@ -1580,18 +1902,8 @@ __global__ __launch_bounds__(kCtlBlock) void le_control_kernel(const LeLayerDiff
             const int rel0 = (L.partial_begin - nd.tile_begin) * waves_per_tile;     // offset inside the staged range
             // (same order of additions as one value per trip; eight loads in flight for the part of a large network that
             // did not fit the staging buffer -- ResNet-18's 10 868 partials made this kernel 14.7 us instead of 6)
-            const int n_l = L.n_partials * waves_per_tile;
-            for (int i = lane; i < n_l; i += 8 * kWave) {
-                double x[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int idx = rel0 + i + u * kWave;
-                    x[u] = (i + u * kWave < n_l) ? ((idx < n_stage) ? sh_part[idx] : partials[part0 + idx]) : 0.0;
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) s += x[u];
-            }
-            s = wave_sum(s);
+            s = layer_sum([&](int i) { const int idx = rel0 + i; return (idx < n_stage) ? sh_part[idx] : partials[part0 + idx]; },
+                          L.n_partials * waves_per_tile, lane);
         }
         if (lane == 0) {
             // float(torch.mean(torch.abs(W - W_prev))): float32 mean, widened to double (dfq.py:108)
@@ -1600,41 +1912,87 @@ __global__ __launch_bounds__(kCtlBlock) void le_control_kernel(const LeLayerDiff
         }
     }
     __syncthreads();
-    if (wave != 0) return;
-    // diff_tmp = sum of the layer means IN GRAPH ORDER (Python's left-to-right float64 sum).  Lane l
-    // fetches mean[l] with one LDS instruction per 64 layers; the values then travel lane by lane
-    // through a shuffle so that lane 0 adds them in order (adding +0.0 for missing layers is exact).
-    // (every lane reads the same word: a broadcast; until round 5 lane l fetched mean[l] and the values travelled to lane 0 through
-    // 64 shuffles per 64 layers -- same additions in the same order, a third of the instructions)
-    double diff_tmp = 0.0;
-    {
-        const int n_lds = min(n_layers, 1024);
-        int l = 0;
-        for (; l + 8 <= n_lds; l += 8) {
-            double m[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) m[u] = sh_mean[l + u];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) diff_tmp += m[u];
-        }
-        for (; l < n_lds; ++l) diff_tmp += sh_mean[l];
-        for (; l < n_layers; ++l) diff_tmp += layer_mean[l];
+    const int k = before.sweeps;                       // the sweep this launch closes
+    const int phase = k & (lz.defer - 1);
+    const bool lazy = lz.on && before.lazy;            // (the deferred tiles of this sweep read nothing)
+    if (lazy) {
+        // a lazy sweep: the deferred layers' means are +0.0 above -- keep every mean for the sweep that resolves this one
+        double* const keep = lz.mean_win + (int64_t)phase * lz.n_layers_all + nd.layer_begin;
+        for (int l = tid; l < n_layers; l += kCtlBlock) keep[l] = (l < 1024) ? sh_mean[l] : layer_mean[l];
     }
+    // diff_tmp = sum of the layer means IN GRAPH ORDER (Python's left-to-right float64 sum), by wave 0 (every lane reads the same
+    // word: a broadcast; adding +0.0 for missing layers is exact).  `lb`: the same sum without the deferred layers -- a lower
+    // bound of diff_tmp (non-negative terms, IEEE addition monotone in each operand), equal to it in a lazy sweep.
+    __shared__ double sh_dt[2];
+    if (wave == 0) {
+        double diff_tmp = 0.0, lb = 0.0;
+        for (int l = 0; l < n_layers; ++l) {
+            const double m = (l < 1024) ? sh_mean[l] : layer_mean[l];
+            const bool ow = ((l < 1024) ? sh_layer[l].oneway : layers[l].oneway) != 0;
+            diff_tmp += m;
+            lb += ow ? 0.0 : m;
+        }
+        if (tid == 0) { sh_dt[0] = diff_tmp; sh_dt[1] = lb; }
+    }
+    __syncthreads();
+    const double diff_tmp = sh_dt[0], lb = sh_dt[1];
+    const bool max_end = max_sweeps >= 0 && k + 1 >= max_sweeps;
+    if (lazy) {
+        // go on is certain when lb > thres (diff then stays above it either way: reset to diff_tmp >= lb, or kept -- it was above
+        // the threshold or the loop would have ended) and `count` cannot reach converge_count even if every unresolved sweep
+        // and this one counted; a max_sweeps end is decided as always
+        const int unres = before.unres + 1;
+        if (max_end || (lb > converge_thres && before.count + unres < converge_count)) {
+            if (tid == 0) {
+                state->sweeps = k + 1;
+                state->unres = unres;
+                state->n_lazy = before.n_lazy + 1;
+                state->done = max_end ? 1 : 0;
+                if (!max_end) {
+                    state->happen = k + 1;
+                    state->lazy = le_next_lazy(lz, before.latched != 0, before.log != nullptr, before.lb_prev, k + 1, before.count + unres, lb,
+                                               converge_thres, converge_count);
+                    state->lb_prev = lb;
+                } else {
+                    state->lazy = 0;
+                }
+            }
+            return;
+        }
+        // uncertain: the verdict is left to le_resolve_kernel, launched right behind this launch, which reads the network's
+        // deferred layers, decides exactly and latches the network on reading sweeps.  Nothing runs in between.
+        if (tid == 0) {
+            state->sweeps = k + 1;
+            state->unres = unres;
+            state->n_lazy = before.n_lazy + 1;
+            state->lazy = -1;                          // undecided
+        }
+        return;
+    }
+    // the unresolved sweeps, in order, with their full sums: (diff, count) advanced exactly as the reference advances them
+    // (the state read again: only this workgroup writes it, and `before` held across the replay spilled scalar registers)
+    const LeState st = *state;
+    double diff = st.diff, last = st.last_diff_tmp;
+    int count = st.count;
+    if (st.unres > 0) resolve_window(lz, layers, sh_layer, sh_mean2, nd, n_layers, k - st.unres, st.unres, st.log, st.log_cap, diff, count, last);
     if (tid == 0) {
-        double diff = before.diff;
-        int count = before.count;
         if (fabs(diff - diff_tmp) > 1e-9) { count = 0; diff = diff_tmp; }
         else { count += 1; }
-        const int sweeps = before.sweeps + 1;
+        last = diff_tmp;
+        if (st.log && k < st.log_cap) st.log[k] = diff_tmp;
+        const int sweeps = k + 1;
         const bool go_on = (diff > converge_thres) && (count < converge_count) &&
                            (max_sweeps < 0 || sweeps < max_sweeps);
         state->diff = diff;
         state->count = count;
         state->sweeps = sweeps;
-        state->last_diff_tmp = diff_tmp;
+        state->last_diff_tmp = last;
         state->done = go_on ? 0 : 1;
-        if (go_on) state->happen = sweeps;                   // sweep `sweeps` (the next one) happens
-        if (before.log && before.sweeps < before.log_cap) before.log[before.sweeps] = diff_tmp;
+        state->unres = 0;
+        if (go_on) state->happen = sweeps;             // sweep `sweeps` (the next one) happens
+        state->lazy = go_on ? le_next_lazy(lz, st.latched != 0, st.log != nullptr, st.lb_prev, sweeps, count, lb,
+                                           converge_thres, converge_count) : 0;
+        state->lb_prev = lb;
     }
 }
 
@@ -1651,6 +2009,10 @@ __global__ void le_reset_kernel(LeState* states, int n_nets, double converge_thr
         const bool go_on = (10.0 > converge_thres) && (0 < converge_count) && (max_sweeps != 0);
         state->done = go_on ? 0 : 1;
         state->happen = go_on ? 0 : -1;
+        state->lazy = 0;             // the first sweep reads (lazy sweeps: le_next_lazy)
+        state->unres = 0;
+        state->lb_prev = 0.0;
+        state->latched = 0;
     }
 }
 
@@ -1673,6 +2035,10 @@ __global__ void le_prepare_kernel(ClearArgs a, LeState* states, int n_nets, doub
         const bool go_on = (10.0 > converge_thres) && (0 < converge_count) && (max_sweeps != 0);
         state->done = go_on ? 0 : 1;
         state->happen = go_on ? 0 : -1;
+        state->lazy = 0;             // the first sweep reads (lazy sweeps: le_next_lazy)
+        state->unres = 0;
+        state->lb_prev = 0.0;
+        state->latched = 0;
     }
 }
 
@@ -1808,6 +2174,55 @@ __global__ __launch_bounds__(kBlock) void le_hold_reset_kernel(const LeRelDev* _
     for (int64_t i = threadIdx.x; i < n; i += kBlock) R.hold[i] = 1.0f;
 }
 
+// End of an enqueue call of a lazy plan: the sweeps of a network that are still unresolved (lazy sweeps since its last reading
+// sweep) get their deferred layers' |dW| partials from the stored elements and the remembered factors, and their exact (diff,
+// count) steps -- before le_flush_kernel brings the elements up to date.  One workgroup per network; most leave at once.
+// Launched behind every convergence launch too (`decide`): a network whose lazy sweep ended undecided (lazy == -1) gets its
+// exact verdict here -- the sweep's go on / stop, `happen`, the next sweep's mode -- and reads in every later sweep of the run.
+__global__ __launch_bounds__(kCtlBlock) void le_resolve_kernel(const LeLayerDiff* __restrict__ layers, const LeNetDesc* __restrict__ nets,
+                                                               int uni_layers, int uni_tiles, LeState* __restrict__ states, LeLazy lz,
+                                                               int decide, double converge_thres, int converge_count, int max_sweeps) {
+    __shared__ LeLayerDiff sh_layer[1024];
+    __shared__ double sh_m[1024];
+    LeState* const state = states + blockIdx.x;
+    {
+        const LeState b = *state;
+        if (b.unres == 0 || (decide && b.lazy != -1)) return;
+    }
+    LeNetDesc nd;
+    if (uni_layers > 0) {
+        nd.layer_begin = (int)blockIdx.x * uni_layers; nd.n_layers = uni_layers;
+        nd.tile_begin = (int)blockIdx.x * uni_tiles; nd.n_tiles = uni_tiles;
+    } else {
+        nd = nets[blockIdx.x];
+    }
+    layers += nd.layer_begin;
+    for (int i = threadIdx.x; i < nd.n_layers; i += kCtlBlock) sh_layer[i] = layers[i];
+    replay_oneway(lz.rels, lz.ow + lz.ow_begin[blockIdx.x], lz.ow_begin[blockIdx.x + 1] - lz.ow_begin[blockIdx.x],
+                  (state->sweeps - 1) & (lz.defer - 1), lz.win, lz.part_stride);
+    __syncthreads();                               // (the window sums: global words of this workgroup, read back by it)
+    const LeState before = *state;                 // (read again: held across the replay it spilled scalar registers)
+    double diff = before.diff, last = before.last_diff_tmp;
+    int count = before.count;
+    resolve_window(lz, layers, sh_layer, sh_m, nd, nd.n_layers, before.sweeps - before.unres, before.unres, before.log, before.log_cap,
+                   diff, count, last);
+    if (threadIdx.x == 0) {
+        state->diff = diff;
+        state->count = count;
+        state->last_diff_tmp = last;
+        state->unres = 0;
+        if (before.lazy == -1) {
+            const bool go_on = (diff > converge_thres) && (count < converge_count) &&
+                               (max_sweeps < 0 || before.sweeps < max_sweeps);
+            state->done = go_on ? 0 : 1;
+            if (go_on) state->happen = before.sweeps;
+            state->lazy = 0;
+            state->latched = 1;
+            state->n_uncertain = before.n_uncertain + 1;
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side: the plan
 // ---------------------------------------------------------------------------------------------
@@ -1842,6 +2257,13 @@ struct dfq_le_plan {
     LeFlushRef* d_flush = nullptr;
     int32_t* d_hold_rels = nullptr;
     int n_flush = 0, n_hold_rels = 0;
+    // lazy sweeps of the deferred layers (batched plans with defer > 1; DFQ_LE_LAZY_DW=0: off, DFQ_LE_LAZY_MARGIN: kappa)
+    bool lazy = false;
+    double lazy_kappa = 1.5;
+    double* d_win = nullptr;               // [defer - 1] x part_stride
+    double* d_mean_win = nullptr;          // [defer - 1] x n_layers
+    LeOneway* d_ow = nullptr;
+    int32_t* d_ow_begin = nullptr;
     int total_tiles = 0, boot_blocks = 0;
     int64_t stat_words = 0;                // per parity, per arena
     int64_t r1_zero_words = 0;             // leading part of the R1 arena that is accumulated with atomics
@@ -2122,7 +2544,7 @@ int dfq_le_plan_create_batch(const dfq_layer* layers, int32_t n_layers, const in
     std::vector<LeRelDev> h(n_relations);
     std::vector<LeLayerDiff> ld(n_layers);
     for (int l = 0; l < n_layers; ++l) {
-        ld[l].partial_begin = -1; ld[l].n_partials = 0;
+        ld[l].partial_begin = -1; ld[l].n_partials = 0; ld[l].oneway = 0; ld[l].pad_ = 0;
         ld[l].n_elems = (double)((int64_t)layers[l].out_ch * layers[l].in_per_group * layers[l].khkw);
     }
     // (a single network large enough to stream -- ResNet-18: 11 M paired elements, 2 717 tiles of 4 096 -- has workgroups to spare
@@ -2333,8 +2755,8 @@ int dfq_le_plan_create_batch(const dfq_layer* layers, int32_t n_layers, const in
         for (int r = 0; r < n_relations && p->defer > 1; ++r) {
             LeRelDev& d = h[r];
             if (fr[r]) continue;
-            if (!d.w1_interior && d.rt_vec != 0) { d.defer |= 1; p->deferred_total += (int64_t)d.o1 * d.row_len; }
-            if (!d.w2_interior && d.ct_vec != 0) { d.defer |= 2; p->deferred_total += (int64_t)d.o2 * d.i2g * d.khkw; }
+            if (!d.w1_interior && d.rt_vec != 0) { d.defer |= 1; p->deferred_total += (int64_t)d.o1 * d.row_len; ld[relations[r].first].oneway = 1; }
+            if (!d.w2_interior && d.ct_vec != 0) { d.defer |= 2; p->deferred_total += (int64_t)d.o2 * d.i2g * d.khkw; ld[relations[r].second].oneway = 1; }
             if (d.defer) { hold_off[r] = hold_floats; hold_floats += (int64_t)2 * (p->defer - 1) * d.o1; }
         }
         if (hold_floats > 0) {
@@ -2684,6 +3106,36 @@ int dfq_le_plan_create_batch(const dfq_layer* layers, int32_t n_layers, const in
                 if ((e = p->mem.alloc((void**)&p->d_flush, sizeof(LeFlushRef) * refs.size())) != hipSuccess) return fail_alloc(e);
                 if ((e = hipMemcpy(p->d_flush, refs.data(), sizeof(LeFlushRef) * refs.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail_alloc(e);
             }
+            {
+                // lazy sweeps: every network's deferred sides, the window arrays
+                const char* lz = getenv("DFQ_LE_LAZY_DW");
+                const char* lm = getenv("DFQ_LE_LAZY_MARGIN");
+                bool small = true;
+                for (int n = 0; n < n_nets; ++n) small = small && nets[n].n_layers <= 1024;
+                p->lazy = n_nets > 1 && p->defer > 1 && !hold_rels.empty() && small && !(lz && lz[0] == '0');
+                if (lm) p->lazy_kappa = std::max(0.0, atof(lm));
+                if (p->lazy) {
+                    std::vector<LeOneway> ow;
+                    std::vector<int32_t> ow_begin(n_nets + 1, 0);
+                    for (int n = 0; n < n_nets; ++n) {
+                        ow_begin[n] = (int32_t)ow.size();
+                        for (int i : hold_rels) {
+                            if (sorted[i].net != n) continue;
+                            for (int side = 0; side < 2; ++side) if (sorted[i].defer & (1 << side)) ow.push_back(LeOneway{i, side});
+                        }
+                    }
+                    ow_begin[n_nets] = (int32_t)ow.size();
+                    const size_t nw = (size_t)(p->defer - 1);
+                    if ((e = p->mem.alloc((void**)&p->d_win, sizeof(double) * nw * p->part_stride)) != hipSuccess) return fail_alloc(e);
+                    if ((e = p->mem.alloc((void**)&p->d_mean_win, sizeof(double) * nw * n_layers)) != hipSuccess) return fail_alloc(e);
+                    if ((e = p->mem.alloc((void**)&p->d_ow, sizeof(LeOneway) * ow.size())) != hipSuccess) return fail_alloc(e);
+                    if ((e = p->mem.alloc((void**)&p->d_ow_begin, sizeof(int32_t) * ow_begin.size())) != hipSuccess) return fail_alloc(e);
+                    if ((e = hipMemcpy(p->d_ow, ow.data(), sizeof(LeOneway) * ow.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail_alloc(e);
+                    if ((e = hipMemcpy(p->d_ow_begin, ow_begin.data(), sizeof(int32_t) * ow_begin.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail_alloc(e);
+                    if ((e = hipMemset(p->d_win, 0, sizeof(double) * nw * p->part_stride)) != hipSuccess) return fail_alloc(e);
+                    if ((e = hipMemset(p->d_mean_win, 0, sizeof(double) * nw * n_layers)) != hipSuccess) return fail_alloc(e);
+                }
+            }
             if (!hold_rels.empty()) {
                 if ((e = p->mem.alloc((void**)&p->d_hold_rels, sizeof(int32_t) * hold_rels.size())) != hipSuccess) return fail_alloc(e);
                 if ((e = hipMemcpy(p->d_hold_rels, hold_rels.data(), sizeof(int32_t) * hold_rels.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail_alloc(e);
@@ -2752,6 +3204,8 @@ int dfq_le_plan_create_batch(const dfq_layer* layers, int32_t n_layers, const in
 
 // workgroups (= LDS-resident tiles) of the persistent whole-loop launch, 0 when the plan streams
 static inline bool res_on(const dfq_le_plan* p) { return p && p->resident && !p->resident_off; }
+// lazy sweeps run on le_level_kernel's launches only (not the persistent-workgroup variant, not the resident engine)
+static bool lazy_active(const dfq_le_plan* p) { return p->lazy && p->sweep_grid == 0 && !res_on(p); }
 int32_t dfq_le_plan_resident_tiles(const dfq_le_plan* p) { return res_on(p) ? le_resident_tiles(p->resident) : 0; }
 int32_t dfq_le_plan_degraded(const dfq_le_plan* p) { return p ? p->degraded : 0; }
 int32_t dfq_le_plan_uniform(const dfq_le_plan* p) { return (p && p->uni_layers > 0) ? 1 : 0; }
@@ -2764,6 +3218,7 @@ int dfq_le_plan_set_safe_mode(dfq_le_plan* p) {
     p->resident_off = true;
     p->merged = false;
     p->sweep_grid = 0;
+    p->lazy = false;
     if (p->resident_why.empty() || p->resident) p->resident_why = "safe mode: one launch per dependency level, no in-launch waits";
     return DFQ_OK;
 }
@@ -2810,6 +3265,21 @@ int64_t dfq_le_plan_ro_elements(const dfq_le_plan* p) { return p ? p->ro_total :
 // every `depth`-th; depth 1 = every sweep (resident plans, DFQ_LE_DEFER=1)
 int64_t dfq_le_plan_deferred_elements(const dfq_le_plan* p) { return (p && !res_on(p)) ? p->deferred_total : 0; }
 int32_t dfq_le_plan_defer_depth(const dfq_le_plan* p) { return (p && !res_on(p)) ? p->defer : 1; }
+// lazy sweeps of the deferred layers: 1 when the plan runs them (dfq_le.hip, "Lazy sweeps")
+int32_t dfq_le_plan_lazy(const dfq_le_plan* p) { return (p && lazy_active(p)) ? 1 : 0; }
+// out3 = (lazy sweeps, uncertain verdicts, sweeps) summed over the networks: the counts since the plan was made, the sweeps of the
+// current run (synchronises the stream)
+int dfq_le_plan_lazy_stats(dfq_le_plan* p, void* stream, int64_t* out3) {
+    if (!p || !out3) return fail_arg("dfq_le_plan_lazy_stats: null argument");
+    out3[0] = out3[1] = out3[2] = 0;
+    if (res_on(p) || !p->d_state) return DFQ_OK;
+    std::vector<LeState> h(p->n_nets);
+    hipStream_t st = (hipStream_t)stream;
+    DFQ_HIP_TRY(hipMemcpyAsync(h.data(), p->d_state, sizeof(LeState) * p->n_nets, hipMemcpyDeviceToHost, st));
+    DFQ_HIP_TRY(hipStreamSynchronize(st));
+    for (const LeState& x : h) { out3[0] += x.n_lazy; out3[1] += x.n_uncertain; out3[2] += x.sweeps; }
+    return DFQ_OK;
+}
 // free-running segments of the streaming engine (dfq_le_cf.hpp): elements (NOT part of rw_elements) of layers whose every
 // statistic is closed-form -- read and written once per `group` sweeps by le_lean_kernel; group 1 = none
 int64_t dfq_le_plan_free_running_elements(const dfq_le_plan* p) { return (p && !res_on(p)) ? p->fr_total : 0; }
@@ -2881,6 +3351,14 @@ int32_t dfq_le_plan_level_launches(const dfq_le_plan* p, int32_t level, int64_t*
 
 }  // extern "C"
 
+static LeLazy lazy_args(const dfq_le_plan* p) {
+    LeLazy z;
+    z.on = lazy_active(p) ? 1 : 0; z.defer = p->defer; z.kappa = p->lazy_kappa;
+    z.win = p->d_win; z.part_stride = p->part_stride; z.mean_win = p->d_mean_win; z.n_layers_all = p->n_layers;
+    z.rels = (const LeRelDev*)p->d_rels; z.ow = (const LeOneway*)p->d_ow; z.ow_begin = (const int32_t*)p->d_ow_begin;
+    return z;
+}
+
 static LeParams plan_params(const dfq_le_plan* p, const dfq_le_config* cfg) {
     LeParams q = make_params(cfg);
     q.defer = p->defer;
@@ -2928,6 +3406,12 @@ static int le_restart(dfq_le_plan* p, const dfq_le_config* cfg, hipStream_t st) 
 static int le_flush(dfq_le_plan* p, hipStream_t st) {
     int rcj = le_bg_join(p, st);                     // (a background lean launch stores the values the write-back starts from)
     if (rcj) return rcj;
+    if (lazy_active(p)) {
+        // the lazy sweeps' verdicts exactly, from the elements as they are stored now
+        hipLaunchKernelGGL(le_resolve_kernel, dim3(p->n_nets), dim3(kCtlBlock), 0, st, (const LeLayerDiff*)p->d_layer_diff,
+                           (const LeNetDesc*)p->d_nets, p->uni_layers, p->uni_tiles, p->d_state, lazy_args(p), 0, 0.0, 0, 0);
+        DFQ_CHECK_LAUNCH();
+    }
     if (p->n_flush == 0) return DFQ_OK;
     hipLaunchKernelGGL(le_flush_kernel, dim3(p->n_flush), dim3(kBlock), 0, st, (const LeFlushRef*)p->d_flush, (const LeState*)p->d_state,
                        p->defer, p->cf_group);
@@ -3035,6 +3519,7 @@ static int le_launch_level(dfq_le_plan* p, int launch, const LeParams& q, hipStr
     la.table = (const LeRelDev*)p->d_rels; la.blocks = table; la.p = q; la.sweep = (int32_t)p->sweep_index; la.pad = 0;
     la.state = (const LeState*)p->d_state; la.partials = sweep_partials(p); la.dep_counters = p->d_dep;
     la.err = p->d_dep + (size_t)p->n_rels * kDepStride; la.tr = tr; la.lean = (const LeLeanRef*)p->d_lean; la.part_stride = p->part_stride;
+    la.win = lazy_active(p) ? p->d_win : nullptr;
 #ifdef DFQ_EMU
     if (p->has_slab_tiles) {           // tiles wait for LATER tiles of their row block: the CPU emulation must keep the launch's workgroups alive together
         DFQ_LAUNCH_SPINNING(le_level_kernel<false>, dim3(count), dim3(kBlock), kLevelSmem, st, la);
@@ -3067,8 +3552,15 @@ static int le_launch_control(dfq_le_plan* p, const dfq_le_config* cfg, hipStream
                        (int64_t)p->r1_zero_words, (int)(p->sweep_index & 1),
                        p->d_state, cfg->converge_thres, (int)cfg->converge_count, (int)cfg->max_sweeps, p->uni_layers, p->uni_tiles,
                        n_helpers, (const LeCfSeg*)p->d_cf_segs, (const LeCfRel*)p->d_cf_rels, (const int32_t*)p->d_cf_map,
-                       plan_params(p, cfg), (int)(p->sweep_index + 1 + (p->cf_bg ? p->cf_group : 0)), p->cf_group);
+                       plan_params(p, cfg), (int)(p->sweep_index + 1 + (p->cf_bg ? p->cf_group : 0)), p->cf_group, lazy_args(p));
     DFQ_CHECK_LAUNCH();
+    if (lazy_active(p)) {
+        // the uncertain verdicts of lazy sweeps (le_resolve_kernel; a workgroup per network, all but those leave at once)
+        hipLaunchKernelGGL(le_resolve_kernel, dim3(p->n_nets), dim3(kCtlBlock), 0, st, (const LeLayerDiff*)p->d_layer_diff,
+                           (const LeNetDesc*)p->d_nets, p->uni_layers, p->uni_tiles, p->d_state, lazy_args(p), 1,
+                           cfg->converge_thres, (int)cfg->converge_count, (int)cfg->max_sweeps);
+        DFQ_CHECK_LAUNCH();
+    }
     p->sweep_index += 1;             // the control launch closes a sweep
     return DFQ_OK;
 }

@@ -31,6 +31,18 @@ struct LeState {
     // runs chunks of sweeps without the reference's exit test and all-reduces a chunk's values in ONE collective
     // (dfq_le_set_diff_log; untouched by restarts)
     double* log;
+    // streaming engine, lazy sweeps of the one-way-scaled layers (dfq_le.hip, "Lazy sweeps"): `lazy` = 1 when sweep `sweeps` (the
+    // next one) reads none of their elements; `unres` sweeps before it have a bound, not yet a value, for their |dW| sum --
+    // diff, count, last_diff_tmp and log stand where they stood before them; `lb_prev` = the previous sweep's bound (the
+    // prediction), `latched` = an uncertain verdict was met, every later sweep of this run reads; n_lazy / n_uncertain count
+    // lazy sweeps and uncertain verdicts since the plan was made (a diagnostic)
+    int32_t lazy;
+    int32_t unres;
+    double lb_prev;
+    int32_t latched;
+    int32_t n_lazy;
+    int32_t n_uncertain;
+    int32_t pad2_;
 };
 
 // Every in-launch wait is bounded: DFQ_SPIN_LIMIT polls (default: seconds), then the workgroup gives up, raises the plan's

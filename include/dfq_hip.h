@@ -150,6 +150,12 @@ int64_t dfq_le_plan_ro_elements(const dfq_le_plan* plan);
  * elements: bytes per sweep as executed, averaged over D sweeps = 8 * rw + 4 * ro - 4 * deferred * (D - 1) / D. */
 int64_t dfq_le_plan_deferred_elements(const dfq_le_plan* plan);
 int32_t dfq_le_plan_defer_depth(const dfq_le_plan* plan);
+/* 1 when the plan runs lazy sweeps: the deferred layers are read only in their storing sweep and in sweeps whose verdict
+ * needs their |dW| sums (batched plans with defer > 1; DFQ_LE_LAZY_DW=0 turns them off) */
+int32_t dfq_le_plan_lazy(const dfq_le_plan* plan);
+/* out3 = (lazy sweeps, uncertain verdicts resolved by the convergence launch, sweeps of the current run), summed over the
+ * networks; the first two count since the plan was made.  Synchronises `stream`. */
+int dfq_le_plan_lazy_stats(dfq_le_plan* plan, void* stream, int64_t* out3);
 /* Free-running segments of the streaming engine (dfq_le_cf.hpp; DFQ_LE_CF=0 switches them off, DFQ_LE_CF_GROUP = G in
  * {2, 4, 8}, default 8 for a batched plan, 4 for a single network of >= 6 M paired elements, none for a smaller one: its
  * sweep is two launch latencies, and the lean launches only add to them).  A chain of relations whose every consumed range is closed-form -- a chain's first layer (rows * s,
