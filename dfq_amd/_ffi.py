@@ -52,6 +52,11 @@ class DfqSegment(Structure):
                 ('codes', c_void_p)]
 
 
+class DfqRowSegment(Structure):
+    _fields_ = [('data', c_void_p), ('rows', c_int64), ('row_len', c_int64), ('num_bits', c_int32), ('symmetric', c_int32),
+                ('codes', c_void_p), ('ranges', c_void_p)]
+
+
 class DfqBcSource(Structure):
     _fields_ = [('fake_weight', c_void_p), ('fake_bias', c_void_p), ('channels', c_int32),
                 ('relu', c_int32), ('concat', c_int32)]
@@ -137,12 +142,16 @@ SIGNATURES = {
     'dfq_quant_plan_run': (c_int32, [c_void_p, c_void_p]),
     'dfq_quant_plan_measure': (c_int32, [c_void_p, c_void_p]),
     'dfq_quant_plan_minmax': (c_void_p, [c_void_p]),
+    'dfq_row_quant_plan_create': (c_int32, [POINTER(DfqRowSegment), c_int32, POINTER(c_void_p)]),
+    'dfq_row_quant_plan_destroy': (None, [c_void_p]),
+    'dfq_row_quant_plan_run': (c_int32, [c_void_p, c_void_p]),
     'dfq_bc_plan_create': (c_int32, [POINTER(DfqLayer), c_int32, POINTER(DfqBcStep), c_int32,
                                      POINTER(DfqBcSource), c_int32, POINTER(c_void_p)]),
     'dfq_bc_plan_create_replicated': (c_int32, [POINTER(DfqLayer), c_int32, POINTER(DfqBcStep), c_int32, POINTER(DfqBcSource), c_int32,
                                                 POINTER(c_void_p), c_int32, POINTER(c_void_p)]),
     'dfq_bc_plan_destroy': (None, [c_void_p]),
     'dfq_bc_plan_run': (c_int32, [c_void_p, c_int32, c_void_p]),
+    'dfq_bc_plan_run_per_channel': (c_int32, [c_void_p, c_int32, c_int32, c_void_p]),
     'dfq_bc_plan_status': (c_int32, [c_void_p, c_void_p]),
     'dfq_bc_plan_eps': (c_void_p, [c_void_p, c_int32]),
     'dfq_bc_plan_correction': (c_void_p, [c_void_p, c_int32]),

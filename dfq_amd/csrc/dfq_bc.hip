@@ -81,6 +81,7 @@ struct BcStepDev {
     int32_t next_tag_off;    // tagged-value slots of the next BN, or -1
     int32_t mm_index, mm_blocks, wait_cache;   // one-launch correction: the layer's arrival counter, how many min/max blocks feed it; 1: a
                                                // source is a never-rewritten BN read through a ReLU (its moment is refreshed by blocks of the launch)
+    int32_t row_base;        // per-channel runs: first entry of this layer's rows in the per-row quantiser table (fills what was padding)
     BcSourceDev src[kStepSources];   // copy of sources[source_begin ...] when source_count <= kStepSources
 };
 
@@ -103,7 +104,7 @@ struct BcFoldDev {
     float* next_cache;
     float* corr;                 // [O] out
     float* eps;                  // debug copy target is written by bc_quant_error_kernel; unused here
-    int32_t khkw, next_tag_off, src_relu, pad;
+    int32_t khkw, next_tag_off, src_relu, row_base;   // row_base: as in BcStepDev
     int32_t mm_index, mm_blocks;           // (as in BcStepDev)
 };
 
@@ -251,6 +252,60 @@ __global__ __launch_bounds__(kBlock) void bc_quant_error_kernel(const BcLayerDev
     L.eps[pair] = acc;
 }
 
+// ---- per-channel mode (an extension: per-output-channel weight quantisation, the error model of per-channel int8 deployments) ----
+// The quantiser of output row o is the reference's UniformQuantize recipe (utils/quantize.py:23-76, Python-float min/max: recipe A,
+// qparams_double) at `num_bits` with row o's own (min, max) -- what prims.fake_quant_rows applies to one tensor.  A stage in front of
+// the chain reduces every row of every corrected layer (one wave per row, one read of the weights) and leaves the row's quantiser in
+// the plan's table: {scale, min_value}, the two members of QParams that depend on the range (qmin / qmax depend on the bit width
+// alone, neg_min is -min_value exactly).  Plans that keep the eps matrices (DFQ_BC_EPS=1) get them from the same wave: the row is in
+// hand, eps[o, i] = sum_k (Q_o(W) - W)[o, i, k], sequential float32 sum from 0.0f like bc_quant_error_kernel's.
+struct BcRowLayerDev {
+    const float* w;          // [O, I/g, khkw]
+    float* eps;              // [O, I/g] debug copy, or null
+    int32_t out_ch, in_per_group, khkw, row_base;
+};
+
+__global__ __launch_bounds__(kBlock) void bc_row_range_kernel(const BcRowLayerDev* __restrict__ layers, const int32_t* __restrict__ row_begin,
+                                                              int n_layers, int total_rows, float* __restrict__ rowq, int num_bits, int symmetric) {
+    const int r = (int)blockIdx.x * (kBlock / kWave) + (int)threadIdx.x / kWave;
+    if (r >= total_rows) return;                       // (wave-uniform: the reductions below stay whole-wave)
+    const int lane = threadIdx.x % kWave;
+    const int l = bc_find(row_begin, n_layers, r);
+    const BcRowLayerDev L = layers[l];
+    const int o = r - L.row_base;
+    const int64_t len = (int64_t)L.in_per_group * L.khkw;
+    const float* w = L.w + (int64_t)o * len;
+    float mn = INFINITY, mx = -INFINITY;
+    for (int64_t i = lane; i < len; i += kWave) {
+        const float v = w[i];
+        mn = fminf(mn, v);
+        mx = fmaxf(mx, v);
+    }
+    mn = wave_min(mn);
+    mx = wave_max(mx);
+    const QParams p = qparams_double((double)mn, (double)mx, num_bits, symmetric);
+    if (lane == 0) { rowq[2 * (int64_t)r + 0] = p.scale; rowq[2 * (int64_t)r + 1] = p.min_value; }
+    if (L.eps) {
+        for (int i = lane; i < L.in_per_group; i += kWave) {
+            float acc = 0.0f, code;
+            for (int k = 0; k < L.khkw; ++k) {
+                const float v = w[(int64_t)i * L.khkw + k];
+                acc = acc + (fake_quant_one(v, p, &code) - v);
+            }
+            L.eps[(int64_t)o * L.in_per_group + i] = acc;
+        }
+    }
+}
+
+// the quantiser of row `r` of the table (see bc_row_range_kernel); `base` carries qmin / qmax of the run's bit width
+__device__ __forceinline__ QParams bc_row_qparams(const QParams& base, float scale, float min_value) {
+    QParams q = base;
+    q.scale = scale;
+    q.min_value = min_value;
+    q.neg_min = -min_value;
+    return q;
+}
+
 // dfq.py:182-184: gamma*pdf(-beta/gamma) + beta*(1 - cdf(-beta/gamma)), clipped at 0 (NaN stays NaN).
 // DFQ_BC_F32_MOMENT=1 (tuning): pdf / cdf from the float32 expf / erfcf instead of float64 exp / erf rounded to float32 (what
 // scipy gives the reference).  They differ by a few float32 ulps (<= 5e-7 absolute on a moment of order one, far inside the
@@ -370,6 +425,8 @@ struct BcDep {            // null counters: every step is its own launch (depend
     const uint32_t* mm_arrive;   // one-launch correction: per layer, the min/max blocks of THIS launch that have merged; else null
     const uint32_t* cache_arrive;   // ... and the blocks that have refreshed the cached moments of the never-rewritten BNs
     int32_t cache_blocks;
+    int32_t num_bits;     // per-channel runs (kRows bodies only): the bit width of every row's quantiser
+    const float* rowq;    // ... and the per-row quantiser table {scale, min_value} (bc_row_range_kernel)
 };
 // The error word.  Counter protocol: cleared by the run's clear launch, any non-zero value = a wait of this run was abandoned.
 // Tagged protocol (no clear launch): it holds the EPOCH of the latest run in which a wait was abandoned (atomicMax: epochs
@@ -384,9 +441,12 @@ __device__ __forceinline__ void bc_raise_err(const BcDep& dep) { atomicMax(dep.e
 // the chain is latency and nothing else) -- the body then spends two dozen registers more on settling the row sum's operands
 // before the wait.  A batch keeps the leaner body: its chain is bound by how many workgroups are resident ahead of the front
 // (80 against 119 VGPRs: the batch of 32 measured 0.46 against 0.49 ms).
-template <int kExp, bool kOneGroup>
+// kRows: per-channel mode -- every row has its own quantiser (dep.rowq, staged through sh_q), at dep.num_bits; the per-tensor
+// instantiations (kRows = false) compile to what they were.
+template <int kExp, bool kOneGroup, bool kRows = false>
 __device__ __forceinline__ void bc_step_body(const BcStepDev& st, int blk, const BcSourceDev* __restrict__ sources,
-                                             const BcFoldDev* __restrict__ folds, const BcDep& dep, float* sh_E, float* sh_corr, int* sh_flag) {
+                                             const BcFoldDev* __restrict__ folds, const BcDep& dep, float* sh_E, float* sh_corr, int* sh_flag,
+                                             float* sh_q = nullptr) {
     const int tid = threadIdx.x;
     const int lane = tid % kWave;
     const int wave = tid / kWave;
@@ -453,7 +513,24 @@ __device__ __forceinline__ void bc_step_body(const BcStepDev& st, int blk, const
         __syncthreads();
         if (*sh_flag == 0) return;           // abandoned: nothing has been stored
     }
-    const QParams qp = qparams_double((double)slot_min(mm_slot(st.mm + dep.mm_off + 0)), (double)slot_max(mm_slot(st.mm + dep.mm_off + 1)), 8, dep.symmetric);
+    const QParams qp = kRows ? qparams_double(0.0, 0.0, dep.num_bits, dep.symmetric)      // (qmin / qmax only: the rows bring the rest)
+                             : qparams_double((double)slot_min(mm_slot(st.mm + dep.mm_off + 0)), (double)slot_max(mm_slot(st.mm + dep.mm_off + 1)), 8, dep.symmetric);
+    if (kRows) {
+        // the quantisers of this workgroup's rows, staged in LDS (one global load per row, requested behind the weights)
+        if (tid < rpb) {
+            const int o = min(blk * rpb + tid, st.out_ch - 1);
+            const float* q = dep.rowq + 2 * ((int64_t)st.row_base + o);
+            sh_q[2 * tid + 0] = q[0];
+            sh_q[2 * tid + 1] = q[1];
+        }
+        __syncthreads();
+    }
+    // quantiser of the row behind register slot `row_u` (clamped into the workgroup's rows like the loads)
+    auto slot_qp = [&](int row_u) {
+        if (!kRows) return qp;
+        const int li = min(min(row_u, st.out_ch - 1) - blk * rpb, rpb - 1);
+        return bc_row_qparams(qp, sh_q[2 * li + 0], sh_q[2 * li + 1]);
+    };
     // Everything of the matvec that does not depend on the expectation is settled here, before the wait: where in sh_E each
     // slot's factor will lie (a byte offset < 64 Ki, two per register) and which slots take part at all (a slot outside the
     // row or the layer holds eps = 0: its product is a zero of either sign, and adding one to a sum that started at +0.0
@@ -483,9 +560,10 @@ __device__ __forceinline__ void bc_step_body(const BcStepDev& st, int blk, const
                     if (u == 0) off0 = off;
                     eo[u >> 1] |= off << (16 * (u & 1));
                 }
+                const QParams uq = slot_qp(row_u);
                 if (khkw == 1) {
                     const float v = ev[u];
-                    ev[u] = (DFQ_BC_ABLATE & 8) ? v : 0.0f + (fake_quant_one(v, qp, &code) - v);
+                    ev[u] = (DFQ_BC_ABLATE & 8) ? v : 0.0f + (fake_quant_one(v, uq, &code) - v);
                 } else {
                     const int row = min(row_u, st.out_ch - 1);
                     const int col = min(col_u, in - 1);
@@ -493,7 +571,7 @@ __device__ __forceinline__ void bc_step_body(const BcStepDev& st, int blk, const
                     float acc = 0.0f;
                     for (int k = 0; k < khkw; ++k) {
                         const float v = wp[k];
-                        acc = (DFQ_BC_ABLATE & 8) ? acc + v : acc + (fake_quant_one(v, qp, &code) - v);
+                        acc = (DFQ_BC_ABLATE & 8) ? acc + v : acc + (fake_quant_one(v, uq, &code) - v);
                     }
                     ev[u] = acc;
                 }
@@ -531,7 +609,8 @@ __device__ __forceinline__ void bc_step_body(const BcStepDev& st, int blk, const
         if (F.next_bn_bias) f_nb = F.next_bn_bias[o_tail];
         if (F.next_cache) f_nw = F.next_bn_weight[o_tail];
         if (dep.mm_arrive) mm_wait(dep.mm_arrive + F.mm_index, F.mm_blocks);      // (the few threads that own a row of it; an abandoned wait is noticed behind the merges)
-        const QParams fq = qparams_double((double)slot_min(mm_slot(F.mm + dep.mm_off + 0)), (double)slot_max(mm_slot(F.mm + dep.mm_off + 1)), 8, dep.symmetric);
+        const QParams fq = kRows ? bc_row_qparams(qp, dep.rowq[2 * ((int64_t)F.row_base + o_tail) + 0], dep.rowq[2 * ((int64_t)F.row_base + o_tail) + 1])
+                                 : qparams_double((double)slot_min(mm_slot(F.mm + dep.mm_off + 0)), (double)slot_max(mm_slot(F.mm + dep.mm_off + 1)), 8, dep.symmetric);
         float acc = 0.0f, code;
 #pragma unroll
         for (int k = 0; k < kFoldTaps; ++k)
@@ -668,6 +747,7 @@ __device__ __forceinline__ void bc_step_body(const BcStepDev& st, int blk, const
         const int o = min(row0, st.out_ch - 1);
         const float* ex = sh_E + bc_small_div(o, step_o) * in;
         const float* wr = st.w + (int64_t)o * in * khkw;
+        const QParams oq = slot_qp(o);
         double acc = 0.0;
 #pragma unroll
         for (int u = 0; u < kBcRegs; ++u) {
@@ -678,7 +758,7 @@ __device__ __forceinline__ void bc_step_body(const BcStepDev& st, int blk, const
             float er = 0.0f, code;
             for (int k = 0; k < khkw; ++k) {
                 const float v = wr[(int64_t)i * khkw + k];
-                er = er + (fake_quant_one(v, qp, &code) - v);
+                er = er + (fake_quant_one(v, oq, &code) - v);
             }
             acc += (double)er * (double)ex[i];
         }
@@ -842,6 +922,24 @@ __global__ __launch_bounds__(kBlock) void bc_step_kernel(BcStepDev st_inline, co
     bc_step_body<kExp, false>(desc.st, blockIdx.x, sources, folds, BcDep{nullptr, nullptr, -1, 0, -1, 0, nullptr, 0u, symmetric, 0, 0, nullptr, nullptr, 0}, sh_E, sh_corr, &sh_flag);
 }
 
+// ... per-channel mode (the quantiser of every row from the table of bc_row_range_kernel, at `num_bits`)
+template <int kExp>
+__global__ __launch_bounds__(kBlock) void bc_step_kernel_rows(BcStepDev st_inline, const BcStepDev* __restrict__ table,
+                                                              const BcSourceDev* __restrict__ sources, const BcFoldDev* __restrict__ folds, int symmetric,
+                                                              int num_bits, const float* __restrict__ rowq) {
+    __shared__ float sh_E[kExp];
+    __shared__ float sh_corr[kBlock];
+    __shared__ float sh_q[2 * kBlock];
+    __shared__ int sh_flag;
+    union { BcStepDev st; uint32_t u[kStepWords]; } desc;
+    if (table) bc_load_step(table + blockIdx.y, desc.u);
+    else desc.st = st_inline;
+    if ((int)blockIdx.x * desc.st.rows_per_block >= desc.st.out_ch) return;
+    bc_step_body<kExp, false, true>(desc.st, blockIdx.x, sources, folds,
+                                    BcDep{nullptr, nullptr, -1, 0, -1, 0, nullptr, 0u, symmetric, 0, 0, nullptr, nullptr, 0, num_bits, rowq},
+                                    sh_E, sh_corr, &sh_flag, sh_q);
+}
+
 // the whole chain of every network in one launch: 1-D grid over (step, workgroup) in chain order; a workgroup waits
 // for the previous step of its network (lower indices only -> no deadlock, see dfq_le.hip)
 // One-launch correction (round 5): the per-tensor min/max blocks are workgroups of the chain launch.  The plan interleaves them with
@@ -867,16 +965,13 @@ struct BcFusedMm {
 };
 
 // (the batch body at 64 VGPRs -- amdgpu_waves_per_eu(8, 8): 17 registers spilled to scratch -- measured 0.44 against 0.40 ms)
-template <int kExp, bool kOneGroup>
-__global__ __launch_bounds__(kBlock) void bc_chain_kernel(const BcStepDev* __restrict__ table,
-                                                          const BcChainRef* __restrict__ refs,
-                                                          const BcSourceDev* __restrict__ sources, const BcFoldDev* __restrict__ folds,
-                                                          uint32_t* counters, uint32_t* err, unsigned long long* tags, uint32_t epoch,
-                                                          int symmetric, int spin_limit, int mm_off, uint32_t* slots_clear, int n_slots_clear,
-                                                          BcFusedMm fm) {
-    __shared__ float sh_E[kExp];
-    __shared__ float sh_corr[kBlock];
-    __shared__ int sh_flag;
+template <int kExp, bool kOneGroup, bool kRows>
+__device__ __forceinline__ void bc_chain_block(const BcStepDev* __restrict__ table, const BcChainRef* __restrict__ refs,
+                                               const BcSourceDev* __restrict__ sources, const BcFoldDev* __restrict__ folds,
+                                               uint32_t* counters, uint32_t* err, unsigned long long* tags, uint32_t epoch,
+                                               int symmetric, int spin_limit, int mm_off, uint32_t* slots_clear, int n_slots_clear,
+                                               const BcFusedMm& fm, int num_bits, const float* rowq,
+                                               float* sh_E, float* sh_corr, int* sh_flag, float* sh_q) {
     typedef int ivec4 __attribute__((vector_size(16)));
     // the tagged chain has no clear launch in front of it: its first workgroup clears the (min, max) slots the NEXT run's
     // min/max launch accumulates into (the other parity: nobody touches it in this run)
@@ -898,10 +993,40 @@ __global__ __launch_bounds__(kBlock) void bc_chain_kernel(const BcStepDev* __res
     }
     union { BcStepDev st; uint32_t u[kStepWords]; } desc;
     bc_load_step(table + step, desc.u);
-    bc_step_body<kExp, kOneGroup>(desc.st, blk, sources, folds,
+    bc_step_body<kExp, kOneGroup, kRows>(desc.st, blk, sources, folds,
                        BcDep{counters, err, __builtin_amdgcn_readfirstlane(ref[2]), __builtin_amdgcn_readfirstlane(ref[3]), step, 0,
-                             tags, epoch, symmetric, spin_limit, mm_off, fm.arrive, fm.cache_arrive, fm.cache_blocks},
-                       sh_E, sh_corr, &sh_flag);
+                             tags, epoch, symmetric, spin_limit, mm_off, fm.arrive, fm.cache_arrive, fm.cache_blocks, num_bits, rowq},
+                       sh_E, sh_corr, sh_flag, sh_q);
+}
+
+template <int kExp, bool kOneGroup>
+__global__ __launch_bounds__(kBlock) void bc_chain_kernel(const BcStepDev* __restrict__ table,
+                                                          const BcChainRef* __restrict__ refs,
+                                                          const BcSourceDev* __restrict__ sources, const BcFoldDev* __restrict__ folds,
+                                                          uint32_t* counters, uint32_t* err, unsigned long long* tags, uint32_t epoch,
+                                                          int symmetric, int spin_limit, int mm_off, uint32_t* slots_clear, int n_slots_clear,
+                                                          BcFusedMm fm) {
+    __shared__ float sh_E[kExp];
+    __shared__ float sh_corr[kBlock];
+    __shared__ int sh_flag;
+    bc_chain_block<kExp, kOneGroup, false>(table, refs, sources, folds, counters, err, tags, epoch, symmetric, spin_limit, mm_off,
+                                           slots_clear, n_slots_clear, fm, 8, nullptr, sh_E, sh_corr, &sh_flag, nullptr);
+}
+
+// ... per-channel mode (every row's quantiser from the table of bc_row_range_kernel, at `num_bits`)
+template <int kExp, bool kOneGroup>
+__global__ __launch_bounds__(kBlock) void bc_chain_kernel_rows(const BcStepDev* __restrict__ table,
+                                                               const BcChainRef* __restrict__ refs,
+                                                               const BcSourceDev* __restrict__ sources, const BcFoldDev* __restrict__ folds,
+                                                               uint32_t* counters, uint32_t* err, unsigned long long* tags, uint32_t epoch,
+                                                               int symmetric, int spin_limit, int mm_off, uint32_t* slots_clear, int n_slots_clear,
+                                                               BcFusedMm fm, int num_bits, const float* __restrict__ rowq) {
+    __shared__ float sh_E[kExp];
+    __shared__ float sh_corr[kBlock];
+    __shared__ float sh_q[2 * kBlock];
+    __shared__ int sh_flag;
+    bc_chain_block<kExp, kOneGroup, true>(table, refs, sources, folds, counters, err, tags, epoch, symmetric, spin_limit, mm_off,
+                                          slots_clear, n_slots_clear, fm, num_bits, rowq, sh_E, sh_corr, &sh_flag, sh_q);
 }
 
 }  // namespace dfq
@@ -951,6 +1076,13 @@ struct dfq_bc_plan {
     int n_cache_segs = 0, cache_total = 0;
     hipStream_t capture_stream = nullptr;  // private stream used only to record the graph
     hipGraphExec_t exec[2] = {nullptr, nullptr};   // recorded run, by `symmetric`
+    // per-channel mode (dfq_bc_plan_run_per_channel), set up by its first run: one {scale, min_value} per output row of every step
+    // (row_base of a step = its first row), the per-step descriptors of bc_row_range_kernel, and the recorded runs by (symmetric, bits)
+    int total_rows = 0;
+    float* d_rowq = nullptr;
+    BcRowLayerDev* d_row_layers = nullptr;
+    int32_t* d_row_begin = nullptr;
+    std::map<int, hipGraphExec_t> exec_rows;
 };
 
 extern "C" {
@@ -960,6 +1092,7 @@ void dfq_bc_plan_destroy(dfq_bc_plan* p) {
     dfq::dev_quiesce();                                  // nothing in flight may still use the blocks released below
     p->mem.release();
     for (auto& e : p->exec) if (e) (void)hipGraphExecDestroy(e);
+    for (auto& e : p->exec_rows) if (e.second) (void)hipGraphExecDestroy(e.second);
     if (p->capture_stream) (void)hipStreamDestroy(p->capture_stream);
     delete p;
 }
@@ -1048,7 +1181,7 @@ int dfq_bc_plan_create(const dfq_layer* layers, int32_t n_layers, const dfq_bc_s
         mm_blocks += (pairs * L.khkw + mm_chunk - 1) / mm_chunk;
         qe_blocks += (L.khkw == 1) ? (pairs + kBlock * kQePairs - 1) / (kBlock * kQePairs) : (pairs + kBlock - 1) / kBlock;
     }
-    if (mm_blocks > 0x7fffffff || qe_blocks > 0x7fffffff) return fail_arg("dfq_bc_plan_create: too large");
+    if (mm_blocks > 0x7fffffff || qe_blocks > 0x7fffffff || corr_total > 0x7fffffff - kBlock) return fail_arg("dfq_bc_plan_create: too large");
 
     dfq_bc_plan* p = new dfq_bc_plan();
     p->n_steps = n_steps;
@@ -1144,6 +1277,7 @@ int dfq_bc_plan_create(const dfq_layer* layers, int32_t n_layers, const dfq_bc_s
         BcStepDev& d = p->steps[s];
         d.w = L.weight; d.mm = p->d_slots + 2 * s; d.khkw = L.khkw; d.fold = -1;
         d.mm_index = s; d.mm_blocks = (int32_t)((hl[s].n + mm_chunk - 1) / mm_chunk); d.wait_cache = 0;
+        d.row_base = (int32_t)corr_off;
         d.eps = p->keep_eps ? p->d_eps + eps_off : nullptr; d.bias = L.bias; d.next_bn_bias = steps[s].next_bn_bias; d.corr = p->d_corr + corr_off;
         d.out_ch = L.out_ch; d.in_per_group = L.in_per_group; d.source_begin = steps[s].source_begin;
         d.source_count = steps[s].source_count; d.expect_len = expect_len[s];
@@ -1205,7 +1339,7 @@ int dfq_bc_plan_create(const dfq_layer* layers, int32_t n_layers, const dfq_bc_s
             const BcStepDev& d = p->steps[D];
             F.w = d.w; F.mm = d.mm; F.bias = d.bias; F.next_bn_bias = d.next_bn_bias; F.next_bn_weight = d.next_bn_weight;
             F.next_cache = d.next_cache; F.corr = d.corr; F.eps = nullptr; F.khkw = d.khkw; F.next_tag_off = d.next_tag_off;
-            F.src_relu = src.relu ? 1 : 0; F.pad = 0; F.mm_index = d.mm_index; F.mm_blocks = d.mm_blocks;
+            F.src_relu = src.relu ? 1 : 0; F.row_base = d.row_base; F.mm_index = d.mm_index; F.mm_blocks = d.mm_blocks;
             p->steps[P].fold = (int)folds.size();
             folds.push_back(F);
             folded_into[D] = P;
@@ -1431,7 +1565,7 @@ int dfq_bc_plan_create(const dfq_layer* layers, int32_t n_layers, const dfq_bc_s
     return DFQ_OK;
 }
 
-static int bc_run_direct(dfq_bc_plan* p, int32_t symmetric, hipStream_t st);
+static int bc_run_direct(dfq_bc_plan* p, int32_t symmetric, hipStream_t st, int row_bits = 0);
 
 int dfq_bc_plan_run(dfq_bc_plan* p, int32_t symmetric, void* stream) {
     if (!p) return fail_arg("dfq_bc_plan_run: null plan");
@@ -1455,8 +1589,54 @@ int dfq_bc_plan_run(dfq_bc_plan* p, int32_t symmetric, void* stream) {
     return DFQ_OK;
 }
 
-static int bc_run_direct(dfq_bc_plan* p, int32_t symmetric, hipStream_t st) {
+// Per-channel mode (extension; the per-output-channel counterpart of dfq.py:216-219): the correction of dfq_bc_plan_run with the
+// quantiser of every weight row formed from that row's own (min, max) at `num_bits` bits (utils/quantize.py:23-76, recipe A).  Every
+// hand-over protocol of the plan is kept; the per-row quantisers come from bc_row_range_kernel, a launch in front of the chain.
+int dfq_bc_plan_run_per_channel(dfq_bc_plan* p, int32_t symmetric, int32_t num_bits, void* stream) {
+    if (!p) return fail_arg("dfq_bc_plan_run_per_channel: null plan");
+    if (num_bits < 2 || num_bits > 16) return fail_arg("dfq_bc_plan_run_per_channel: num_bits %d outside [2, 16]", (int)num_bits);
+    hipStream_t st = as_stream(stream);
+    if (!p->d_rowq) {
+        // the per-row tables, once per plan (host copies of the steps carry everything)
+        std::vector<BcRowLayerDev> rl(p->n_steps);
+        std::vector<int32_t> rb(p->n_steps + 1);
+        for (int s = 0; s < p->n_steps; ++s) {
+            const BcStepDev& d = p->steps[s];
+            rl[s].w = d.w; rl[s].eps = p->keep_eps ? const_cast<float*>(p->eps_ptr[s]) : nullptr;
+            rl[s].out_ch = d.out_ch; rl[s].in_per_group = d.in_per_group; rl[s].khkw = d.khkw; rl[s].row_base = d.row_base;
+            rb[s] = d.row_base;
+        }
+        const int total = p->n_steps ? p->steps.back().row_base + p->steps.back().out_ch : 0;
+        rb[p->n_steps] = total;
+        DFQ_HIP_TRY(p->mem.alloc((void**)&p->d_row_layers, sizeof(BcRowLayerDev) * p->n_steps));
+        DFQ_HIP_TRY(p->mem.alloc((void**)&p->d_row_begin, sizeof(int32_t) * (p->n_steps + 1)));
+        DFQ_HIP_TRY(p->mem.alloc((void**)&p->d_rowq, sizeof(float) * 2 * (size_t)total));
+        DFQ_HIP_TRY(hipMemcpy(p->d_row_layers, rl.data(), sizeof(BcRowLayerDev) * p->n_steps, hipMemcpyHostToDevice));
+        DFQ_HIP_TRY(hipMemcpy(p->d_row_begin, rb.data(), sizeof(int32_t) * (p->n_steps + 1), hipMemcpyHostToDevice));
+        p->total_rows = total;
+    }
+    const char* ge = getenv("DFQ_GRAPH");
+    if (!(ge && ge[0] == '1')) return bc_run_direct(p, symmetric, st, num_bits);
+    hipGraphExec_t& exec = p->exec_rows[(symmetric ? 1 : 0) + 2 * num_bits];
+    if (!exec) {
+        if (!p->capture_stream) DFQ_HIP_TRY(hipStreamCreate(&p->capture_stream));
+        DFQ_HIP_TRY(hipStreamBeginCapture(p->capture_stream, hipStreamCaptureModeThreadLocal));
+        const int rc = bc_run_direct(p, symmetric, p->capture_stream, num_bits);
+        hipGraph_t graph = nullptr;
+        const hipError_t ee = hipStreamEndCapture(p->capture_stream, &graph);
+        if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+        if (ee != hipSuccess) return fail_hip(ee, "hipStreamEndCapture", __FILE__, __LINE__);
+        DFQ_HIP_TRY(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+        (void)hipGraphDestroy(graph);
+    }
+    DFQ_HIP_TRY(hipGraphLaunch(exec, st));
+    return DFQ_OK;
+}
+
+// row_bits: 0 = per-tensor (dfq_bc_plan_run), else the bit width of a per-channel run
+static int bc_run_direct(dfq_bc_plan* p, int32_t symmetric, hipStream_t st, int row_bits) {
     const bool chain = p->merged && p->chain_blocks > 0;
+    const bool rows = row_bits > 0;
     // (the NULL stream is a caller's stream like any other: `capture_stream` is null until a graph is recorded, and until round 5
     //  a run on the NULL stream compared equal to it -- counter protocol, no guard: 250 instead of 130 us for a MobileNetV2)
     const bool capturing = p->capture_stream != nullptr && st == p->capture_stream;
@@ -1480,13 +1660,28 @@ static int bc_run_direct(dfq_bc_plan* p, int32_t symmetric, hipStream_t st) {
     const int cache_blocks = (p->cache_total + kBlock - 1) / kBlock;
     // one-launch correction: the min/max blocks are workgroups of the tagged chain launch below
     const bool one_launch = tagged_run && p->fused_mm;
-    if (!one_launch) {
+    if (rows) {
+        // per-channel: every row's quantiser (and, for DFQ_BC_EPS=1 plans, the eps matrices) in front of everything that reads them
+        hipLaunchKernelGGL(bc_row_range_kernel, dim3((p->total_rows + kBlock / kWave - 1) / (kBlock / kWave)), dim3(kBlock), 0, st,
+                           (const BcRowLayerDev*)p->d_row_layers, (const int32_t*)p->d_row_begin, p->n_steps, p->total_rows, p->d_rowq,
+                           row_bits, (int)symmetric);
+        DFQ_CHECK_LAUNCH();
+    }
+    if (!one_launch && rows) {
+        // per-channel: nobody reads the per-tensor (min, max) -- only the cached ReLU moments are refreshed
+        if (cache_blocks > 0) {
+            hipLaunchKernelGGL(bc_minmax_kernel, dim3(cache_blocks), dim3(kBlock), 0, st, (const BcLayerDev*)p->d_layers,
+                               (const int32_t*)p->d_mm_begin, p->n_steps, slots, 0,
+                               (const BcCacheSeg*)p->d_cache_segs, p->n_cache_segs, p->cache_total, p->mm_chunk);
+            DFQ_CHECK_LAUNCH();
+        }
+    } else if (!one_launch) {
         hipLaunchKernelGGL(bc_minmax_kernel, dim3(p->minmax_blocks + cache_blocks), dim3(kBlock), 0, st, (const BcLayerDev*)p->d_layers,
                            (const int32_t*)p->d_mm_begin, p->n_steps, slots, p->minmax_blocks,
                            (const BcCacheSeg*)p->d_cache_segs, p->n_cache_segs, p->cache_total, p->mm_chunk);
         DFQ_CHECK_LAUNCH();
     }
-    if (p->keep_eps) {
+    if (p->keep_eps && !rows) {
         hipLaunchKernelGGL(bc_quant_error_kernel, dim3(p->qerr_blocks), dim3(kBlock), 0, st, (const BcLayerDev*)p->d_layers,
                            (const int32_t*)p->d_qe_begin, p->n_steps, (const uint32_t*)slots, 8, (int)symmetric);
         DFQ_CHECK_LAUNCH();
@@ -1508,10 +1703,17 @@ static int bc_run_direct(dfq_bc_plan* p, int32_t symmetric, hipStream_t st) {
         const int grid_blocks = one_launch ? p->chain_blocks_fused : p->chain_blocks;
         const BcChainRef* ref_table = one_launch ? p->d_refs_fused : p->d_refs;
 #define DFQ_BC_CHAIN_LAUNCH(EXP, ONE)                                                                                                  \
+        do { if (rows)                                                                                                                 \
+            hipLaunchKernelGGL((bc_chain_kernel_rows<EXP, ONE>), dim3(grid_blocks), dim3(kBlock), 0, st, (const BcStepDev*)p->d_steps, \
+                               ref_table, (const BcSourceDev*)p->d_sources, (const BcFoldDev*)p->d_folds, p->d_counters,                \
+                               err, tags, p->epoch, (int)symmetric, spin_limit, mm_off,                                                 \
+                               tagged_run ? p->d_slots + (parity ^ 1) * (3 * p->n_steps + 1) : nullptr, 3 * p->n_steps + 1, fm,         \
+                               row_bits, (const float*)p->d_rowq);                                                                      \
+        else                                                                                                                           \
         hipLaunchKernelGGL((bc_chain_kernel<EXP, ONE>), dim3(grid_blocks), dim3(kBlock), 0, st, (const BcStepDev*)p->d_steps,             \
                            ref_table, (const BcSourceDev*)p->d_sources, (const BcFoldDev*)p->d_folds, p->d_counters,                    \
                            err, tags, p->epoch, (int)symmetric, spin_limit, mm_off,                                                     \
-                           tagged_run ? p->d_slots + (parity ^ 1) * (3 * p->n_steps + 1) : nullptr, 3 * p->n_steps + 1, fm)
+                           tagged_run ? p->d_slots + (parity ^ 1) * (3 * p->n_steps + 1) : nullptr, 3 * p->n_steps + 1, fm); } while (0)
         if (p->max_expect <= kExpectSmall) { if (p->one_group) DFQ_BC_CHAIN_LAUNCH(kExpectSmall, true); else DFQ_BC_CHAIN_LAUNCH(kExpectSmall, false); }
         else { if (p->one_group) DFQ_BC_CHAIN_LAUNCH(kExpectMax, true); else DFQ_BC_CHAIN_LAUNCH(kExpectMax, false); }
 #undef DFQ_BC_CHAIN_LAUNCH
@@ -1520,7 +1722,14 @@ static int bc_run_direct(dfq_bc_plan* p, int32_t symmetric, hipStream_t st) {
     }
     for (const auto& L : p->launches) {
         const BcStepDev* table = (L.n == 1) ? nullptr : p->d_steps + L.begin;
-        if (L.max_expect <= kExpectSmall)
+        if (rows) {
+            if (L.max_expect <= kExpectSmall)
+                hipLaunchKernelGGL(bc_step_kernel_rows<kExpectSmall>, dim3(L.max_blocks, L.n), dim3(kBlock), 0, st, p->launch_steps[L.begin], table,
+                                   (const BcSourceDev*)p->d_sources, (const BcFoldDev*)p->d_folds, (int)symmetric, row_bits, (const float*)p->d_rowq);
+            else
+                hipLaunchKernelGGL(bc_step_kernel_rows<kExpectMax>, dim3(L.max_blocks, L.n), dim3(kBlock), 0, st, p->launch_steps[L.begin], table,
+                                   (const BcSourceDev*)p->d_sources, (const BcFoldDev*)p->d_folds, (int)symmetric, row_bits, (const float*)p->d_rowq);
+        } else if (L.max_expect <= kExpectSmall)
             hipLaunchKernelGGL(bc_step_kernel<kExpectSmall>, dim3(L.max_blocks, L.n), dim3(kBlock), 0, st,
                                p->launch_steps[L.begin], table, (const BcSourceDev*)p->d_sources, (const BcFoldDev*)p->d_folds, (int)symmetric);
         else

@@ -1225,18 +1225,23 @@ class BCPlan:
         """From now on one launch per chain position: nothing waits, nothing can be abandoned (dfq_bc_plan_set_safe_mode)."""
         _ffi.check(_ffi.lib().dfq_bc_plan_set_safe_mode(self._plan))
 
-    def run(self, signed=False, check=False, recover=True):
+    def run(self, signed=False, check=False, recover=True, per_channel=False, bits=8):
         """Enqueue the whole correction (asynchronous).  ``check`` synchronises; with ``recover`` (default) a run in which a
         workgroup of the one-launch chain gave up its wait (DFQ_ERR_ABANDONED) is then REPEATED instead of raised: biases and BN
         proxies go back to a device-side copy taken in front of the run, the plan switches to one launch per chain position for
         good (``set_safe_mode``) and the correction runs again (``repeated`` counts it).  Without ``check`` nothing is copied
-        and an abandoned run surfaces at the next ``status()``."""
+        and an abandoned run surfaces at the next ``status()``.
+
+        ``per_channel`` (extension): the quant error of output row o is Q_o(W) - W with row o's own (min, max) at ``bits``
+        bits (2..16; dfq_bc_plan_run_per_channel).  The per-tensor mode ignores ``bits`` (8, like dfq.py:218)."""
+        if per_channel:
+            _check_bits(bits)
         guard = check and recover and self.has_waits
         if guard:
             if self._snapshot is None:
                 self._snapshot = _Snapshot(self._mutable)
             self._snapshot.take()
-        _ffi.check(_ffi.lib().dfq_bc_plan_run(self._plan, int(bool(signed)), _ffi.stream_arg()))
+        self._launch(signed, per_channel, bits)
         if check:
             try:
                 self.status()
@@ -1247,8 +1252,14 @@ class BCPlan:
                 self.set_safe_mode()
                 self.repeated += 1
                 degraded_runs['bc'] += 1
-                _ffi.check(_ffi.lib().dfq_bc_plan_run(self._plan, int(bool(signed)), _ffi.stream_arg()))
+                self._launch(signed, per_channel, bits)
                 self.status()
+
+    def _launch(self, signed, per_channel, bits):
+        if per_channel:
+            _ffi.check(_ffi.lib().dfq_bc_plan_run_per_channel(self._plan, int(bool(signed)), int(bits), _ffi.stream_arg()))
+        else:
+            _ffi.check(_ffi.lib().dfq_bc_plan_run(self._plan, int(bool(signed)), _ffi.stream_arg()))
 
     @property
     def tagged(self):
@@ -1403,11 +1414,21 @@ def _bc_tables_cached(graph, bottoms, targ_type, bn_type):
     return layers, steps, [t['keys'][li] for (li, _, _) in t['steps']]
 
 
-def bias_correction(graph, bottoms, targ_type, bits_weight=8, bn_type=torch.nn.BatchNorm2d, signed=False):
+def _check_bits(bits):
+    """Bit widths of the per-channel quantisers: an int in [2, 16]."""
+    if isinstance(bits, bool) or not isinstance(bits, int) or not 2 <= bits <= 16:
+        raise ValueError('per-channel bit width must be an int in [2, 16], got {!r}'.format(bits))
+
+
+def bias_correction(graph, bottoms, targ_type, bits_weight=8, bn_type=torch.nn.BatchNorm2d, signed=False, per_channel=False):
     """Analytic bias correction: b -= eps . E[x], propagated into the next BN's beta~.
 
     ``bits_weight`` is accepted and ignored -- the reference hard-codes 8 bits (dfq.py:218).
+    ``per_channel=True`` (extension): eps is the quant error of a per-output-channel quantiser -- row o quantised with its own
+    (min, max) at ``bits_weight`` bits (2..16, else ValueError) -- the error a per-channel int8 deployment makes.
     """
+    if per_channel:
+        _check_bits(bits_weight)
     print("Start bias correction")
     with torch.no_grad(), _cache_lock:
         layers, steps, _ = _bc_tables_cached(graph, bottoms, targ_type, bn_type)
@@ -1422,7 +1443,7 @@ def bias_correction(graph, bottoms, targ_type, bits_weight=8, bn_type=torch.nn.B
                 scope.prefetch([x for (w, b, g) in layers for x in (w, b)] +
                                [x for st in steps for (fw, fb, relu, concat) in st[1] for x in (fw, fb)] + [st[2] for st in steps])
             tk = lambda t: _tensor_key(t, dev, scope)    # noqa: E731
-            key = (_env_key(),) + tuple((tk(w), tk(b), g) for (w, b, g) in layers) + tuple(
+            key = (_env_key(), 'per_channel' if per_channel else 'per_tensor') + tuple((tk(w), tk(b), g) for (w, b, g) in layers) + tuple(
                 (li, tuple((tk(fw), tk(fb), bool(relu), bool(cat)) for (fw, fb, relu, cat) in srcs), tk(nxt)) for (li, srcs, nxt, _) in steps)
         except _Uncacheable:
             key = None
@@ -1438,7 +1459,7 @@ def bias_correction(graph, bottoms, targ_type, bits_weight=8, bn_type=torch.nn.B
             if key is not None:
                 _cache_put(_bc_plan_cache, key, (plan,))
         try:
-            plan.run(signed=signed, check=True)
+            plan.run(signed=signed, check=True, per_channel=per_channel, bits=bits_weight if per_channel else 8)
         except Exception as exc:
             if key is not None:
                 _cache_drop(_bc_plan_cache, key)

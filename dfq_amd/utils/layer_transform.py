@@ -100,16 +100,22 @@ def merge_batchnorm(model, graph, bottoms, targ_type=[QConv2d]):
     return model
 
 
-def quantize_targ_layer(graph, bit_weight=8, bits_bias=16, targ_type=None, return_codes=False):
+def quantize_targ_layer(graph, bit_weight=8, bits_bias=16, targ_type=None, return_codes=False, per_channel=False, signed=False):
     """Per-tensor asymmetric fake-quant of every targ layer's weight (and bias unless 32 bit).
 
     Two launches for the whole network: one multi-tensor min/max, one multi-tensor quantise.
     ``return_codes`` (extension) additionally returns {key: int32 code tensor of the weight}.
+    ``signed`` (extension): the symmetric recipe for the weights.
+    ``per_channel`` (extension): every weight row (output channel) is quantised with its own (min, max); biases stay per
+    tensor.  ONE launch for the whole network (dfq_row_quant_plan).  With ``return_codes`` the result is
+    ``(graph, codes, ranges)``: ranges[key] = float32 [O, 2], the (min, max) each row was quantised with.
     """
     print("Quantizing Layer parameters")
     if bits_bias == 32:
         print("Skipping bias quantization (32 bits)")
     assert targ_type != None, "targ_type cannot be None!"
+    if per_channel:
+        return _quantize_targ_layer_rows(graph, bit_weight, bits_bias, targ_type, return_codes, signed)
     lib = _ffi.lib()
     with torch.no_grad():
         stage = _ffi.entry_stage()
@@ -124,7 +130,7 @@ def quantize_targ_layer(graph, bit_weight=8, bits_bias=16, targ_type=None, retur
             if return_codes:
                 c = stage.new(w.shape, dtype=torch.int32)
                 codes[key] = c
-            segs.append(_ffi.DfqSegment(w.data_ptr(), w.numel(), int(bit_weight), 0, c.data_ptr() if c is not None else None))
+            segs.append(_ffi.DfqSegment(w.data_ptr(), w.numel(), int(bit_weight), int(bool(signed)), c.data_ptr() if c is not None else None))
             keep.append(w)
             if layer.bias is not None and bits_bias < 32:
                 b = stage.bind(layer.bias)
@@ -142,6 +148,49 @@ def quantize_targ_layer(graph, bit_weight=8, bits_bias=16, targ_type=None, retur
         stage.writeback()
     if return_codes:
         return graph, codes
+    return graph
+
+
+def _quantize_targ_layer_rows(graph, bit_weight, bits_bias, targ_type, return_codes, signed):
+    """quantize_targ_layer(per_channel=True): weight rows with their own ranges, biases per tensor (a segment of one row)."""
+    for bits in (bit_weight,) + ((bits_bias,) if bits_bias < 32 else ()):
+        if isinstance(bits, bool) or not isinstance(bits, int) or not 2 <= bits <= 16:
+            raise ValueError('per-channel quantisation needs bit widths in [2, 16], got {!r}'.format(bits))
+    lib = _ffi.lib()
+    with torch.no_grad():
+        stage = _ffi.entry_stage()
+        segs, keep, codes, ranges = [], [], {}, {}
+        stage.prefetch([t for layer in graph.values() if type(layer) in targ_type for t in (layer.weight, layer.bias)])
+        for key in graph:
+            layer = graph[key]
+            if type(layer) not in targ_type:
+                continue
+            w = stage.bind(layer.weight)
+            rows = int(w.shape[0])
+            c = r = None
+            if return_codes:
+                c = stage.new(w.shape, dtype=torch.int32)
+                r = stage.new((rows, 2))
+                codes[key], ranges[key] = c, r
+            segs.append(_ffi.DfqRowSegment(w.data_ptr(), rows, w.numel() // rows, int(bit_weight), int(bool(signed)),
+                                           c.data_ptr() if c is not None else None, r.data_ptr() if r is not None else None))
+            keep.append(w)
+            if layer.bias is not None and bits_bias < 32:
+                b = stage.bind(layer.bias)
+                segs.append(_ffi.DfqRowSegment(b.data_ptr(), 1, b.numel(), int(bits_bias), 0, None, None))
+                keep.append(b)
+        if segs:
+            arr = (_ffi.DfqRowSegment * len(segs))(*segs)
+            plan = ctypes.c_void_p()
+            _ffi.check(lib.dfq_row_quant_plan_create(arr, len(segs), ctypes.byref(plan)))
+            try:
+                _ffi.check(lib.dfq_row_quant_plan_run(plan, _ffi.stream_arg()))
+                _ffi.synchronize()
+            finally:
+                lib.dfq_row_quant_plan_destroy(plan)
+        stage.writeback()
+    if return_codes:
+        return graph, codes, ranges
     return graph
 
 

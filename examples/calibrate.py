@@ -3,6 +3,7 @@
 
     python examples/calibrate.py [--net mobilenet_v2] [--seed 0] [--bits-weight 8] [--bits-bias 16]
                                  [--absorption] [--distill-range] [--table model_int8_tensor.table]
+                                 [--per-channel [--signed]]
 
 A synthetic, randomly initialised network stands in for the pretrained checkpoint (no network access);
 everything after "model built" is what a user of the reference runs, with only the imports changed
@@ -10,6 +11,8 @@ everything after "model built" is what a user of the reference runs, with only t
 bias correction -> weight/bias fake-quant -> analytic activation ranges -> ncnn calibration table; with
 --distill-range (main_cls.py:86-113, :183-186): ZeroQ-distilled batches from the UNFOLDED model's BatchNorm statistics, then
 activation ranges recorded by running them through the quantised model instead of the analytic ranges.
+With --per-channel (extension): bias correction for a per-output-channel weight quantiser at --bits-weight, per-channel
+weight quantisation, and a per-channel calibration table; --signed selects the symmetric recipe for both.
 Needs an MI355X (the engine has no CPU path).
 """
 import argparse
@@ -70,6 +73,8 @@ def main(argv=None):
     ap.add_argument('--image-size', type=int, default=32)
     ap.add_argument('--table', default=None, help='write the ncnn int8 calibration table here')
     ap.add_argument('--device', default='cuda')
+    ap.add_argument('--per-channel', action='store_true', help='per-output-channel weight quantisation (correction, weights, table)')
+    ap.add_argument('--signed', action='store_true', help='with --per-channel: the symmetric weight quantiser')
     args = ap.parse_args(argv)
 
     model, graph, bottoms = synthetic.build(args.net, seed=args.seed)      # main_cls.py:91-135 (model + traced graph)
@@ -92,13 +97,19 @@ def main(argv=None):
     sweeps = engine.last_equalization['sweeps']
     if args.absorption:
         bias_absorption(graph, res, bottoms, 3)                                                     # :156
-    bias_correction(graph, bottoms, targ_layer, bits_weight=args.bits_weight)                       # :175
+    if args.per_channel:
+        bias_correction(graph, bottoms, targ_layer, bits_weight=args.bits_weight, signed=args.signed, per_channel=True)
+    else:
+        bias_correction(graph, bottoms, targ_layer, bits_weight=args.bits_weight)                   # :175
     if args.distill_range:                                                                           # :183-186
         set_update_stat(model, [QuantMeasure], True)
         model = update_quant_range(model, data_distill, graph, bottoms)
         set_update_stat(model, [QuantMeasure], False)
     else:
-        graph = quantize_targ_layer(graph, args.bits_weight, args.bits_bias, targ_layer)            # :181
+        if args.per_channel:
+            graph = quantize_targ_layer(graph, args.bits_weight, args.bits_bias, targ_layer, per_channel=True, signed=args.signed)
+        else:
+            graph = quantize_targ_layer(graph, args.bits_weight, args.bits_bias, targ_layer)        # :181
         set_quant_minmax(graph, bottoms, verbose=False)                                             # :188
     if args.device == 'cuda':
         torch.cuda.synchronize()
@@ -109,7 +120,7 @@ def main(argv=None):
           '{:.1f} ms wall for the whole calibration section'.format(args.net, sum(type(graph[k]) in targ_layer for k in graph),
                                                                      n_w, len(res), sweeps, levels, dt * 1e3))
     if args.table:
-        lines = ncnn_table.write_calibration_table(args.table, graph, targ_type=targ_layer)
+        lines = ncnn_table.write_calibration_table(args.table, graph, targ_type=targ_layer, per_channel=args.per_channel)
         print('wrote {} lines to {}'.format(len(lines), args.table))
     return model, graph, bottoms
 

@@ -355,6 +355,25 @@ int dfq_quant_plan_measure(dfq_quant_plan* plan, void* stream);
 /* device float32[2*n_segs] min/max pairs of the last run / measure (valid after the stream reaches it) */
 const float* dfq_quant_plan_minmax(const dfq_quant_plan* plan);
 
+/* Per-output-channel weight quantisation (extension; the per-channel counterpart of quantize_targ_layer,
+ * utils/layer_transform.py:279-296): every segment is a [rows, row_len] matrix whose row r is fake-quantised in
+ * place with its OWN (min, max) -- utils/quantize.py:23-76 UniformQuantize, Python-float min/max recipe, as
+ * dfq_fake_quant_rows.  A per-tensor segment (a bias) is a segment of one row.  ONE launch for all segments. */
+typedef struct dfq_row_quant_plan dfq_row_quant_plan;
+typedef struct dfq_row_segment {
+    float* data;            /* device [rows, row_len], quantised in place                 */
+    int64_t rows;
+    int64_t row_len;
+    int32_t num_bits;       /* 2..16                                                      */
+    int32_t symmetric;
+    int32_t* codes;         /* device int32[rows * row_len] or NULL                       */
+    float* ranges;          /* device float32[rows, 2]: (min, max) each row used, or NULL */
+} dfq_row_segment;
+
+int dfq_row_quant_plan_create(const dfq_row_segment* segs, int32_t n_segs, dfq_row_quant_plan** out_plan);
+void dfq_row_quant_plan_destroy(dfq_row_quant_plan* plan);
+int dfq_row_quant_plan_run(dfq_row_quant_plan* plan, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Lazy-scale equalisation (opt-in extension): the sweeps of dfq.py:83-101 with a GIVEN sweep count,
  * computed from the pristine weights and the cumulative scale vectors of utils/relation.py:20-24 -- a sweep only READS
@@ -422,6 +441,11 @@ void dfq_bc_plan_destroy(dfq_bc_plan* plan);
  * the quant-error row sums eps[o, i] = sum_k (Q(w) - w) of its rows (8 bit, dfq.py:216-219) in registers, straight from
  * the weights: 8 B per weight for the whole pass.  Asynchronous. */
 int dfq_bc_plan_run(dfq_bc_plan* plan, int32_t symmetric, void* stream);
+/* Per-channel mode (extension; dfq.py:216-219 with a per-output-channel quantiser): the same correction, but the quant
+ * error of output row o is Q_o(W) - W with Q_o the recipe of utils/quantize.py:23-76 (Python-float min/max) built from
+ * row o's own (min, max) at `num_bits` (2..16) bits.  One more launch in front of the chain reduces every row; every
+ * hand-over protocol of the plan is kept.  DFQ_ERR_ARG for a null plan or a bad bit width.  Asynchronous. */
+int dfq_bc_plan_run_per_channel(dfq_bc_plan* plan, int32_t symmetric, int32_t num_bits, void* stream);
 /* device pointers into the plan's scratch (tests): the correction vector bias[O] of a step; eps[O*I/g] only for plans
  * created with DFQ_BC_EPS=1 in the environment (debug: one more launch materialises the row sums the chain computes on the
  * fly, same arithmetic) -- NULL otherwise */
