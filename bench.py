@@ -1,11 +1,16 @@
 #!/usr/bin/env python
 """Headline benchmark: conv weights calibrated per second by the LE+BC pass over synthetic MobileNetV2 graphs
-(BASELINE.json configs[1]: `--relu --equalize --correction`, 53 layers), plus one measured entry per other
-BASELINE configuration in the same JSON line.
+(BASELINE.json configs[1]: `--relu --equalize --correction`, 53 layers), plus, with `--full`, one measured entry per
+other BASELINE configuration in the same JSON line.
 
   python bench.py --gpus 1 --steps 20 --warmup 3
+  python bench.py --gpus 1 --steps 20 --warmup 3 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes `--dump-outputs` and
+prints the line.  `--full` adds everything below "Next to it" (and the one-unit split `config.one_unit_alone_ms`);
+each of those takes runs of its own, and together they are most of a full run's wall time.
 
 Headline (`value`).  A step = one complete pass of the hot path over a batch of `--batch` networks (distinct seeds)
 whose folded weights are already resident in HBM: cross_layer_equalization until every network's reference
@@ -15,7 +20,7 @@ own) followed by bias_correction.  Every step runs on its own replicas (in-place
 never synchronises between launches.  Multi-GPU: the unit that shards without any exchange is a network; rank r
 calibrates its own replicas, `value` = weights calibrated by all ranks / max-over-ranks time -> "scaling": "weak".
 
-Next to it, measured by the same run and reported in the same line:
+Next to it, measured by the same run with `--full` and reported in the same line:
   latency   one single-network pass with nothing else in flight (what main_cls.py would feel), with its own
             roofline fraction;
   config.others   configs[2] ResNet-18, configs[3] DeepLab on one GPU -- through the reference's own data-dependent loop (46
@@ -85,6 +90,10 @@ def parse():
     ap.add_argument('--lazy-steps', type=int, default=6, help='timed steps of the opt-in lazy-scale formulation; 0 disables')
     ap.add_argument('--dump-outputs', metavar='DIR', default='', help='write what the last timed step computed to DIR/<name>.npy '
                     '(dump_outputs); "" disables')
+    ap.add_argument('--full', action=argparse.BooleanOptionalAction, default=False,
+                    help='also measure everything besides the headline: one-unit split, latency, roofline, the other configs '
+                    '(--others, --act-shape, --lazy-steps, --distill, --pcie, --sharded) and the CPU baseline; --no-full: the '
+                    'headline alone (the default)')
     args = ap.parse_args()
     if args.steps < 1:
         ap.error('--steps must be at least 1')
@@ -106,14 +115,38 @@ def prepare(net, seed, dev):
     return model, graph, bottoms, rels
 
 
+def replicate(proto, share_tensors=False):
+    """A copy of a prepared network: (None, graph, bottoms, relations), every module and relation its own.  Same values as
+    copy.deepcopy(proto) at a fraction of the host time: deepcopy rebuilds every module's hook tables object by object, 14 ms
+    per MobileNetV2, and every unit make_unit builds takes one copy per network.  The graphs hold leaf modules only; no unit uses the
+    model around them, so it is not copied.
+    Every tensor is a clone, unless `share_tensors`: then the copy's parameters are new Parameter objects over the prototype's
+    storage and its buffers are the prototype's -- for a batch laid out by NetworkBatch, which copies every tensor a plan touches
+    into its own allocation and re-points the copy's modules at it (a clone would only be copied once more and dropped)."""
+    _, graph, bottoms, rels = proto
+
+    def module(m):
+        assert not m._modules, 'replicate: {} has submodules'.format(type(m).__name__)
+        c = copy.copy(m)
+        c.__dict__.update({k: copy.copy(v) for k, v in m.__dict__.items() if isinstance(v, (dict, set))})
+        with torch.no_grad():
+            c._parameters.update({n: type(p)(p.data if share_tensors else p.data.clone(), p.requires_grad)
+                                  for n, p in m._parameters.items() if p is not None})
+            if not share_tensors:
+                c._buffers.update({n: b.clone() for n, b in m._buffers.items() if b is not None})
+        return c
+    return (None, {k: module(m) if isinstance(m, nn.Module) else m for k, m in graph.items()},
+            copy.deepcopy(bottoms), copy.deepcopy(rels))
+
+
 ARENA = os.environ.get('DFQ_BENCH_ARENA', '1') != '0'      # batches as one allocation (dfq_amd/arena.py); 0: tensors where torch put them
 
 
 def make_unit(protos):
-    """One unit of work = a batch of networks calibrated together: deep copies of the prototypes plus
+    """One unit of work = a batch of networks calibrated together: copies of the prototypes (replicate) plus
     one LE plan and one BC plan over the whole batch (a batch of 1 is an ordinary single-network plan)."""
     from dfq_amd import arena, dfq
-    nets = [copy.deepcopy(p) for p in protos]
+    nets = [replicate(p, share_tensors=ARENA and len(protos) > 1) for p in protos]
     if len(nets) == 1:
         t0 = time.perf_counter()
         model, graph, bottoms, rels = nets[0]
@@ -122,7 +155,7 @@ def make_unit(protos):
         return dict(nets=nets, le=le, bc=bc, plan_build_ms=(time.perf_counter() - t0) * 1e3)
     if ARENA:
         # the batch is put together ONCE as one allocation with a fixed stride per network (part of loading the models, like
-        # the deep copy above); a plan is then one network's tables + a base address per network
+        # the copies above); a plan is then one network's tables + a base address per network
         t0 = time.perf_counter()
         batch = arena.NetworkBatch([(g, b, r) for (_, g, b, r) in nets], TARG)
         t1 = time.perf_counter()
@@ -132,6 +165,50 @@ def make_unit(protos):
     le = dfq.build_le_plan_batch([(g, r) for (_, g, _, r) in nets], TARG)
     bc = dfq.build_bc_plan_batch([(g, b) for (_, g, b, _) in nets], TARG)
     return dict(nets=nets, le=le, bc=bc, plan_build_ms=(time.perf_counter() - t0) * 1e3)
+
+
+def copy_unit(unit):
+    """Another unit of work over the same networks as `unit`, a batch laid out by NetworkBatch that has not run yet: a device
+    copy of its allocation and the same plans moved onto the copy.  Every pointer in a batch's tables lies inside the first
+    network's slot (arena.py checks it), so the tables NetworkBatch would build for the copy are the unit's own, shifted by the
+    distance between the two allocations.  One copy and two plan creations instead of replicating and laying out the whole
+    batch again (0.4 s of host time per MobileNetV2 batch of 64); the copy has no network objects (`nets` is None)."""
+    import numpy as np
+    from dfq_amd import dfq
+    src = unit['batch']
+    t0 = time.perf_counter()
+    storage = src.storage.clone()
+    t1 = time.perf_counter()
+    base = src.storage.data_ptr()
+    shift = np.uint64((storage.data_ptr() - base) % (1 << 64))
+
+    def tables(T):
+        t = dfq._Tables()
+        for key, a in T.arrays.items():
+            a = a.copy()
+            for field in (a.dtype.names or ()):
+                if a.dtype[field] == np.uint64:
+                    col = a[field]
+                    col[col != 0] += shift
+            t.arrays[key] = a
+        t.n_layers, t.keep, t.mutable, t.bases = T.n_layers, [storage], [storage], src.bases + shift
+        return t
+    le_t, bc_t = tables(src._le), tables(src._bc)
+    le_t.n_relations = src._le.n_relations
+    le_t.scale_cum = [storage[(s.data_ptr() - base) // 4:][:s.numel()] for s in src._scale_cum]
+    bc_t.n_steps, bc_t.n_sources = src._bc.n_steps, src._bc.n_sources
+    bc_t.step_out_ch, bc_t.step_in = src._bc.step_out_ch, src._bc.step_in
+    le, bc = dfq.LEPlan(le_t, None, stage=src.stage), dfq.BCPlan(bc_t, None, stage=src.stage)
+    return dict(nets=None, le=le, bc=bc, storage=storage, layout_ms=(t1 - t0) * 1e3, plan_build_ms=(time.perf_counter() - t1) * 1e3)
+
+
+def make_units(protos, n):
+    """`n` units over the same prototypes.  A batch laid out as one allocation is built once and copied (copy_unit) for the
+    others; it comes last, so that it is still untouched when they are copied and the last unit keeps its network objects."""
+    last = make_unit(protos)
+    if 'batch' not in last:
+        return [make_unit(protos) for _ in range(n - 1)] + [last]
+    return [copy_unit(last) for _ in range(n - 1)] + [last]
 
 
 DUMP_SAMPLE = 1 << 19             # --dump-outputs: weights (biases) sampled over the whole batch
@@ -463,7 +540,7 @@ def lazy_scale_pass(protos, net_sweeps, steps, warm, net='mobilenet_v2'):
     from dfq_amd import dfq
     units = []
     for _ in range(steps + warm + 1):
-        nets = [copy.deepcopy(p) for p in protos]
+        nets = [replicate(p) for p in protos]
         units.append(dict(nets=nets, le=dfq.LazyLEPlan([(g, r) for (_, g, _, r) in nets], TARG),
                           bc=dfq.build_bc_plan_batch([(g, b) for (_, g, b, _) in nets], TARG)))
 
@@ -642,7 +719,7 @@ def sharded_single_network(spec, steps, dev, dist, rank, world):
     def fresh(n):
         reps = []
         for _ in range(n):
-            model, graph, bottoms, rels = copy.deepcopy(proto)
+            _, graph, bottoms, rels = replicate(proto)
             eq = sharded.ShardedEqualizer(graph, rels, TARG)            # partition + the owned components' plan (untimed)
             bc, _ = dfq.build_bc_plan(graph, bottoms, TARG)
             reps.append((eq, bc, graph))
@@ -725,7 +802,7 @@ def main():
             raise SystemExit('launch with torch.distributed.run --nproc-per-node {}'.format(args.gpus))
     dev = _device(local_rank)
     dist = None
-    if world > 1 or args.sharded:
+    if world > 1 or (args.full and args.sharded):
         import torch.distributed as dist_mod
         os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
         if world == 1:                                     # the sharded pass needs a (one-rank) group
@@ -755,7 +832,9 @@ def main():
 
     # sweep counts of the reference's convergence loop on these inputs (device-side loop, untimed); the
     # timed steps enqueue the largest one, every network still stops at its own count
-    probe = make_unit(protos)
+    # the units of the timed steps and, first, the probe: all copied before any of them runs
+    units = make_units(protos, args.steps + args.warmup + 1)
+    probe = units.pop(0)
     probe['le'].run()
     net_sweeps = [r['sweeps'] for r in probe['le'].query_all()[0]]
     sweeps = args.sweeps if args.sweeps > 0 else max(net_sweeps)
@@ -768,8 +847,6 @@ def main():
     rw, ro = probe['le'].rw_elements, probe['le'].ro_elements
     sweep_bytes, defer_depth, deferred = probe['le'].sweep_bytes, probe['le'].defer_depth, probe['le'].deferred_elements
     fr_elems, fr_group = probe['le'].free_running_elements, probe['le'].free_running_group     # (dfq_le_cf.hpp)
-
-    units = [make_unit(protos) for _ in range(args.steps + args.warmup)]
 
     force = dict(converge_thres=-1.0, converge_count=10 ** 9) if args.force_sweeps else {}
 
@@ -829,16 +906,6 @@ def main():
         last = units[-1]
         dump_outputs(args.dump_outputs, last, [r['sweeps'] for r in last['le'].query_all()[0]])
 
-    # where a step's time goes: the two halves of one unit on an otherwise idle GPU (one stream)
-    br_units = [make_unit(protos) for _ in range(3)]
-    with _stream_ctx(streams[0]):
-        for u in br_units[:1]:
-            step(u)
-        _sync()
-        le_ms = sum(_gpu_elapsed_ms(lambda u=u: u['le'].enqueue(sweeps, restart=True, max_sweeps=sweeps, **force))
-                    for u in br_units[1:]) / 2
-        bc_ms = sum(_gpu_elapsed_ms(lambda u=u: u['bc'].run()) for u in br_units[1:]) / 2
-
     out = {
         'metric': 'conv weights calibrated/sec (LE+BC pass, MobileNetV2)' if args.net == 'mobilenet_v2'
                   else 'conv weights calibrated/sec (LE+BC pass, {})'.format(args.net),
@@ -862,12 +929,11 @@ def main():
             'networks_per_step': batch * world,
             'launches_per_sweep': levels + 1,
             'units_in_flight_per_gpu': n_streams,
-            'one_unit_alone_ms': {'equalization': le_ms, 'bias_correction': bc_ms},
             # host-side, once per batch, outside the timed region (like graph tracing / BN folding): descriptor and
             # launch tables of the two plans, small device allocations, one synchronisation
             'plan_build_ms_per_unit': sum(u['plan_build_ms'] for u in units) / len(units),
             'batch_layout': ('one allocation, fixed stride per network (dfq_amd/arena.py NetworkBatch); a plan = the first network\'s '
-                             'tables + {} base addresses'.format(batch)) if ARENA and batch > 1 else 'tensors where torch allocated them',
+                             'tables + {} base addresses; laid out once, every other unit a device copy of that allocation (copy_unit)'.format(batch)) if ARENA and batch > 1 else 'tensors where torch allocated them',
             'batch_layout_ms_per_unit': sum(u.get('layout_ms', 0.0) for u in units) / len(units),
         },
     }
@@ -881,10 +947,26 @@ def main():
                                      'network; device tables from a free list), then the timed step; excludes fx tracing, BN folding, relation '
                                      'pairing and laying the batch out as one allocation (once per architecture / per network / per batch, '
                                      'when the models are loaded: batch_layout_ms_per_unit)'}
+    if not args.full:
+        finish(out, rank, dist)
+        return
+
+    # ---- --full: everything below takes runs of its own, after the headline has been measured ----
+    # where a step's time goes: the two halves of one unit on an otherwise idle GPU (one stream)
+    br_units = [make_unit(protos) for _ in range(3)]
+    with _stream_ctx(streams[0]):
+        for u in br_units[:1]:
+            step(u)
+        _sync()
+        le_ms = sum(_gpu_elapsed_ms(lambda u=u: u['le'].enqueue(sweeps, restart=True, max_sweeps=sweeps, **force))
+                    for u in br_units[1:]) / 2
+        bc_ms = sum(_gpu_elapsed_ms(lambda u=u: u['bc'].run()) for u in br_units[1:]) / 2
+    out['config']['one_unit_alone_ms'] = {'equalization': le_ms, 'bias_correction': bc_ms}
+
     if ARENA and batch > 1 and rank == 0:
         # the same plans over tensors left where torch allocated them: 7 000 addresses gathered in Python per batch
         from dfq_amd import dfq
-        nets = [copy.deepcopy(p) for p in protos]
+        nets = [replicate(p) for p in protos]
         _sync()
         t0 = time.perf_counter()
         le_g = dfq.build_le_plan_batch([(g, r) for (_, g, _, r) in nets], TARG)
@@ -1045,13 +1127,18 @@ def main():
         out['cpu_baseline'], cpu_sweeps = cpu_baseline(args.net, rank * 1000, args.cpu_seconds)
         if args.sweeps == 0 and cpu_sweeps != net_sweeps[0]:      # a parity failure: say so IN the line (and fail after printing it)
             out['cpu_baseline_error'] = 'engine needed {} sweeps, the CPU oracle {}'.format(net_sweeps[0], cpu_sweeps)
+    finish(out, rank, dist)
+    if rank == 0 and 'cpu_baseline_error' in out:
+        raise SystemExit('bench.py: ' + out['cpu_baseline_error'])
+
+
+def finish(out, rank, dist):
+    """Rank 0 prints the line; every rank leaves the process group together."""
     if rank == 0:
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0 and 'cpu_baseline_error' in out:
-        raise SystemExit('bench.py: ' + out['cpu_baseline_error'])
 
 
 if __name__ == '__main__':

@@ -1,5 +1,6 @@
 """TEST INFRASTRUCTURE: run bench.py / __graft_entry__.smoke() logic on the CPU emulation (tiny net) to
-catch Python-level mistakes before spending GPU minutes.   python tests/emu/dryrun.py [more bench.py arguments]"""
+catch Python-level mistakes before spending GPU minutes.   python tests/emu/dryrun.py [more bench.py arguments]
+The dry run is a `--full` one; `--no-full` among the arguments makes it a plain run (the headline alone)."""
 import ctypes
 import os
 import sys
@@ -38,14 +39,14 @@ bench._stream_ctx = lambda s: contextlib.nullcontext()
 world = int(os.environ.get('WORLD_SIZE', '1'))
 extra = sys.argv[1:]               # appended to bench.py's arguments (the last of a repeated option wins)
 sys.argv = ['bench.py', '--net', 'tiny_mobile', '--steps', '2', '--warmup', '1', '--cpu-seconds', '0.2', '--streams', '1', '--batch', '2',
-            '--gpus', str(world), '--others', 'tiny_res,tiny_mobile:3', '--act-shape', '4,3,8,8', '--sharded', 'tiny_mobile:4,tiny_res:3',
+            '--gpus', str(world), '--full', '--others', 'tiny_res,tiny_mobile:3', '--act-shape', '4,3,8,8', '--sharded', 'tiny_mobile:4,tiny_res:3',
             '--sharded-steps', '2', '--distill', 'tiny_mobile:2:4,3,16,16', '--pcie', 'tiny_mobile', '--lazy-steps', '1'] + extra
 bench._BACKEND = 'gloo'            # the process group of bench.py over gloo (tests/test_bench_multirank.py)
 if world > 1:
     # the multi-rank run checks the rank protocol (barrier, MAX over ranks, one line from rank 0) and the sharded pass; the
     # single-network legs are the single-rank run's business
     sys.argv = ['bench.py', '--net', 'tiny_mobile', '--steps', '2', '--warmup', '1', '--cpu-seconds', '0', '--streams', '1', '--batch', '2',
-                '--gpus', str(world), '--others', '', '--act-shape', '', '--sharded', 'tiny_mobile:4,tiny_res:3', '--sharded-steps', '2',
+                '--gpus', str(world), '--full', '--others', '', '--act-shape', '', '--sharded', 'tiny_mobile:4,tiny_res:3', '--sharded-steps', '2',
                 '--distill', '', '--pcie', '', '--lazy-steps', '0'] + extra
     bench.main()
     sys.exit(0)

@@ -95,6 +95,34 @@ def test_bench_line_contract_single_rank():
     assert 'reference' in c          # the committed reference-CPU record (null for nets it was not measured on)
 
 
+FULL_ONLY = ('roofline', 'latency', 'cpu_baseline', 'sharded', 'lazy_scale', 'value_lazy_scale', 'value_single_network',
+             'pcie_inclusive', 'pcie_inclusive_ms')
+
+
+def test_bench_plain_line_is_the_headline_alone():
+    """Without --full (the default) bench.py sets up, warms up, times the steps and prints the line: the headline fields
+    the measurement contract names, and none of what only --full measures."""
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
+        env.pop(k, None)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'emu', 'dryrun.py'), '--no-full'], env=env, cwd=ROOT,
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith('{"metric"')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
+                'vs_baseline', 'dtype', 'data', 'config'):
+        assert key in d, key
+    assert d['metric'] == 'conv weights calibrated/sec (LE+BC pass, tiny_mobile)' and d['unit'] == 'weights/s'
+    assert d['higher_is_better'] is True and d['dtype'] == 'f32' and d['steps'] == 2 and d['warmup'] == 1
+    assert abs(d['value'] - d['config']['networks_per_step'] * 5000 / (d['ms_per_step'] * 1e-3)) < 1e-6 * d['value']
+    assert not [k for k in d if k in FULL_ONLY or k.endswith('_error')]
+    assert not [k for k in ('others', 'activation_ranges', 'distill_range', 'one_unit_alone_ms', 'single_pass_latency_ms')
+                if k in d['config']]
+    assert 'plan_build_ms_per_unit_scattered_tensors' not in d['host_inclusive']
+
+
 DUMP_FILES = {'le_sweeps', 'weights_net0', 'biases_net0', 'weights_sample', 'weights_sample_index', 'biases_sample',
               'biases_sample_index'}
 
@@ -181,3 +209,86 @@ def test_bench_dump_samples_a_large_batch_at_fixed_places(monkeypatch, tmp_path)
     assert 900 < idx.size <= 1000 and np.all(np.diff(idx) > 0) and idx[-1] < 3 * flat[0].size
     assert np.array_equal(load('a', 'weights_sample'), np.concatenate(flat)[idx.astype(np.int64)])
     assert np.array_equal(load('a', 'weights_net0'), flat[0]) and load('a', 'le_sweeps').tolist() == [1, 2, 3]
+
+
+def test_bench_replica_is_a_deep_copy_less_the_model(engine):
+    """bench.replicate, the copies every unit of work is made of: the graph, bottoms and relations copy.deepcopy would give
+    (keys, module types, attributes, tensor values and types), and nothing mutable shared with the prototype."""
+    import copy
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    proto = bench.prepare('tiny_res', 0, engine.device)
+    want, got = copy.deepcopy(proto), bench.replicate(proto)
+    assert got[0] is None
+    assert got[2] == want[2] and got[2] is not proto[2]
+    assert [vars(r) for r in got[3]] == [vars(r) for r in want[3]] and not {id(r) for r in got[3]} & {id(r) for r in proto[3]}
+    assert list(got[1]) == list(want[1])
+    for k, m in proto[1].items():
+        a, b = want[1][k], got[1][k]
+        if not isinstance(m, torch.nn.Module):
+            assert a == b == m
+            continue
+        assert type(b) is type(a) and b is not m and list(b.__dict__) == list(a.__dict__)
+        for name, v in m.__dict__.items():
+            if isinstance(v, (dict, set)):
+                assert b.__dict__[name] is not v and type(b.__dict__[name]) is type(a.__dict__[name])
+            else:
+                assert b.__dict__[name] == a.__dict__[name], (k, name)
+        ta, tb, tm = ({**x._parameters, **x._buffers} for x in (a, b, m))
+        assert list(tb) == list(ta)
+        for n in ta:
+            if ta[n] is None:
+                assert tb[n] is None
+                continue
+            assert type(tb[n]) is type(ta[n]) and tb[n].requires_grad == ta[n].requires_grad and tb[n].dtype == ta[n].dtype
+            assert tb[n].device == ta[n].device and torch.equal(tb[n], ta[n]) and tb[n].stride() == ta[n].stride()
+            assert tb[n].untyped_storage().data_ptr() != tm[n].untyped_storage().data_ptr()
+
+
+def test_bench_units_leave_their_prototypes_as_they_were(engine):
+    """A batched unit's copies share the prototypes' storage until NetworkBatch moves them into the batch allocation: calibrating
+    the unit changes its own weights and biases and leaves every tensor of the prototypes as it was."""
+    import copy
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    protos = [bench.prepare('tiny_res', s, engine.device) for s in (0, 1)]
+    before = copy.deepcopy(protos)
+    unit = bench.make_unit(protos)
+    assert 'batch' in unit
+    unit['le'].run()
+    unit['bc'].run()
+    changed = 0
+    for p, b, (_, g, _, _) in zip(protos, before, unit['nets']):
+        for k, m in p[1].items():
+            if not isinstance(m, torch.nn.Module):
+                continue
+            for n, t in {**m._parameters, **m._buffers}.items():
+                if t is not None:
+                    assert torch.equal(t, {**b[1][k]._parameters, **b[1][k]._buffers}[n]), (k, n)
+            if type(m) in bench.TARG:
+                changed += not torch.equal(g[k].weight, m.weight)
+    assert changed > 0
+
+
+def test_bench_unit_copies_compute_what_their_source_computes(engine):
+    """copy_unit: a device copy of a laid-out batch with the plans moved onto it calibrates to the same bits as the batch
+    itself, and running one leaves the other as it was."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    protos = [bench.prepare('tiny_res', s, engine.device) for s in (0, 1)]
+    src = bench.make_unit(protos)
+    cp = bench.copy_unit(src)
+    bits = lambda t: t.view(torch.int32)         # noqa: E731 -- the padding between slots is never written: compare bits
+    pristine = src['batch'].storage.clone()
+    assert cp['storage'].data_ptr() != pristine.data_ptr() and torch.equal(bits(cp['storage']), bits(pristine))
+    cp['le'].run()
+    cp['bc'].run()
+    assert torch.equal(bits(src['batch'].storage), bits(pristine))
+    assert not torch.equal(bits(cp['storage']), bits(pristine))
+    src['le'].run()
+    src['bc'].run()
+    assert torch.equal(bits(cp['storage']), bits(src['batch'].storage))
+    assert [r['sweeps'] for r in cp['le'].query_all()[0]] == [r['sweeps'] for r in src['le'].query_all()[0]]

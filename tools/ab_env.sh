@@ -4,13 +4,14 @@
 #   e.g.  gpurun -- 'bash tools/ab_env.sh "" "DFQ_LE_CF=0" "DFQ_LE_CF_GROUP=4"'        (round 6: the free-running segments)
 #         DFQ_HIP_LIB=$PWD/variants/libdfq_hip_x.so in a setting selects a variant build (make BUILD=build_x OUT=... EXTRA=-D...)
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out
+RESULTS=${RESULTS:-results}                   # where the outputs go
+mkdir -p $RESULTS
 FLAGS="${AB_FLAGS:---steps 8 --warmup 3 --cpu-seconds 0 --others= --act-shape= --sharded= --distill= --pcie= --lazy-steps 0}"
 for round in 1 2; do
   i=0
   for cfg in "$@"; do
     i=$((i+1))
-    env $cfg timeout 300 python bench.py $FLAGS > gpurun_out/abenv_${i}_$round.json 2> gpurun_out/abenv_${i}_$round.err < /dev/null
-    echo -n "round $round [$cfg] "; python tools/bench_line.py gpurun_out/abenv_${i}_$round.json | head -1 | cut -c1-220
+    env $cfg timeout 300 python bench.py --full $FLAGS > $RESULTS/abenv_${i}_$round.json 2> $RESULTS/abenv_${i}_$round.err < /dev/null
+    echo -n "round $round [$cfg] "; python tools/bench_line.py $RESULTS/abenv_${i}_$round.json | head -1 | cut -c1-220
   done
 done

@@ -5,8 +5,10 @@
 # for a counter pass).
 # Every pass runs under `timeout`: a counter pass that aborts can leave rocprofv3 waiting forever.
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
+RESULTS=${RESULTS:-results}                   # where the outputs go
+mkdir -p $RESULTS
 for c in FETCH_SIZE WRITE_SIZE; do
-  rm -rf gpurun_out/pmc_$c
-  timeout ${PMC_TIMEOUT:-150} rocprofv3 --pmc $c --kernel-trace --output-format csv -d gpurun_out/pmc_$c -o pmc -- python tools/pmc_unit.py "$@" > gpurun_out/pmc_$c.log 2>&1 < /dev/null
+  rm -rf $RESULTS/pmc_$c
+  timeout ${PMC_TIMEOUT:-150} rocprofv3 --pmc $c --kernel-trace --output-format csv -d $RESULTS/pmc_$c -o pmc -- python tools/pmc_unit.py "$@" > $RESULTS/pmc_$c.log 2>&1 < /dev/null
   echo "pmc $c rc=$?"
 done
