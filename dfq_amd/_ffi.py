@@ -57,6 +57,11 @@ class DfqRowSegment(Structure):
                 ('codes', c_void_p), ('ranges', c_void_p)]
 
 
+class DfqBatchQuantTensor(Structure):
+    _fields_ = [('data', c_void_p), ('rows', c_int64), ('row_len', c_int64), ('num_bits', c_int32), ('symmetric', c_int32),
+                ('per_row', c_int32), ('pad', c_int32), ('code_offset', c_int64), ('range_offset', c_int64)]
+
+
 class DfqBcSource(Structure):
     _fields_ = [('fake_weight', c_void_p), ('fake_bias', c_void_p), ('channels', c_int32),
                 ('relu', c_int32), ('concat', c_int32)]
@@ -145,6 +150,12 @@ SIGNATURES = {
     'dfq_row_quant_plan_create': (c_int32, [POINTER(DfqRowSegment), c_int32, POINTER(c_void_p)]),
     'dfq_row_quant_plan_destroy': (None, [c_void_p]),
     'dfq_row_quant_plan_run': (c_int32, [c_void_p, c_void_p]),
+    'dfq_batch_quant_plan_create': (c_int32, [POINTER(DfqBatchQuantTensor), c_int32, POINTER(c_void_p), c_int32, c_void_p, c_int32,
+                                              c_int64, c_void_p, c_int64, POINTER(c_void_p)]),
+    'dfq_batch_quant_plan_destroy': (None, [c_void_p]),
+    'dfq_batch_quant_plan_run': (c_int32, [c_void_p, c_void_p]),
+    'dfq_batch_quant_plan_launches': (c_int32, [c_void_p]),
+    'dfq_batch_quant_register_elements': (c_int64, []),
     'dfq_bc_plan_create': (c_int32, [POINTER(DfqLayer), c_int32, POINTER(DfqBcStep), c_int32,
                                      POINTER(DfqBcSource), c_int32, POINTER(c_void_p)]),
     'dfq_bc_plan_create_replicated': (c_int32, [POINTER(DfqLayer), c_int32, POINTER(DfqBcStep), c_int32, POINTER(DfqBcSource), c_int32,

@@ -12,9 +12,13 @@ model, because torch pickles and copies a view together with its whole storage).
 
 This is the host side of the reference's per-network graph walks (dfq.py:78-82, :194-270) for a batch; the arithmetic is the
 engine's, unchanged -- the plans a NetworkBatch creates are the plans ``build_le_plan_batch`` / ``build_bc_plan_batch``
-would create over the same tensors (tests/test_arena.py).
+would create over the same tensors (tests/test_arena.py).  ``quant_plan`` is the batch form of ``quantize_targ_layer``
+(layer_transform.py:279-296, main_cls.py:178-181): one plan, one or two launches for every network of the batch, the
+integer codes and ranges in two caller-visible blocks (tests/test_batch_quant.py).
 """
 from __future__ import annotations
+
+import ctypes
 
 import numpy as np
 import torch
@@ -223,3 +227,143 @@ class NetworkBatch:
         t.n_steps, t.n_sources = self._bc.n_steps, self._bc.n_sources
         t.step_out_ch, t.step_in = self._bc.step_out_ch, self._bc.step_in
         return _dfq.BCPlan(t, None, stage=self.stage)
+
+    def quant_plan(self, bit_weight=8, bits_bias=16, per_channel=False, signed=False, codes=None):
+        """One weight-quantisation plan over the whole batch (BatchQuantPlan): what ``quantize_targ_layer(graph, bit_weight,
+        bits_bias, targ_type, per_channel=, signed=)`` does to each network -- every targ_type layer's weight (per tensor, or
+        per output row with ``per_channel``; ``signed``: the symmetric recipe) and its bias unless ``bits_bias == 32`` (per
+        tensor, asymmetric) -- bit for bit.  ``codes``: None, 'int32' or 'int8' (uint8 for asymmetric weights, int8 for signed
+        ones; bit_weight <= 8): the weights' integer codes land in a block of the plan (``codes(n)``), every range in another
+        (``ranges(n)``).  Bit widths are taken as quantize_targ_layer takes them: per tensor through ``int()`` (8.0 is 8), the
+        bias skipped when ``bits_bias >= 32``; per channel integers in [2, 16] only.  Where quantize_targ_layer would fail
+        inside the library (a per-tensor width outside [1, 30]) this raises ValueError up front.  Every tensor of network 0
+        must still lie in its slot of the batch allocation (RuntimeError otherwise: the plan writes every network at network
+        0's addresses moved by a fixed offset)."""
+        self.check()
+        return BatchQuantPlan(self, bit_weight, bits_bias, per_channel, signed, codes)
+
+    def quantize(self, bit_weight=8, bits_bias=16, per_channel=False, signed=False, codes='int32'):
+        """quant_plan + run + synchronise: returns (codes, ranges), lists of one dict per network (``codes=None``: empty
+        dicts)."""
+        plan = self.quant_plan(bit_weight, bits_bias, per_channel, signed, codes)
+        try:
+            plan.run()
+            _ffi.synchronize()
+            n = len(self.nets)
+            return [plan.codes(i) for i in range(n)], [plan.ranges(i) for i in range(n)]
+        finally:
+            plan.close()
+
+
+def _check_bits(bits, per_channel, what):
+    """a bit width as quantize_targ_layer takes it: per channel an integer in [2, 16] (_quantize_targ_layer_rows), per tensor
+    whatever int() makes of it, in [1, 30] (what dfq_quant_plan_create accepts)"""
+    if per_channel:
+        if isinstance(bits, bool) or not isinstance(bits, (int, np.integer)) or not 2 <= bits <= 16:
+            raise ValueError('quant_plan: per-channel {} {!r} outside [2, 16]'.format(what, bits))
+        return int(bits)
+    try:
+        b = int(bits)
+    except (TypeError, ValueError):
+        raise ValueError('quant_plan: {} {!r} is not a bit width'.format(what, bits)) from None
+    if not 1 <= b <= 30:
+        raise ValueError('quant_plan: {} {!r} outside [1, 30]'.format(what, bits))
+    return b
+
+
+class BatchQuantPlan:
+    """Weight quantisation of every network of a NetworkBatch (dfq_batch_quant_plan, include/dfq_hip.h): network 0's tensor
+    table plus the batch's base addresses.  ``run()`` enqueues on the current stream; the weights and biases are quantised in
+    place, the codes and ranges written to blocks [n_nets, stride] the plan owns and hands out as views."""
+
+    def __init__(self, batch, bit_weight, bits_bias, per_channel, signed, codes):
+        bit_weight = _check_bits(bit_weight, per_channel, 'bit_weight')
+        with_bias = bits_bias < 32                   # layer_transform.py: `bits_bias < 32` decides whether biases are quantised
+        if with_bias:
+            bits_bias = _check_bits(bits_bias, per_channel, 'bits_bias')
+        if codes not in (None, 'int32', 'int8'):
+            raise ValueError("quant_plan: codes must be None, 'int32' or 'int8', got {!r}".format(codes))
+        if codes == 'int8' and bit_weight > 8:
+            raise ValueError('quant_plan: 1-byte codes need bit_weight <= 8, got {}'.format(bit_weight))
+        self._batch = batch
+        self.per_channel, self.signed = bool(per_channel), bool(signed)
+        n_nets = len(batch.nets)
+        dev = batch.stage.device
+        g0 = batch.nets[0][0]
+        tt = tuple(batch.targ_type)
+        entries, self._code_views, self._range_views = [], [], []
+        code_stride = range_stride = 0
+        lo, hi = int(batch.bases[0]), int(batch.bases[0]) + 4 * batch.stride
+
+        def in_slot(key, name, t):
+            """network n's copy is written at t's address + bases[n] - bases[0]: t has to be network 0's slot"""
+            p = t.data_ptr()
+            if not (t.dtype is torch.float32 and t.is_contiguous() and lo <= p and p + 4 * t.numel() <= hi):
+                raise RuntimeError('NetworkBatch: {} of {} in network 0 no longer lives in its slot of the batch allocation'.format(
+                    name, key))
+            return p
+        for key, layer in g0.items():
+            if type(layer) not in tt:
+                continue
+            w = layer.weight
+            rows = int(w.shape[0])
+            c_off = -1
+            if codes is not None:
+                c_off = code_stride
+                self._code_views.append((key, c_off, w.numel(), tuple(w.shape)))
+                code_stride += -(-w.numel() // 64) * 64
+            n_rng = 2 * rows if per_channel else 2
+            self._range_views.append((key, range_stride, (rows, 2) if per_channel else (2,)))
+            entries.append(_ffi.DfqBatchQuantTensor(in_slot(key, 'weight', w), rows, w.numel() // rows, bit_weight, int(self.signed),
+                                                    int(self.per_channel), 0, c_off, range_stride))
+            range_stride += n_rng
+            b = layer.bias
+            if b is not None and with_bias:
+                self._range_views.append((key + '.bias', range_stride, (2,)))
+                entries.append(_ffi.DfqBatchQuantTensor(in_slot(key, 'bias', b), 1, b.numel(), bits_bias, 0, 0, 0, -1, range_stride))
+                range_stride += 2
+        if not entries:
+            raise ValueError('quant_plan: the batch has no {} layer'.format(tt))
+        dtype = {None: torch.int32, 'int32': torch.int32, 'int8': torch.int8 if self.signed else torch.uint8}[codes]
+        self.code_dtype = None if codes is None else dtype
+        self.code_block = torch.empty((n_nets, code_stride), dtype=dtype, device=dev) if codes is not None else None
+        self.range_block = torch.empty((n_nets, range_stride), dtype=torch.float32, device=dev)
+        self.n_nets, self.n_tensors = n_nets, len(entries)
+        arr = (_ffi.DfqBatchQuantTensor * len(entries))(*entries)
+        self._plan = ctypes.c_void_p()
+        _ffi.check(_ffi.lib().dfq_batch_quant_plan_create(
+            arr, len(entries), batch.bases.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)), n_nets,
+            None if self.code_block is None else self.code_block.data_ptr(), 1 if codes == 'int8' else 4, code_stride,
+            self.range_block.data_ptr(), range_stride, ctypes.byref(self._plan)))
+        self.launches = int(_ffi.lib().dfq_batch_quant_plan_launches(self._plan))
+
+    def run(self):
+        """Quantise every network, asynchronously on the current stream."""
+        if self._batch.storage is None:
+            raise RuntimeError('NetworkBatch: the batch has been released')
+        if not self._plan:
+            raise RuntimeError('BatchQuantPlan: the plan has been closed')
+        _ffi.check(_ffi.lib().dfq_batch_quant_plan_run(self._plan, _ffi.stream_arg()))
+
+    def codes(self, n):
+        """{graph key: integer codes of network n's weight, shaped like it} -- views of the code block"""
+        if self.code_block is None:
+            return {}
+        row = self.code_block[n]
+        return {key: row[off:off + numel].view(shape) for (key, off, numel, shape) in self._code_views}
+
+    def ranges(self, n):
+        """{graph key: float32 [O, 2] (per channel) or [2]} of network n's weights, {key + '.bias': [2]} of its biases"""
+        row = self.range_block[n]
+        return {key: row[off:off + 2 * (shape[0] if len(shape) == 2 else 1)].view(shape) for (key, off, shape) in self._range_views}
+
+    def close(self):
+        if self._plan:
+            _ffi.lib().dfq_batch_quant_plan_destroy(self._plan)
+            self._plan = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

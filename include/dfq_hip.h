@@ -374,6 +374,43 @@ int dfq_row_quant_plan_create(const dfq_row_segment* segs, int32_t n_segs, dfq_r
 void dfq_row_quant_plan_destroy(dfq_row_quant_plan* plan);
 int dfq_row_quant_plan_run(dfq_row_quant_plan* plan, void* stream);
 
+/* Weight quantisation of a whole batch of networks of one architecture (extension; quantize_targ_layer,
+ * utils/layer_transform.py:279-296, for every network of a batch at once).  The tensor table describes the FIRST of
+ * `n_nets` networks; network n's copy of a tensor lies bases[n] - bases[0] bytes further (as the replicated LE / BC
+ * plans).  A per-row tensor quantises row r with its own (min, max) -- bit-identical to dfq_row_quant_plan_run; a
+ * per-tensor one uses the tensor's (min, max) -- bit-identical to dfq_quant_plan_run.  Integer codes go to a
+ * caller-owned block [n_nets, code_stride] of `code_bytes`-wide elements: 4 = int32, 1 = uint8 (asymmetric tensors,
+ * 0 .. 2^b-1) / int8 (symmetric, -2^(b-1) .. 2^(b-1)-1), only for tensors of at most 8 bits.  Ranges go to a caller-owned
+ * float32 block [n_nets, range_stride]: (min, max) per row of a per-row tensor, one pair for a per-tensor one.
+ * Offsets are in elements of their block, -1 = none.  No workgroup waits for another: per-row tensors and per-tensor
+ * tensors of at most dfq_batch_quant_register_elements() elements take one launch, longer per-tensor ones a min/max
+ * launch in front of it (folding every chunk into one pair of slots per tensor and network, cleared first).  Every
+ * tensor of network 0 must lie inside network 0's slot: nothing here can check that.  create: DFQ_ERR_ARG (and dfq_last_error) for empty / null arguments, bit widths outside
+ * [2, 16] (per row) or [1, 30] (per tensor), 1-byte codes of more than 8 bits, offsets that overflow their stride.
+ * Synchronises (create only); run is asynchronous on `stream`. */
+typedef struct dfq_batch_quant_plan dfq_batch_quant_plan;
+typedef struct dfq_batch_quant_tensor {
+    float* data;            /* device, inside network 0's slot; [rows, row_len], quantised in place      */
+    int64_t rows;
+    int64_t row_len;
+    int32_t num_bits;
+    int32_t symmetric;
+    int32_t per_row;        /* 1: every row its own range; 0: one range for the tensor                   */
+    int32_t pad;
+    int64_t code_offset;    /* elements into a network's code block, or -1                               */
+    int64_t range_offset;   /* floats into a network's range block, or -1                                */
+} dfq_batch_quant_tensor;
+
+int dfq_batch_quant_plan_create(const dfq_batch_quant_tensor* tensors, int32_t n_tensors, const void* const* bases, int32_t n_nets,
+                                void* codes, int32_t code_bytes, int64_t code_stride, float* ranges, int64_t range_stride,
+                                dfq_batch_quant_plan** out_plan);
+void dfq_batch_quant_plan_destroy(dfq_batch_quant_plan* plan);
+int dfq_batch_quant_plan_run(dfq_batch_quant_plan* plan, void* stream);
+/* launches per run (1 or 2) */
+int32_t dfq_batch_quant_plan_launches(const dfq_batch_quant_plan* plan);
+/* longest row (or per-tensor tensor) kept in registers between its min/max and its quantisation; longer ones are read twice */
+int64_t dfq_batch_quant_register_elements(void);
+
 /* ------------------------------------------------------------------------------------------
  * Lazy-scale equalisation (opt-in extension): the sweeps of dfq.py:83-101 with a GIVEN sweep count,
  * computed from the pristine weights and the cumulative scale vectors of utils/relation.py:20-24 -- a sweep only READS
