@@ -62,6 +62,15 @@ class DfqBatchQuantTensor(Structure):
                 ('per_row', c_int32), ('pad', c_int32), ('code_offset', c_int64), ('range_offset', c_int64)]
 
 
+class DfqBatchAbsorbRelation(Structure):
+    _fields_ = [('w2', c_void_p), ('b1', c_void_p), ('b2', c_void_p), ('bn_weight', c_void_p), ('bn_bias', c_void_p),
+                ('o2', c_int32), ('in_per_group', c_int32), ('khkw', c_int32), ('o1', c_int32), ('shift_offset', c_int64)]
+
+
+class DfqBatchAbsorbClip(Structure):
+    _fields_ = [('data', c_void_p), ('n', c_int64)]
+
+
 class DfqBcSource(Structure):
     _fields_ = [('fake_weight', c_void_p), ('fake_bias', c_void_p), ('channels', c_int32),
                 ('relu', c_int32), ('concat', c_int32)]
@@ -156,6 +165,13 @@ SIGNATURES = {
     'dfq_batch_quant_plan_run': (c_int32, [c_void_p, c_void_p]),
     'dfq_batch_quant_plan_launches': (c_int32, [c_void_p]),
     'dfq_batch_quant_register_elements': (c_int64, []),
+    'dfq_batch_absorb_plan_create': (c_int32, [POINTER(DfqBatchAbsorbRelation), c_int32, POINTER(DfqBatchAbsorbClip), c_int32,
+                                               POINTER(c_void_p), c_int32, c_float, c_float, c_float, c_void_p, c_int64,
+                                               POINTER(c_void_p)]),
+    'dfq_batch_absorb_plan_destroy': (None, [c_void_p]),
+    'dfq_batch_absorb_plan_run': (c_int32, [c_void_p, c_void_p]),
+    'dfq_batch_absorb_plan_launches': (c_int32, [c_void_p]),
+    'dfq_batch_absorb_plan_elements': (c_int32, [c_void_p, POINTER(c_int64), POINTER(c_int64)]),
     'dfq_bc_plan_create': (c_int32, [POINTER(DfqLayer), c_int32, POINTER(DfqBcStep), c_int32,
                                      POINTER(DfqBcSource), c_int32, POINTER(c_void_p)]),
     'dfq_bc_plan_create_replicated': (c_int32, [POINTER(DfqLayer), c_int32, POINTER(DfqBcStep), c_int32, POINTER(DfqBcSource), c_int32,

@@ -14,11 +14,15 @@ This is the host side of the reference's per-network graph walks (dfq.py:78-82, 
 engine's, unchanged -- the plans a NetworkBatch creates are the plans ``build_le_plan_batch`` / ``build_bc_plan_batch``
 would create over the same tensors (tests/test_arena.py).  ``quant_plan`` is the batch form of ``quantize_targ_layer``
 (layer_transform.py:279-296, main_cls.py:178-181): one plan, one or two launches for every network of the batch, the
-integer codes and ranges in two caller-visible blocks (tests/test_batch_quant.py).
+integer codes and ranges in two caller-visible blocks (tests/test_batch_quant.py).  ``absorb_plan`` is the batch form of the
+two optional steps between equalisation and correction, ``bias_absorption`` (dfq.py:121-164) and ``clip_weight``
+(dfq.py:167-170): two launches for the whole batch, every weight read once (tests/test_batch_absorb.py).  With it the
+sequence main_cls.py:149-181 runs on a batch as le_plan -> absorb_plan -> bc_plan -> quant_plan.
 """
 from __future__ import annotations
 
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -255,6 +259,26 @@ class NetworkBatch:
             plan.close()
 
 
+    def absorb_plan(self, N=3, range_clip=None, absorb=True):
+        """One plan (BatchAbsorbPlan) for ``bias_absorption(graph, relations, bottoms, N)`` followed, if ``range_clip`` is
+        given, by ``clip_weight(graph, range_clip, targ_type)`` on every network of the batch, bit for bit.  ``absorb=False``
+        with a ``range_clip`` is clip_weight alone.  Relations without a ReLU between their layers are skipped as
+        bias_absorption skips them (the walk is made on network 0).  ValueError for an ``N`` that is not a finite number, a
+        ``range_clip`` that is not a pair lo <= hi, and a second layer of an absorbed relation whose bias has no slot in the
+        batch allocation; RuntimeError for a tensor of network 0 that has left its slot."""
+        self.check()
+        return BatchAbsorbPlan(self, N, range_clip, absorb)
+
+    def absorb(self, N=3, range_clip=None, absorb=True):
+        """absorb_plan + run + synchronise + close"""
+        plan = self.absorb_plan(N, range_clip, absorb)
+        try:
+            plan.run()
+            _ffi.synchronize()
+        finally:
+            plan.close()
+
+
 def _check_bits(bits, per_channel, what):
     """a bit width as quantize_targ_layer takes it: per channel an integer in [2, 16] (_quantize_targ_layer_rows), per tensor
     whatever int() makes of it, in [1, 30] (what dfq_quant_plan_create accepts)"""
@@ -360,6 +384,105 @@ class BatchQuantPlan:
     def close(self):
         if self._plan:
             _ffi.lib().dfq_batch_quant_plan_destroy(self._plan)
+            self._plan = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BatchAbsorbPlan:
+    """Bias absorption and weight clipping of every network of a NetworkBatch (dfq_batch_absorb_plan, include/dfq_hip.h):
+    network 0's relation table plus the batch's base addresses.  ``run()`` enqueues on the current stream; biases, the
+    BatchNorm proxies' ``fake_bias`` and the clipped weights change in place, the shift vectors c = max(0, beta~ - N gamma~)
+    every update used are kept in a block [n_nets, stride] the plan owns (``shifts(n)``)."""
+
+    def __init__(self, batch, N, range_clip, absorb):
+        try:
+            n_sigma = float(N)
+        except (TypeError, ValueError):
+            raise ValueError('absorb_plan: N {!r} is not a number'.format(N)) from None
+        if isinstance(N, bool) or not math.isfinite(n_sigma):
+            raise ValueError('absorb_plan: N {!r} is not a finite number'.format(N))
+        lo = hi = 0.0
+        if range_clip is not None:
+            try:
+                lo, hi = (float(v) for v in range_clip)
+            except (TypeError, ValueError):
+                raise ValueError('absorb_plan: range_clip {!r} is not a pair of numbers'.format(range_clip)) from None
+            if not lo <= hi:
+                raise ValueError('absorb_plan: range_clip {!r} is not a range lo <= hi'.format(range_clip))
+        self._batch = batch
+        n_nets = len(batch.nets)
+        g0, b0, r0 = batch.nets[0]
+        tt = tuple(batch.targ_type)
+        slot_lo, slot_hi = int(batch.bases[0]), int(batch.bases[0]) + 4 * batch.stride
+
+        def in_slot(key, name, t):
+            """network n's copy is found at t's address + bases[n] - bases[0]: t has to be network 0's slot"""
+            p = t.data_ptr()
+            if not (t.dtype is torch.float32 and t.is_contiguous() and slot_lo <= p and p + 4 * t.numel() <= slot_hi):
+                raise RuntimeError('NetworkBatch: {} of {} in network 0 no longer lives in its slot of the batch allocation'.format(
+                    name, key))
+            return p
+        rels, self._shift_views = [], []
+        stride = 0
+        for idx, rr in enumerate(r0 if absorb else ()):
+            kf, ks, kb = rr.get_idxs()
+            if not _dfq._relu_between(g0, b0, ks, kf):          # dfq.py:131-139
+                continue
+            first, second = g0[kf], g0[ks]
+            for key, layer in ((ks, second), (kf, first)):
+                if layer.bias is None:
+                    raise ValueError('absorb_plan: layer {} of an absorbed relation has no bias in the batch allocation'.format(key))
+            fw, fb = _dfq._attr(g0[kb], 'fake_weight'), _dfq._attr(g0[kb], 'fake_bias')
+            if fw is None or fb is None:
+                raise ValueError('absorb_plan: {} has no BatchNorm proxies (merge_batchnorm first)'.format(kb))
+            w2 = second.weight
+            khkw = w2[0, 0].numel() if w2.dim() > 2 else 1
+            o1 = int(first.weight.size(0))
+            rels.append(_ffi.DfqBatchAbsorbRelation(
+                in_slot(ks, 'weight', w2), in_slot(kf, 'bias', first.bias), in_slot(ks, 'bias', second.bias),
+                in_slot(kb, 'fake_weight', fw), in_slot(kb, 'fake_bias', fb), int(w2.shape[0]), int(w2.shape[1]), khkw, o1, stride))
+            self._shift_views.append((idx, stride, o1))
+            stride += -(-o1 // _ALIGN) * _ALIGN
+        clips = []
+        if range_clip is not None:
+            for key, layer in g0.items():                       # dfq.py:168-170
+                if type(layer) in tt:
+                    clips.append(_ffi.DfqBatchAbsorbClip(in_slot(key, 'weight', layer.weight), layer.weight.numel()))
+        self.n_nets, self.n_relations, self.n_clipped = n_nets, len(rels), len(clips)
+        self.shift_block = torch.zeros((n_nets, stride), dtype=torch.float32, device=batch.stage.device)
+        rel_arr = (_ffi.DfqBatchAbsorbRelation * len(rels))(*rels) if rels else None
+        clip_arr = (_ffi.DfqBatchAbsorbClip * len(clips))(*clips) if clips else None
+        self._plan = ctypes.c_void_p()
+        _ffi.check(_ffi.lib().dfq_batch_absorb_plan_create(
+            rel_arr, len(rels), clip_arr, len(clips), batch.bases.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)), n_nets,
+            ctypes.c_float(n_sigma), ctypes.c_float(lo), ctypes.c_float(hi),
+            self.shift_block.data_ptr() if rels else None, stride, ctypes.byref(self._plan)))
+        self.launches = int(_ffi.lib().dfq_batch_absorb_plan_launches(self._plan))
+        a, c = ctypes.c_int64(), ctypes.c_int64()
+        _ffi.check(_ffi.lib().dfq_batch_absorb_plan_elements(self._plan, ctypes.byref(a), ctypes.byref(c)))
+        self.absorbed_elements, self.clip_only_elements = a.value, c.value          # per network
+
+    def run(self):
+        """Absorb and clip every network, asynchronously on the current stream."""
+        if self._batch.storage is None:
+            raise RuntimeError('NetworkBatch: the batch has been released')
+        if not self._plan:
+            raise RuntimeError('BatchAbsorbPlan: the plan has been closed')
+        _ffi.check(_ffi.lib().dfq_batch_absorb_plan_run(self._plan, _ffi.stream_arg()))
+
+    def shifts(self, n):
+        """{index into the relations list: the shift vector c of network n} for the absorbed relations -- views of the block"""
+        row = self.shift_block[n]
+        return {idx: row[off:off + o1] for (idx, off, o1) in self._shift_views}
+
+    def close(self):
+        if self._plan:
+            _ffi.lib().dfq_batch_absorb_plan_destroy(self._plan)
             self._plan = None
 
     def __del__(self):

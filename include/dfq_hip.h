@@ -411,6 +411,51 @@ int32_t dfq_batch_quant_plan_launches(const dfq_batch_quant_plan* plan);
 /* longest row (or per-tensor tensor) kept in registers between its min/max and its quantisation; longer ones are read twice */
 int64_t dfq_batch_quant_register_elements(void);
 
+/* Bias absorption and weight clipping of a whole batch of networks of one architecture (extension; bias_absorption,
+ * dfq.py:121-164, followed by clip_weight, dfq.py:167-170, for every network of a batch at once).  The tables describe the
+ * FIRST of `n_nets` networks; network n's copy of a tensor lies bases[n] - bases[0] bytes further.  `relations` lists, in
+ * the order bias_absorption would walk them, the relations WITH a ReLU between their layers (the caller skips the others,
+ * dfq.py:131-139); one run does for each, in every network, what dfq_bias_absorb does:
+ *   c = max(0, bn_bias - n_sigma * bn_weight);  b1 -= c;  bn_bias -= c;  b2[o] += sum_i (sum_k W2[o,i,k]) * c[g*I2/g + i]
+ * with c taken ONCE, before anything is shifted, and kept in the caller's float32 block [n_nets, shift_stride] at
+ * `shift_offset` (o1 floats).  A bias that is b2 of one relation and b1 of another receives its two updates in the order
+ * of the list.  Then every tensor of `clips` becomes clamp(x, lo, hi) as dfq_clamp leaves it (NaN, infinities and signed
+ * zeros included); a weight that is both summed and clipped is read once, summed unclipped, and written only where the
+ * clamp changed it.  Every result is bit-identical to the dfq_bias_absorb / dfq_clamp calls on that network alone.
+ * Two launches (the shifts, then one pass over the weights), none with absorbed relations = one, nothing to do = none; no
+ * workgroup waits for another.  create: DFQ_ERR_ARG (and dfq_last_error) for null / empty arguments, a geometry
+ * dfq_bias_absorb refuses, a kernel of more than 3136 taps, a non-finite n_sigma, lo > hi or NaN, a shift vector outside
+ * its stride or overlapping another, two relations sharing a first or a second layer, a clip tensor listed twice or
+ * sized unlike the relation's weight it is.  Every tensor of network 0 must lie inside network 0's slot: nothing here can
+ * check that.  Synchronises (create only); run is asynchronous on `stream`. */
+typedef struct dfq_batch_absorb_plan dfq_batch_absorb_plan;
+typedef struct dfq_batch_absorb_relation {
+    const float* w2;        /* second layer's weight [o2, in_per_group, khkw], network 0                   */
+    float* b1;              /* first layer's bias [o1]                                                     */
+    float* b2;              /* second layer's bias [o2]                                                    */
+    const float* bn_weight; /* gamma~ [o1]                                                                 */
+    float* bn_bias;         /* beta~ [o1]                                                                  */
+    int32_t o2;
+    int32_t in_per_group;
+    int32_t khkw;
+    int32_t o1;
+    int64_t shift_offset;   /* floats into a network's shift block                                         */
+} dfq_batch_absorb_relation;
+typedef struct dfq_batch_absorb_clip {
+    float* data;            /* clamped in place, network 0                                                 */
+    int64_t n;
+} dfq_batch_absorb_clip;
+
+int dfq_batch_absorb_plan_create(const dfq_batch_absorb_relation* relations, int32_t n_relations, const dfq_batch_absorb_clip* clips,
+                                 int32_t n_clips, const void* const* bases, int32_t n_nets, float n_sigma, float lo, float hi,
+                                 float* shifts, int64_t shift_stride, dfq_batch_absorb_plan** out_plan);
+void dfq_batch_absorb_plan_destroy(dfq_batch_absorb_plan* plan);
+int dfq_batch_absorb_plan_run(dfq_batch_absorb_plan* plan, void* stream);
+/* launches per run (0, 1 or 2) */
+int32_t dfq_batch_absorb_plan_launches(const dfq_batch_absorb_plan* plan);
+/* weights per network that are read for a row sum, and weights that are only clipped (either pointer may be null) */
+int dfq_batch_absorb_plan_elements(const dfq_batch_absorb_plan* plan, int64_t* absorbed, int64_t* clip_only);
+
 /* ------------------------------------------------------------------------------------------
  * Lazy-scale equalisation (opt-in extension): the sweeps of dfq.py:83-101 with a GIVEN sweep count,
  * computed from the pristine weights and the cumulative scale vectors of utils/relation.py:20-24 -- a sweep only READS
