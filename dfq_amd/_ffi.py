@@ -71,6 +71,25 @@ class DfqBatchAbsorbClip(Structure):
     _fields_ = [('data', c_void_p), ('n', c_int64)]
 
 
+class DfqBatchActResult(Structure):
+    _fields_ = [('step_begin', c_int32), ('step_count', c_int32)]
+
+
+class DfqBatchActStep(Structure):
+    _fields_ = [('fake_weight', c_void_p), ('fake_bias', c_void_p), ('opcode', c_int32), ('channels', c_int32),
+                ('relu_mode', c_int32), ('operand', c_int32), ('source_weight', c_int32), ('source_bias', c_int32),
+                ('lo', c_float), ('hi', c_float)]
+
+
+class DfqBatchActSource(Structure):
+    _fields_ = [('weight', c_void_p), ('bias', c_void_p), ('vector', c_void_p), ('out_ch', c_int32), ('in_per_group', c_int32),
+                ('khkw', c_int32), ('groups', c_int32)]
+
+
+# opcodes of DfqBatchActStep (DFQ_ACT_* of include/dfq_hip.h)
+ACT_CONST, ACT_RANGE, ACT_RANGE_CAT, ACT_RANGE_ONE, ACT_RANGE_DIV, ACT_MOM, ACT_MOM_ADD, ACT_MOM_RELU, ACT_MOM_RANGE = range(9)
+
+
 class DfqBcSource(Structure):
     _fields_ = [('fake_weight', c_void_p), ('fake_bias', c_void_p), ('channels', c_int32),
                 ('relu', c_int32), ('concat', c_int32)]
@@ -172,6 +191,12 @@ SIGNATURES = {
     'dfq_batch_absorb_plan_run': (c_int32, [c_void_p, c_void_p]),
     'dfq_batch_absorb_plan_launches': (c_int32, [c_void_p]),
     'dfq_batch_absorb_plan_elements': (c_int32, [c_void_p, POINTER(c_int64), POINTER(c_int64)]),
+    'dfq_batch_act_plan_create': (c_int32, [POINTER(DfqBatchActResult), c_int32, POINTER(DfqBatchActStep), c_int32,
+                                            POINTER(DfqBatchActSource), c_int32, POINTER(c_void_p), c_int32, c_float, c_float,
+                                            c_void_p, c_int64, POINTER(c_void_p)]),
+    'dfq_batch_act_plan_destroy': (None, [c_void_p]),
+    'dfq_batch_act_plan_run': (c_int32, [c_void_p, c_void_p]),
+    'dfq_batch_act_plan_launches': (c_int32, [c_void_p]),
     'dfq_bc_plan_create': (c_int32, [POINTER(DfqLayer), c_int32, POINTER(DfqBcStep), c_int32,
                                      POINTER(DfqBcSource), c_int32, POINTER(c_void_p)]),
     'dfq_bc_plan_create_replicated': (c_int32, [POINTER(DfqLayer), c_int32, POINTER(DfqBcStep), c_int32, POINTER(DfqBcSource), c_int32,

@@ -16,20 +16,24 @@ would create over the same tensors (tests/test_arena.py).  ``quant_plan`` is the
 (layer_transform.py:279-296, main_cls.py:178-181): one plan, one or two launches for every network of the batch, the
 integer codes and ranges in two caller-visible blocks (tests/test_batch_quant.py).  ``absorb_plan`` is the batch form of the
 two optional steps between equalisation and correction, ``bias_absorption`` (dfq.py:121-164) and ``clip_weight``
-(dfq.py:167-170): two launches for the whole batch, every weight read once (tests/test_batch_absorb.py).  With it the
-sequence main_cls.py:149-181 runs on a batch as le_plan -> absorb_plan -> bc_plan -> quant_plan.
+(dfq.py:167-170): two launches for the whole batch, every weight read once (tests/test_batch_absorb.py).  ``act_range_plan`` is the batch form of
+``set_quant_minmax`` (layer_transform.py:347-609, main_cls.py:188), the analytic activation ranges: the graph walk is made
+once, on network 0, and one launch (two with a conv / linear without BatchNorm in front of a quantiser) fills one block of
+packed (min, max) pairs the quantisers are then pointed at (tests/test_batch_act.py).  With them the default calibration
+sequence main_cls.py:149-190 runs on a batch as le_plan -> absorb_plan -> bc_plan -> quant_plan -> act_range_plan.
 """
 from __future__ import annotations
 
 import ctypes
 import math
+from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from . import _ffi
 from . import dfq as _dfq
-from .utils.layer_transform import _ensure_bias
+from .utils.layer_transform import _RELU_MODE, _ensure_bias, find_prev_bn
 
 _ALIGN = 64            # floats: every tensor starts on a 256-byte boundary (vector loads, the alignment hipMalloc gives)
 
@@ -152,7 +156,9 @@ class NetworkBatch:
                             raise RuntimeError('NetworkBatch: a table of the first network points outside its slot ({})'.format(field))
         self._base_ints = [int(v) for v in self.bases]
         self._scale_cum = [rr.S for (_, _, rels) in self.nets for rr in rels]
-        self._probe = [(slots[0][2], slots[-1][0]) for slots in per_net]       # first weight, last relation of every network
+        # first weight, last relation of every network (None: a network without relations, ReLU6 kept, has no scale vectors)
+        self._probe = [(slots[0][2], slots[-1][0] if r0 else None) for slots in per_net]
+        self._act_bound = {}                  # id -> (quantiser module, range block) of every BatchActRangePlan.bind_quantisers
 
     def release(self):
         """Give every tensor a storage of its own again (a copy of its slot) and drop the batch allocation.  The models' tensors
@@ -182,6 +188,17 @@ class NetworkBatch:
                 for rr in relations:
                     if mine(rr.S):
                         rr.S = rr.S.clone()
+            # quantisers bound to the range block of an act_range_plan: that block is a second home allocation
+            for q, block in self._act_bound.values():
+                bufs = q.__dict__['_buffers']
+                there = block.untyped_storage().data_ptr()
+                mn, mx = bufs.get('running_min'), bufs.get('running_max')
+                if not (torch.is_tensor(mn) and torch.is_tensor(mx) and mn.untyped_storage().data_ptr() == there
+                        and mx.untyped_storage().data_ptr() == there):
+                    continue                                        # somebody has given it other buffers since
+                pair = torch.cat([mn.reshape(1), mx.reshape(1)])    # stays the packed pair QuantMeasure._packed_range looks for
+                bufs['running_min'], bufs['running_max'] = pair[0:1], pair[1:2]
+        self._act_bound = {}
         self._probe, self._scale_cum = [], []
         self.storage = None
 
@@ -202,7 +219,7 @@ class NetworkBatch:
             raise RuntimeError('NetworkBatch: the batch has been released')
         span = 4 * self.stride
         for n, ((w, rr), base) in enumerate(zip(self._probe, self._base_ints)):
-            if w.data_ptr() != base or rr.S is None or not (base <= rr.S.data_ptr() < base + span):
+            if w.data_ptr() != base or (rr is not None and (rr.S is None or not (base <= rr.S.data_ptr() < base + span))):
                 raise RuntimeError('NetworkBatch: a tensor of network {} no longer lives in the batch allocation'.format(n))
         if thorough:
             for n, (g, b, r) in enumerate(self.nets):
@@ -277,6 +294,42 @@ class NetworkBatch:
             _ffi.synchronize()
         finally:
             plan.close()
+
+    def act_range_plan(self, is_detection=False, N=6, tensor_ops=None):
+        """One plan (BatchActRangePlan) for ``set_quant_minmax(graph, bottoms, is_detection, N=N)`` on every network of the
+        batch, bit for bit: the analytic (min, max) of every activation quantiser from the BatchNorm proxies in front of it.
+        The graph walk is made once, on network 0.  A range is computed for every layer with a ``.quant`` and for every
+        ``targ_type`` layer without one (its input range, what ``ncnn_table`` asks for); ``tensor_ops = {graph key: count}``
+        adds the inputs of add / cat / mean / interpolate / softmax nodes, as ``tensor_op_quant`` does for the single-network
+        function.  ValueError for an ``N`` that is not a finite number, an unknown key or a non-positive count in
+        ``tensor_ops``, a BatchNorm without proxies, and a graph set_quant_minmax itself would refuse; RuntimeError for a
+        tensor of network 0 that has left its slot."""
+        self.check()
+        return BatchActRangePlan(self, is_detection, N, tensor_ops)
+
+    def set_quant_minmax(self, is_detection=False, N=6, tensor_op_quant=None):
+        """act_range_plan + run + synchronise + bind_quantisers + close: afterwards every ``layer.quant`` of every network
+        holds its range, as a view of the plan's block.  ``tensor_op_quant``: one ``{graph key: [QuantMeasure, ...]}`` per
+        network (the quantisers of tensor ops, as the single-network function takes them).  Returns the closed plan, whose
+        ``ranges(n)`` stay readable."""
+        ops = None
+        if tensor_op_quant is not None:
+            tensor_op_quant = list(tensor_op_quant)
+            if len(tensor_op_quant) != len(self.nets):
+                raise ValueError('set_quant_minmax: tensor_op_quant wants one dict per network ({}), got {}'.format(
+                    len(self.nets), len(tensor_op_quant)))
+            ops = OrderedDict((k, len(v)) for k, v in tensor_op_quant[0].items())
+            for n, tq in enumerate(tensor_op_quant):
+                if OrderedDict((k, len(v)) for k, v in tq.items()) != ops:
+                    raise ValueError('set_quant_minmax: the tensor-op quantisers of network {} are not those of network 0'.format(n))
+        plan = self.act_range_plan(is_detection, N, ops)
+        try:
+            plan.run()
+            _ffi.synchronize()
+            plan.bind_quantisers(tensor_op_quant)
+        finally:
+            plan.close()
+        return plan
 
 
 def _check_bits(bits, per_channel, what):
@@ -483,6 +536,262 @@ class BatchAbsorbPlan:
     def close(self):
         if self._plan:
             _ffi.lib().dfq_batch_absorb_plan_destroy(self._plan)
+            self._plan = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _act_program(graph, bottoms, bn_type, targ_type, tensor_ops, is_detection):
+    """The walk of set_quant_minmax (layer_transform.py:347-609) over ONE graph, compiled instead of executed:
+    [(graph key, [result, ...])] in the order that function meets the quantised nodes, a result being the list of steps
+    (opcode, bn or None, relu mode, operand, case-(d) layer or None) whose execution gives one quantiser's (min, max).  Same
+    node classification, same ``find_prev_bn``, same branch grouping and ordering, so the steps of a result are the launches
+    ``set_quant_minmax`` issues for it, in its order.  What that function asserts, or would trip over, is a ValueError here."""
+    A = _ffi
+    tt = tuple(targ_type)
+    bn_module, relu_attached, nodes = {}, {}, []
+    for key in graph:
+        bot = bottoms[key]
+        if bot is None:
+            continue
+        layer = graph[key]
+        if type(layer) == bn_type:
+            bn_module[key] = layer
+            relu_attached[key] = 'none'
+            continue
+        if type(layer) == torch.nn.ReLU:
+            relu_attached[bot[0]] = 'relu'
+        elif type(layer) == torch.nn.ReLU6:
+            relu_attached[bot[0]] = 'relu6'
+        if isinstance(layer, str):
+            count = tensor_ops.get(key)
+        elif hasattr(layer, 'quant') or type(layer) in tt:
+            count = 1
+        else:
+            count = None
+        if count is None:
+            continue
+        if len(bot) == 1 and bot[0] == 'Data':                     # :443-449 (only the first quantiser of the node is set)
+            lo, hi = (-1.0, 1.0) if is_detection else (-2.11790393, 2.64)
+            nodes.append((key, [[(A.ACT_CONST, None, 0, (lo, hi), None)]]))
+            continue
+        try:
+            bn_list, relu_list, connect_list, no_bn = find_prev_bn(bn_module, relu_attached, graph, bottoms, bot[:])
+        except AssertionError as e:
+            raise ValueError('act_range_plan: {}: {}'.format(key, e)) from None
+        if count == len(bn_list):                                   # 1 to 1 mapping (:444-474)
+            results = []
+            for (bn, bid), relu in zip(bn_list, relu_list):
+                if bid[0] in no_bn:                                 # case (d): no ReLU clamp in the reference
+                    results.append([(A.ACT_RANGE, bn, 0, 0, no_bn[bid[0]])])
+                else:
+                    results.append([(A.ACT_RANGE, bn, _RELU_MODE[relu], 0, None)])
+            nodes.append((key, results))
+            continue
+        # ---- 1 to many / many to many (:476-601) ----
+        branches = OrderedDict()
+        for ent, relu, ctype in zip(bn_list, relu_list, connect_list):
+            branches.setdefault(ent[1][0], []).append((ent, relu, ctype))
+        compiled = OrderedDict()
+        for bkey, items in branches.items():
+            def bad(why):
+                return ValueError('act_range_plan: {}: branch {} {} (set_quant_minmax cannot evaluate it either)'.format(key, bkey, why))
+            items = sorted(items, key=lambda x: len(x[0][1]), reverse=True)
+            (bn, bid), use_relu, connect_type = items.pop(0)
+            depth = len(bid)
+            moments = 'add' in connect_type
+            steps = [(A.ACT_MOM if moments else A.ACT_RANGE, bn, _RELU_MODE[use_relu], 0, None)]
+            while items:
+                bound = 0
+                while bound < len(items) and len(items[bound][0][1]) == depth:
+                    bound += 1
+                if bound == 0:
+                    depth = len(items[0][0][1])                     # cut depth
+                    continue
+                for (bn, bid), relu_t, connect_type in items[:bound]:
+                    if 'add' in connect_type:
+                        if not moments:
+                            raise bad('meets an add after a cat / plain connection')
+                        steps.append((A.ACT_MOM_ADD, bn, _RELU_MODE[relu_t], 0, None))
+                        if 'relu6' in connect_type:
+                            steps.append((A.ACT_MOM_RELU, None, 2, 0, None))
+                        elif 'relu' in connect_type:
+                            steps.append((A.ACT_MOM_RELU, None, 1, 0, None))
+                    elif moments:
+                        raise bad('meets a cat / plain connection after an add')
+                    elif connect_type == 'cat':
+                        steps.append((A.ACT_RANGE_CAT, bn, _RELU_MODE[relu_t], 0, None))
+                    else:                                           # `if use_relu_tmp` is always true: clamp at 0, in the step
+                        steps.append((A.ACT_RANGE_ONE, bn, 0, 0, None))
+                items = items[bound:]
+                if connect_type == 'one':
+                    if moments:
+                        raise bad('meets a cat / plain connection after an add')
+                    steps.append((A.ACT_RANGE_DIV, None, 0, bound + 1, None))
+            if ('add' in connect_type) != moments:
+                raise bad('mixes adds with cat / plain connections')
+            if moments:
+                steps.append((A.ACT_MOM_RANGE, None, 0, 0, None))
+            compiled[bkey] = steps
+        if count == 1 and count < len(bn_list):                     # 1 to many
+            if len(compiled) != 1:
+                raise ValueError('act_range_plan: {}: error occurs when setting min/max, should be 1 to many'.format(key))
+            nodes.append((key, [list(compiled.values())[0]]))
+        elif count < len(bn_list):                                  # many to many
+            if len(compiled) != count or any(str(i) not in compiled for i in range(count)):
+                raise ValueError('act_range_plan: {}: LENGTH NOT EQUAL {} vs {}'.format(key, len(compiled), count))
+            nodes.append((key, [compiled[str(i)] for i in range(count)]))
+        else:
+            raise ValueError('act_range_plan: {}: {} quantisers for {} BatchNorm layers'.format(key, count, len(bn_list)))
+    return nodes
+
+
+class BatchActRangePlan:
+    """The analytic activation ranges of every network of a NetworkBatch (dfq_batch_act_plan, include/dfq_hip.h): the program
+    compiled from network 0's graph plus the batch's base addresses.  ``run()`` enqueues on the current stream; it reads the
+    BatchNorm proxies (and, for a conv / linear without BatchNorm in front of a quantiser, that layer's weight and bias) and
+    writes only ``self.block``, float32 [n_nets, n_results, 2]: the packed (min, max) pairs in the layout ``QuantMeasure``
+    keeps its range in.  The block is a torch tensor and outlives ``close()``."""
+
+    def __init__(self, batch, is_detection, N, tensor_ops):
+        try:
+            n_sigma = float(N)
+        except (TypeError, ValueError):
+            raise ValueError('act_range_plan: N {!r} is not a number'.format(N)) from None
+        if isinstance(N, bool) or not math.isfinite(n_sigma):
+            raise ValueError('act_range_plan: N {!r} is not a finite number'.format(N))
+        g0, b0, _ = batch.nets[0]
+        ops = OrderedDict()
+        for key, count in (tensor_ops or {}).items():
+            if key not in g0 or not isinstance(g0[key], str) or b0[key] is None:
+                raise ValueError('act_range_plan: tensor_ops names {!r}, which is not a tensor op of the graph'.format(key))
+            if isinstance(count, bool) or not isinstance(count, (int, np.integer)) or count <= 0:
+                raise ValueError('act_range_plan: tensor_ops[{!r}] = {!r} is not a positive count'.format(key, count))
+            ops[key] = int(count)
+        self._batch = batch
+        self.is_detection, self.n_sigma, self.eps = bool(is_detection), n_sigma, 1e-6          # eps: layer_transform.py:349
+        nodes = _act_program(g0, b0, batch.bn_type, batch.targ_type, ops, self.is_detection)
+        if not nodes:
+            raise ValueError('act_range_plan: the graph has no quantised node')
+        key_of = {id(m): k for k, m in g0.items() if isinstance(m, torch.nn.Module)}
+        slot_lo, slot_hi = int(batch.bases[0]), int(batch.bases[0]) + 4 * batch.stride
+
+        def in_slot(key, name, t):
+            """network n's copy is found at t's address + bases[n] - bases[0]: t has to be network 0's slot"""
+            p = t.data_ptr()
+            if not (t.dtype is torch.float32 and t.is_contiguous() and slot_lo <= p and p + 4 * t.numel() <= slot_hi):
+                raise RuntimeError('NetworkBatch: {} of {} in network 0 no longer lives in its slot of the batch allocation'.format(
+                    name, key))
+            return p
+
+        def proxies(bn):
+            key = key_of.get(id(bn), '?')
+            fw, fb = _dfq._attr(bn, 'fake_weight'), _dfq._attr(bn, 'fake_bias')
+            if fw is None or fb is None:
+                raise ValueError('act_range_plan: {} has no BatchNorm proxies (merge_batchnorm first)'.format(key))
+            if fw.numel() != fb.numel():
+                raise ValueError('act_range_plan: the proxies of {} have {} and {} channels'.format(key, fw.numel(), fb.numel()))
+            return key, fw, fb
+        results, steps, sources = [], [], []
+        self._views = []                       # (graph key, first result, number of results, is a tensor op)
+        for key, node_results in nodes:
+            self._views.append((key, len(results), len(node_results), isinstance(g0[key], str)))
+            for prog in node_results:
+                results.append(_ffi.DfqBatchActResult(len(steps), len(prog)))
+                channels = None                # of the moment vectors of this result
+                for (op, bn, relu, operand, through) in prog:
+                    if op == _ffi.ACT_CONST:
+                        steps.append(_ffi.DfqBatchActStep(None, None, op, 0, 0, 0, -1, -1, operand[0], operand[1]))
+                        continue
+                    if bn is None:
+                        steps.append(_ffi.DfqBatchActStep(None, None, op, 0, relu, operand, -1, -1, 0.0, 0.0))
+                        continue
+                    bkey, fw, fb = proxies(bn)
+                    if through is not None:    # case (d): both proxies through the layer, fake_bias first like set_quant_minmax
+                        kind, layer = through
+                        lkey = key_of.get(id(layer), '?')
+                        w = layer.weight
+                        khkw = w[0, 0].numel() if w.dim() == 4 else 1
+                        groups = int(getattr(layer, 'groups', 1)) if kind == 'conv' else 1
+                        if groups * int(w.shape[1]) != fw.numel() or int(w.shape[0]) % groups:
+                            raise ValueError('act_range_plan: {} takes {} x {} channels, the BatchNorm {} in front of it has {}'.format(
+                                lkey, groups, int(w.shape[1]), bkey, fw.numel()))
+                        pw = in_slot(lkey, 'weight', w)
+                        pb = in_slot(lkey, 'bias', layer.bias) if layer.bias is not None else None
+                        for vec, name in ((fb, 'fake_bias'), (fw, 'fake_weight')):
+                            sources.append(_ffi.DfqBatchActSource(pw, pb, in_slot(bkey, name, vec), int(w.shape[0]), int(w.shape[1]),
+                                                                  khkw, groups))
+                        steps.append(_ffi.DfqBatchActStep(None, None, op, int(w.shape[0]), relu, 0, len(sources) - 1, len(sources) - 2,
+                                                          0.0, 0.0))
+                        continue
+                    if op in (_ffi.ACT_MOM, _ffi.ACT_MOM_ADD):
+                        if channels is None:
+                            channels = fw.numel()
+                        elif fw.numel() != channels:
+                            raise ValueError('act_range_plan: {}: {} feeds an add of {} channels with {}'.format(key, bkey, channels, fw.numel()))
+                    steps.append(_ffi.DfqBatchActStep(in_slot(bkey, 'fake_weight', fw), in_slot(bkey, 'fake_bias', fb), op, fw.numel(),
+                                                      relu, 0, -1, -1, 0.0, 0.0))
+        self.keys = [key for (key, _, _, _) in self._views]
+        self.n_nets, self.n_results, self.n_steps, self.n_sources = len(batch.nets), len(results), len(steps), len(sources)
+        self.block = torch.zeros((self.n_nets, self.n_results, 2), dtype=torch.float32, device=batch.stage.device)
+        res_arr = (_ffi.DfqBatchActResult * len(results))(*results)
+        step_arr = (_ffi.DfqBatchActStep * len(steps))(*steps)
+        src_arr = (_ffi.DfqBatchActSource * len(sources))(*sources) if sources else None
+        self._plan = ctypes.c_void_p()
+        _ffi.check(_ffi.lib().dfq_batch_act_plan_create(
+            res_arr, len(results), step_arr, len(steps), src_arr, len(sources),
+            batch.bases.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)), self.n_nets, ctypes.c_float(n_sigma), ctypes.c_float(self.eps),
+            self.block.data_ptr(), 2 * self.n_results, ctypes.byref(self._plan)))
+        self.launches = int(_ffi.lib().dfq_batch_act_plan_launches(self._plan))
+
+    def run(self):
+        """Compute every range of every network, asynchronously on the current stream."""
+        if self._batch.storage is None:
+            raise RuntimeError('NetworkBatch: the batch has been released')
+        if not self._plan:
+            raise RuntimeError('BatchActRangePlan: the plan has been closed')
+        _ffi.check(_ffi.lib().dfq_batch_act_plan_run(self._plan, _ffi.stream_arg()))
+
+    def ranges(self, n):
+        """OrderedDict graph key -> float32 [2] view (min, max) of network n's part of the block, in set_quant_minmax's
+        order; a list of such views for a tensor op (one per quantised input)"""
+        rows = self.block[n]
+        out = OrderedDict()
+        for key, first, count, is_op in self._views:
+            out[key] = [rows[first + i] for i in range(count)] if is_op else rows[first]
+        return out
+
+    def bind_quantisers(self, tensor_op_quant=None):
+        """Point ``running_min`` / ``running_max`` of every quantiser module of every network at its pair in the block: no
+        launch, no copy.  The two buffers become the halves of one float32[2], which is the packed pair
+        ``QuantMeasure._packed_range`` looks for, so a later forward pass adopts it as it is.  ``tensor_op_quant``: one
+        ``{graph key: [QuantMeasure, ...]}`` per network for the tensor ops the plan was created with.  Run (and let finish)
+        the plan before anything reads the buffers; ``NetworkBatch.release()`` gives them storages of their own."""
+        batch = self._batch
+        if batch.storage is None:
+            raise RuntimeError('NetworkBatch: the batch has been released')
+        if tensor_op_quant is not None and len(tensor_op_quant) != self.n_nets:
+            raise ValueError('bind_quantisers: tensor_op_quant wants one dict per network')
+        for n, (graph, _, _) in enumerate(batch.nets):
+            rows = self.block[n]
+            for key, first, count, is_op in self._views:
+                node = graph[key]
+                if is_op:
+                    mods = (tensor_op_quant[n].get(key) if tensor_op_quant is not None else None) or []
+                else:
+                    mods = [node.quant] if hasattr(node, 'quant') else []
+                for i, q in enumerate(mods[:count]):
+                    _rebind(q, 'running_min', rows[first + i, 0:1])
+                    _rebind(q, 'running_max', rows[first + i, 1:2])
+                    batch._act_bound[id(q)] = (q, self.block)
+
+    def close(self):
+        if self._plan:
+            _ffi.lib().dfq_batch_act_plan_destroy(self._plan)
             self._plan = None
 
     def __del__(self):

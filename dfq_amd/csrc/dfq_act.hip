@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "dfq_act_shared.hpp"
 #include "dfq_common.hpp"
 
 namespace dfq {
@@ -26,24 +27,6 @@ struct BnRangeReq {
     int32_t channels;
     int32_t relu_mode;     // 0 none, 1 ReLU, 2 ReLU6
 };
-
-// torch.min / torch.max propagate NaN
-__device__ __forceinline__ float nan_min(float a, float b) { return (a < b || a != a) ? a : b; }
-__device__ __forceinline__ float nan_max(float a, float b) { return (a > b || a != a) ? a : b; }
-
-__device__ __forceinline__ void block_minmax(float& mn, float& mx, float* sh) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        mn = nan_min(mn, __shfl_xor(mn, m));
-        mx = nan_max(mx, __shfl_xor(mx, m));
-    }
-    const int wave = threadIdx.x / kWave;
-    if (threadIdx.x % kWave == 0) { sh[2 * wave] = mn; sh[2 * wave + 1] = mx; }
-    __syncthreads();
-    mn = sh[0]; mx = sh[1];
-#pragma unroll
-    for (int w = 1; w < kBlock / kWave; ++w) { mn = nan_min(mn, sh[2 * w]); mx = nan_max(mx, sh[2 * w + 1]); }
-}
 
 // get_min_value / get_max_value (layer_transform.py:403-404) + the ReLU clamps of :468-469, one request
 // per workgroup
@@ -64,47 +47,6 @@ __global__ __launch_bounds__(kBlock) void bn_ranges_kernel(const BnRangeReq* __r
         out[2 * blockIdx.x + 0] = mn;
         out[2 * blockIdx.x + 1] = mx;
     }
-}
-
-// calculate_mean / calculate_var (:407-410)
-__device__ __forceinline__ void moments_relu(float w, float b, float& mean, float& var) {
-    const float t = (-b) / w;
-    float pdf, cdf;
-    normal_pdf_cdf(t, pdf, cdf);
-    const float one_m = 1.0f - cdf;
-    mean = w * pdf + b * one_m;
-    const float poly = ((b * b + w * w) + mean * mean) - (2.0f * mean) * b;
-    const float t1 = one_m * poly;
-    const float t2 = (w * (b - 2.0f * mean)) * pdf;
-    const float t3 = (mean * mean) * cdf;
-    var = (t1 + t2) + t3;
-}
-
-// calculate_mean_6 / calculate_var_6 (:411-418)
-__device__ __forceinline__ void moments_relu6(float w, float b, float& mean, float& var) {
-    const float lo = (-b) / w;
-    const float hi = (6.0f - b) / w;
-    float pdf_lo, cdf_lo, pdf_hi, cdf_hi;
-    normal_pdf_cdf(lo, pdf_lo, cdf_lo);
-    normal_pdf_cdf(hi, pdf_hi, cdf_hi);
-    const float dp = pdf_lo - pdf_hi;
-    const float dc = cdf_hi - cdf_lo;
-    const float top = 1.0f - cdf_hi;
-    mean = (w * dp + b * dc) + 6.0f * top;
-    const float poly = ((b * b + w * w) + mean * mean) - (2.0f * mean) * b;
-    const float t1 = dc * poly;
-    const float t2 = (w * -6.0f) * pdf_hi;
-    const float t3 = (w * (b - 2.0f * mean)) * dp;
-    const float t4 = (mean * mean) * cdf_lo;
-    const float d6 = 6.0f - mean;
-    const float t5 = (d6 * d6) * top;
-    var = (((t1 + t2) + t3) + t4) + t5;
-}
-
-__device__ __forceinline__ void moments_of(int mode, float w, float b, float& mean, float& var) {
-    if (mode == 1) moments_relu(w, b, mean, var);
-    else if (mode == 2) moments_relu6(w, b, mean, var);
-    else { mean = b; var = w * w; }                     // :505-507
 }
 
 __global__ __launch_bounds__(kBlock) void relu_moments_kernel(const float* __restrict__ w, const float* __restrict__ b,

@@ -456,6 +456,79 @@ int32_t dfq_batch_absorb_plan_launches(const dfq_batch_absorb_plan* plan);
 /* weights per network that are read for a row sum, and weights that are only clipped (either pointer may be null) */
 int dfq_batch_absorb_plan_elements(const dfq_batch_absorb_plan* plan, int64_t* absorbed, int64_t* clip_only);
 
+/* Analytic activation ranges of a whole batch of networks of one architecture (extension; set_quant_minmax,
+ * utils/layer_transform.py:347-609, main_cls.py:188, for every network of a batch at once).  The caller walks the graph of
+ * the FIRST network once (find_prev_bn, :299-344, and the branch grouping of :476-580) and hands over what the walk found
+ * as a small program: one RESULT per quantiser, each a run of STEPS that one workgroup executes per network.  Network n's
+ * copy of a tensor lies bases[n] - bases[0] bytes further.  The steps are the arithmetic of :403-418 and :444-601:
+ *   CONST       (min, max) = (lo, hi): the quantiser of the network's input (:443-449)
+ *   RANGE       (min, max) = (min_c beta - N gamma, max_c beta + N gamma), min clamped at 0 behind ReLU / ReLU6, max at 6
+ *               behind ReLU6 (:403-404, :468-469); what dfq_bn_ranges computes
+ *   RANGE_CAT   min = min(min, lo); max = max(max, hi) of another such pair (:560-562)
+ *   RANGE_ONE   min += max(0., lo); max += hi (:563-567)
+ *   RANGE_DIV   min /= operand; max /= operand (operand = bound + 1, :569-570)
+ *   MOM         per-channel (mean, var) of N(beta, gamma^2) behind `relu_mode` (:494-507); what dfq_relu_moments computes
+ *   MOM_ADD     mean += mean', var += var' of another BatchNorm (:521-531)
+ *   MOM_RELU    (mean, var) of N(mean, var + eps) behind ReLU / ReLU6 (:533-540); what dfq_moments_after_add computes
+ *   MOM_RANGE   (min, max) = (min_c mean - N sqrt(var + eps), max_c mean + N sqrt(var + eps)) (:571-573); dfq_moment_range
+ * A result is CONST alone, or RANGE followed by RANGE_CAT / RANGE_ONE / RANGE_DIV steps, or MOM followed by MOM_ADD /
+ * MOM_RELU steps of the same channel count and closed by MOM_RANGE.  A RANGE* step with `source_weight >= 0` reads its two
+ * vectors not from a BatchNorm but from SOURCES (case d, :451-466): a proxy vector pushed through a conv / linear layer that
+ * has no BatchNorm of its own, v_out[o] = sum_i (sum_k W[o, i, k]) v_in[g(o) I/g + i] + bias[o], what dfq_bn_through_layer
+ * computes; the plan keeps them in a block of its own, written by a first launch.
+ * Per-channel arithmetic in float32 in the order of those single-network entry points, the fold over channels with their
+ * NaN-propagating min / max and partition, the scalar steps in float64 (Python floats in the reference), rounded to float32
+ * once at the store into `out` [n_nets][out_stride] at 2 * result: bit-identical to set_quant_minmax on that network alone.
+ * One launch (n_results * n_nets workgroups), two with sources; no workgroup waits for another; nothing but `out` and the
+ * plan's own block is written.  create: DFQ_ERR_ARG (and dfq_last_error) for null / empty tables, a result whose steps are
+ * not one of the three shapes above, an unknown opcode or ReLU mode, a null vector, channel counts that disagree, a source
+ * index out of range, a source geometry dfq_bn_through_layer refuses, a non-finite n_sigma, an `out_stride` below
+ * 2 * n_results.  Every tensor of network 0 must lie inside network 0's slot: nothing here can check that.  Synchronises
+ * (create only); run is asynchronous on `stream` and copies nothing. */
+#define DFQ_ACT_CONST 0
+#define DFQ_ACT_RANGE 1
+#define DFQ_ACT_RANGE_CAT 2
+#define DFQ_ACT_RANGE_ONE 3
+#define DFQ_ACT_RANGE_DIV 4
+#define DFQ_ACT_MOM 5
+#define DFQ_ACT_MOM_ADD 6
+#define DFQ_ACT_MOM_RELU 7
+#define DFQ_ACT_MOM_RANGE 8
+typedef struct dfq_batch_act_plan dfq_batch_act_plan;
+typedef struct dfq_batch_act_result {
+    int32_t step_begin;     /* into `steps`                                                                */
+    int32_t step_count;
+} dfq_batch_act_result;
+typedef struct dfq_batch_act_step {
+    const float* fake_weight;   /* gamma~ [channels], network 0 (RANGE*, MOM, MOM_ADD without sources)        */
+    const float* fake_bias;     /* beta~  [channels]                                                          */
+    int32_t opcode;             /* DFQ_ACT_*                                                                   */
+    int32_t channels;
+    int32_t relu_mode;          /* 0 none, 1 ReLU, 2 ReLU6                                                     */
+    int32_t operand;            /* RANGE_DIV: the divisor                                                      */
+    int32_t source_weight;      /* >= 0: the vectors are sources `source_weight` / `source_bias`, not a BN's   */
+    int32_t source_bias;
+    float lo;                   /* CONST                                                                       */
+    float hi;
+} dfq_batch_act_step;
+typedef struct dfq_batch_act_source {
+    const float* weight;        /* [out_ch, in_per_group, khkw], network 0                                     */
+    const float* bias;          /* [out_ch] or null                                                            */
+    const float* vector;        /* the proxy vector pushed through the layer [groups * in_per_group]           */
+    int32_t out_ch;
+    int32_t in_per_group;
+    int32_t khkw;
+    int32_t groups;
+} dfq_batch_act_source;
+
+int dfq_batch_act_plan_create(const dfq_batch_act_result* results, int32_t n_results, const dfq_batch_act_step* steps, int32_t n_steps,
+                              const dfq_batch_act_source* sources, int32_t n_sources, const void* const* bases, int32_t n_nets,
+                              float n_sigma, float eps, float* out, int64_t out_stride, dfq_batch_act_plan** out_plan);
+void dfq_batch_act_plan_destroy(dfq_batch_act_plan* plan);
+int dfq_batch_act_plan_run(dfq_batch_act_plan* plan, void* stream);
+/* launches per run (1, or 2 with sources) */
+int32_t dfq_batch_act_plan_launches(const dfq_batch_act_plan* plan);
+
 /* ------------------------------------------------------------------------------------------
  * Lazy-scale equalisation (opt-in extension): the sweeps of dfq.py:83-101 with a GIVEN sweep count,
  * computed from the pristine weights and the cumulative scale vectors of utils/relation.py:20-24 -- a sweep only READS
