@@ -7,8 +7,9 @@ batch cost, against 7.6 ms of GPU work for the whole calibration.  ``NetworkBatc
 is put together (model loading, not calibration), into one allocation in which network n's tensors sit at the same offsets
 from ``base + n * stride``; the modules' parameters and buffers are re-pointed at those slots (views, so the models keep
 working as before; ``release()`` gives them storages of their own again -- do that before saving or deep-copying a packed
-model, because torch pickles and copies a view together with its whole storage).  A plan over the batch is then the tables of the FIRST network plus one base address per network
-(``dfq_le_plan_create_replicated`` / ``dfq_bc_plan_create_replicated``, include/dfq_hip.h): no per-tensor host work at all.
+model, because torch pickles and copies a view together with its whole storage).  A plan over the batch is then the tables
+of the FIRST network plus one base address per network (``dfq_le_plan_create_replicated`` /
+``dfq_bc_plan_create_replicated``, include/dfq_hip.h): no per-tensor host work at all.
 
 This is the host side of the reference's per-network graph walks (dfq.py:78-82, :194-270) for a batch; the arithmetic is the
 engine's, unchanged -- the plans a NetworkBatch creates are the plans ``build_le_plan_batch`` / ``build_bc_plan_batch``
@@ -16,11 +17,13 @@ would create over the same tensors (tests/test_arena.py).  ``quant_plan`` is the
 (layer_transform.py:279-296, main_cls.py:178-181): one plan, one or two launches for every network of the batch, the
 integer codes and ranges in two caller-visible blocks (tests/test_batch_quant.py).  ``absorb_plan`` is the batch form of the
 two optional steps between equalisation and correction, ``bias_absorption`` (dfq.py:121-164) and ``clip_weight``
-(dfq.py:167-170): two launches for the whole batch, every weight read once (tests/test_batch_absorb.py).  ``act_range_plan`` is the batch form of
-``set_quant_minmax`` (layer_transform.py:347-609, main_cls.py:188), the analytic activation ranges: the graph walk is made
-once, on network 0, and one launch (two with a conv / linear without BatchNorm in front of a quantiser) fills one block of
-packed (min, max) pairs the quantisers are then pointed at (tests/test_batch_act.py).  With them the default calibration
-sequence main_cls.py:149-190 runs on a batch as le_plan -> absorb_plan -> bc_plan -> quant_plan -> act_range_plan.
+(dfq.py:167-170): two launches for the whole batch, every weight read once (tests/test_batch_absorb.py).
+``act_range_plan`` is the batch form of ``set_quant_minmax`` (layer_transform.py:347-609, main_cls.py:188), the analytic
+activation ranges: the graph walk both share (``utils.layer_transform._act_program``; this module holds no walk of its own)
+is made once, on network 0, and one launch (two with a conv / linear without BatchNorm in front of a quantiser) fills one
+block of packed (min, max) pairs the quantisers are then pointed at (tests/test_batch_act.py).  With them the default
+calibration sequence main_cls.py:149-190 runs on a batch as le_plan -> absorb_plan -> bc_plan -> quant_plan ->
+act_range_plan.
 """
 from __future__ import annotations
 
@@ -33,7 +36,7 @@ import torch
 
 from . import _ffi
 from . import dfq as _dfq
-from .utils.layer_transform import _RELU_MODE, _ensure_bias, find_prev_bn
+from .utils.layer_transform import _WalkError, _act_program, _ensure_bias
 
 _ALIGN = 64            # floats: every tensor starts on a 256-byte boundary (vector loads, the alignment hipMalloc gives)
 
@@ -203,6 +206,15 @@ class NetworkBatch:
         self.storage = None
 
     # -- plans ---------------------------------------------------------------------------------------------------------
+    def _in_slot(self, key, name, t):
+        """address of `t`, a tensor of network 0: a batch plan finds network n's copy at that address + bases[n] - bases[0],
+        so t has to lie in network 0's slot"""
+        lo, p = self._base_ints[0], t.data_ptr()
+        if not (t.dtype is torch.float32 and t.is_contiguous() and lo <= p and p + 4 * t.numel() <= lo + 4 * self.stride):
+            raise RuntimeError('NetworkBatch: {} of {} in network 0 no longer lives in its slot of the batch allocation'.format(
+                name, key))
+        return p
+
     def _tables(self, T):
         out = _dfq._Tables()
         out.arrays = T.arrays
@@ -274,7 +286,6 @@ class NetworkBatch:
             return [plan.codes(i) for i in range(n)], [plan.ranges(i) for i in range(n)]
         finally:
             plan.close()
-
 
     def absorb_plan(self, N=3, range_clip=None, absorb=True):
         """One plan (BatchAbsorbPlan) for ``bias_absorption(graph, relations, bottoms, N)`` followed, if ``range_clip`` is
@@ -348,10 +359,59 @@ def _check_bits(bits, per_channel, what):
     return b
 
 
-class BatchQuantPlan:
+def _finite(N, who):
+    """N as a float, or ValueError('<who>: N ...'): a number, finite, not a bool"""
+    try:
+        n_sigma = float(N)
+    except (TypeError, ValueError):
+        raise ValueError('{}: N {!r} is not a number'.format(who, N)) from None
+    if isinstance(N, bool) or not math.isfinite(n_sigma):
+        raise ValueError('{}: N {!r} is not a finite number'.format(who, N))
+    return n_sigma
+
+
+class _BatchPlan:
+    """What the plans over a NetworkBatch share: the handle of the C plan (``_c``_create / _run / _destroy / _launches of
+    include/dfq_hip.h, which all take network 0's tables and the batch's base addresses), ``launches``, ``run()`` and
+    ``close()``.  A subclass builds its tables in its constructor and hands them to ``_create``."""
+    _c = None                                   # 'dfq_batch_<step>_plan'
+
+    def __init__(self, batch):
+        self._batch, self._plan, self.launches = batch, None, 0
+
+    def _create(self, tables, *rest):
+        """<_c>_create(*tables, base addresses, number of networks, *rest, &plan)"""
+        batch, lib = self._batch, _ffi.lib()
+        self._plan = ctypes.c_void_p()
+        _ffi.check(getattr(lib, self._c + '_create')(*tables, batch.bases.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)),
+                                                     len(batch.nets), *rest, ctypes.byref(self._plan)))
+        self.launches = int(getattr(lib, self._c + '_launches')(self._plan))
+
+    def run(self):
+        """Enqueue the plan's launches, which cover every network of the batch, on the current stream (asynchronous)."""
+        if self._batch.storage is None:
+            raise RuntimeError('NetworkBatch: the batch has been released')
+        if not self._plan:
+            raise RuntimeError('{}: the plan has been closed'.format(type(self).__name__))
+        _ffi.check(getattr(_ffi.lib(), self._c + '_run')(self._plan, _ffi.stream_arg()))
+
+    def close(self):
+        if self._plan:
+            getattr(_ffi.lib(), self._c + '_destroy')(self._plan)
+            self._plan = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BatchQuantPlan(_BatchPlan):
     """Weight quantisation of every network of a NetworkBatch (dfq_batch_quant_plan, include/dfq_hip.h): network 0's tensor
     table plus the batch's base addresses.  ``run()`` enqueues on the current stream; the weights and biases are quantised in
     place, the codes and ranges written to blocks [n_nets, stride] the plan owns and hands out as views."""
+    _c = 'dfq_batch_quant_plan'
 
     def __init__(self, batch, bit_weight, bits_bias, per_channel, signed, codes):
         bit_weight = _check_bits(bit_weight, per_channel, 'bit_weight')
@@ -362,7 +422,7 @@ class BatchQuantPlan:
             raise ValueError("quant_plan: codes must be None, 'int32' or 'int8', got {!r}".format(codes))
         if codes == 'int8' and bit_weight > 8:
             raise ValueError('quant_plan: 1-byte codes need bit_weight <= 8, got {}'.format(bit_weight))
-        self._batch = batch
+        super().__init__(batch)
         self.per_channel, self.signed = bool(per_channel), bool(signed)
         n_nets = len(batch.nets)
         dev = batch.stage.device
@@ -370,15 +430,7 @@ class BatchQuantPlan:
         tt = tuple(batch.targ_type)
         entries, self._code_views, self._range_views = [], [], []
         code_stride = range_stride = 0
-        lo, hi = int(batch.bases[0]), int(batch.bases[0]) + 4 * batch.stride
-
-        def in_slot(key, name, t):
-            """network n's copy is written at t's address + bases[n] - bases[0]: t has to be network 0's slot"""
-            p = t.data_ptr()
-            if not (t.dtype is torch.float32 and t.is_contiguous() and lo <= p and p + 4 * t.numel() <= hi):
-                raise RuntimeError('NetworkBatch: {} of {} in network 0 no longer lives in its slot of the batch allocation'.format(
-                    name, key))
-            return p
+        in_slot = batch._in_slot
         for key, layer in g0.items():
             if type(layer) not in tt:
                 continue
@@ -407,20 +459,8 @@ class BatchQuantPlan:
         self.range_block = torch.empty((n_nets, range_stride), dtype=torch.float32, device=dev)
         self.n_nets, self.n_tensors = n_nets, len(entries)
         arr = (_ffi.DfqBatchQuantTensor * len(entries))(*entries)
-        self._plan = ctypes.c_void_p()
-        _ffi.check(_ffi.lib().dfq_batch_quant_plan_create(
-            arr, len(entries), batch.bases.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)), n_nets,
-            None if self.code_block is None else self.code_block.data_ptr(), 1 if codes == 'int8' else 4, code_stride,
-            self.range_block.data_ptr(), range_stride, ctypes.byref(self._plan)))
-        self.launches = int(_ffi.lib().dfq_batch_quant_plan_launches(self._plan))
-
-    def run(self):
-        """Quantise every network, asynchronously on the current stream."""
-        if self._batch.storage is None:
-            raise RuntimeError('NetworkBatch: the batch has been released')
-        if not self._plan:
-            raise RuntimeError('BatchQuantPlan: the plan has been closed')
-        _ffi.check(_ffi.lib().dfq_batch_quant_plan_run(self._plan, _ffi.stream_arg()))
+        self._create((arr, len(entries)), None if self.code_block is None else self.code_block.data_ptr(),
+                     1 if codes == 'int8' else 4, code_stride, self.range_block.data_ptr(), range_stride)
 
     def codes(self, n):
         """{graph key: integer codes of network n's weight, shaped like it} -- views of the code block"""
@@ -434,31 +474,16 @@ class BatchQuantPlan:
         row = self.range_block[n]
         return {key: row[off:off + 2 * (shape[0] if len(shape) == 2 else 1)].view(shape) for (key, off, shape) in self._range_views}
 
-    def close(self):
-        if self._plan:
-            _ffi.lib().dfq_batch_quant_plan_destroy(self._plan)
-            self._plan = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class BatchAbsorbPlan:
+class BatchAbsorbPlan(_BatchPlan):
     """Bias absorption and weight clipping of every network of a NetworkBatch (dfq_batch_absorb_plan, include/dfq_hip.h):
     network 0's relation table plus the batch's base addresses.  ``run()`` enqueues on the current stream; biases, the
     BatchNorm proxies' ``fake_bias`` and the clipped weights change in place, the shift vectors c = max(0, beta~ - N gamma~)
     every update used are kept in a block [n_nets, stride] the plan owns (``shifts(n)``)."""
+    _c = 'dfq_batch_absorb_plan'
 
     def __init__(self, batch, N, range_clip, absorb):
-        try:
-            n_sigma = float(N)
-        except (TypeError, ValueError):
-            raise ValueError('absorb_plan: N {!r} is not a number'.format(N)) from None
-        if isinstance(N, bool) or not math.isfinite(n_sigma):
-            raise ValueError('absorb_plan: N {!r} is not a finite number'.format(N))
+        n_sigma = _finite(N, 'absorb_plan')
         lo = hi = 0.0
         if range_clip is not None:
             try:
@@ -467,19 +492,11 @@ class BatchAbsorbPlan:
                 raise ValueError('absorb_plan: range_clip {!r} is not a pair of numbers'.format(range_clip)) from None
             if not lo <= hi:
                 raise ValueError('absorb_plan: range_clip {!r} is not a range lo <= hi'.format(range_clip))
-        self._batch = batch
+        super().__init__(batch)
         n_nets = len(batch.nets)
         g0, b0, r0 = batch.nets[0]
         tt = tuple(batch.targ_type)
-        slot_lo, slot_hi = int(batch.bases[0]), int(batch.bases[0]) + 4 * batch.stride
-
-        def in_slot(key, name, t):
-            """network n's copy is found at t's address + bases[n] - bases[0]: t has to be network 0's slot"""
-            p = t.data_ptr()
-            if not (t.dtype is torch.float32 and t.is_contiguous() and slot_lo <= p and p + 4 * t.numel() <= slot_hi):
-                raise RuntimeError('NetworkBatch: {} of {} in network 0 no longer lives in its slot of the batch allocation'.format(
-                    name, key))
-            return p
+        in_slot = batch._in_slot
         rels, self._shift_views = [], []
         stride = 0
         for idx, rr in enumerate(r0 if absorb else ()):
@@ -510,160 +527,28 @@ class BatchAbsorbPlan:
         self.shift_block = torch.zeros((n_nets, stride), dtype=torch.float32, device=batch.stage.device)
         rel_arr = (_ffi.DfqBatchAbsorbRelation * len(rels))(*rels) if rels else None
         clip_arr = (_ffi.DfqBatchAbsorbClip * len(clips))(*clips) if clips else None
-        self._plan = ctypes.c_void_p()
-        _ffi.check(_ffi.lib().dfq_batch_absorb_plan_create(
-            rel_arr, len(rels), clip_arr, len(clips), batch.bases.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)), n_nets,
-            ctypes.c_float(n_sigma), ctypes.c_float(lo), ctypes.c_float(hi),
-            self.shift_block.data_ptr() if rels else None, stride, ctypes.byref(self._plan)))
-        self.launches = int(_ffi.lib().dfq_batch_absorb_plan_launches(self._plan))
+        self._create((rel_arr, len(rels), clip_arr, len(clips)), ctypes.c_float(n_sigma), ctypes.c_float(lo), ctypes.c_float(hi),
+                     self.shift_block.data_ptr() if rels else None, stride)
         a, c = ctypes.c_int64(), ctypes.c_int64()
         _ffi.check(_ffi.lib().dfq_batch_absorb_plan_elements(self._plan, ctypes.byref(a), ctypes.byref(c)))
         self.absorbed_elements, self.clip_only_elements = a.value, c.value          # per network
-
-    def run(self):
-        """Absorb and clip every network, asynchronously on the current stream."""
-        if self._batch.storage is None:
-            raise RuntimeError('NetworkBatch: the batch has been released')
-        if not self._plan:
-            raise RuntimeError('BatchAbsorbPlan: the plan has been closed')
-        _ffi.check(_ffi.lib().dfq_batch_absorb_plan_run(self._plan, _ffi.stream_arg()))
 
     def shifts(self, n):
         """{index into the relations list: the shift vector c of network n} for the absorbed relations -- views of the block"""
         row = self.shift_block[n]
         return {idx: row[off:off + o1] for (idx, off, o1) in self._shift_views}
 
-    def close(self):
-        if self._plan:
-            _ffi.lib().dfq_batch_absorb_plan_destroy(self._plan)
-            self._plan = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _act_program(graph, bottoms, bn_type, targ_type, tensor_ops, is_detection):
-    """The walk of set_quant_minmax (layer_transform.py:347-609) over ONE graph, compiled instead of executed:
-    [(graph key, [result, ...])] in the order that function meets the quantised nodes, a result being the list of steps
-    (opcode, bn or None, relu mode, operand, case-(d) layer or None) whose execution gives one quantiser's (min, max).  Same
-    node classification, same ``find_prev_bn``, same branch grouping and ordering, so the steps of a result are the launches
-    ``set_quant_minmax`` issues for it, in its order.  What that function asserts, or would trip over, is a ValueError here."""
-    A = _ffi
-    tt = tuple(targ_type)
-    bn_module, relu_attached, nodes = {}, {}, []
-    for key in graph:
-        bot = bottoms[key]
-        if bot is None:
-            continue
-        layer = graph[key]
-        if type(layer) == bn_type:
-            bn_module[key] = layer
-            relu_attached[key] = 'none'
-            continue
-        if type(layer) == torch.nn.ReLU:
-            relu_attached[bot[0]] = 'relu'
-        elif type(layer) == torch.nn.ReLU6:
-            relu_attached[bot[0]] = 'relu6'
-        if isinstance(layer, str):
-            count = tensor_ops.get(key)
-        elif hasattr(layer, 'quant') or type(layer) in tt:
-            count = 1
-        else:
-            count = None
-        if count is None:
-            continue
-        if len(bot) == 1 and bot[0] == 'Data':                     # :443-449 (only the first quantiser of the node is set)
-            lo, hi = (-1.0, 1.0) if is_detection else (-2.11790393, 2.64)
-            nodes.append((key, [[(A.ACT_CONST, None, 0, (lo, hi), None)]]))
-            continue
-        try:
-            bn_list, relu_list, connect_list, no_bn = find_prev_bn(bn_module, relu_attached, graph, bottoms, bot[:])
-        except AssertionError as e:
-            raise ValueError('act_range_plan: {}: {}'.format(key, e)) from None
-        if count == len(bn_list):                                   # 1 to 1 mapping (:444-474)
-            results = []
-            for (bn, bid), relu in zip(bn_list, relu_list):
-                if bid[0] in no_bn:                                 # case (d): no ReLU clamp in the reference
-                    results.append([(A.ACT_RANGE, bn, 0, 0, no_bn[bid[0]])])
-                else:
-                    results.append([(A.ACT_RANGE, bn, _RELU_MODE[relu], 0, None)])
-            nodes.append((key, results))
-            continue
-        # ---- 1 to many / many to many (:476-601) ----
-        branches = OrderedDict()
-        for ent, relu, ctype in zip(bn_list, relu_list, connect_list):
-            branches.setdefault(ent[1][0], []).append((ent, relu, ctype))
-        compiled = OrderedDict()
-        for bkey, items in branches.items():
-            def bad(why):
-                return ValueError('act_range_plan: {}: branch {} {} (set_quant_minmax cannot evaluate it either)'.format(key, bkey, why))
-            items = sorted(items, key=lambda x: len(x[0][1]), reverse=True)
-            (bn, bid), use_relu, connect_type = items.pop(0)
-            depth = len(bid)
-            moments = 'add' in connect_type
-            steps = [(A.ACT_MOM if moments else A.ACT_RANGE, bn, _RELU_MODE[use_relu], 0, None)]
-            while items:
-                bound = 0
-                while bound < len(items) and len(items[bound][0][1]) == depth:
-                    bound += 1
-                if bound == 0:
-                    depth = len(items[0][0][1])                     # cut depth
-                    continue
-                for (bn, bid), relu_t, connect_type in items[:bound]:
-                    if 'add' in connect_type:
-                        if not moments:
-                            raise bad('meets an add after a cat / plain connection')
-                        steps.append((A.ACT_MOM_ADD, bn, _RELU_MODE[relu_t], 0, None))
-                        if 'relu6' in connect_type:
-                            steps.append((A.ACT_MOM_RELU, None, 2, 0, None))
-                        elif 'relu' in connect_type:
-                            steps.append((A.ACT_MOM_RELU, None, 1, 0, None))
-                    elif moments:
-                        raise bad('meets a cat / plain connection after an add')
-                    elif connect_type == 'cat':
-                        steps.append((A.ACT_RANGE_CAT, bn, _RELU_MODE[relu_t], 0, None))
-                    else:                                           # `if use_relu_tmp` is always true: clamp at 0, in the step
-                        steps.append((A.ACT_RANGE_ONE, bn, 0, 0, None))
-                items = items[bound:]
-                if connect_type == 'one':
-                    if moments:
-                        raise bad('meets a cat / plain connection after an add')
-                    steps.append((A.ACT_RANGE_DIV, None, 0, bound + 1, None))
-            if ('add' in connect_type) != moments:
-                raise bad('mixes adds with cat / plain connections')
-            if moments:
-                steps.append((A.ACT_MOM_RANGE, None, 0, 0, None))
-            compiled[bkey] = steps
-        if count == 1 and count < len(bn_list):                     # 1 to many
-            if len(compiled) != 1:
-                raise ValueError('act_range_plan: {}: error occurs when setting min/max, should be 1 to many'.format(key))
-            nodes.append((key, [list(compiled.values())[0]]))
-        elif count < len(bn_list):                                  # many to many
-            if len(compiled) != count or any(str(i) not in compiled for i in range(count)):
-                raise ValueError('act_range_plan: {}: LENGTH NOT EQUAL {} vs {}'.format(key, len(compiled), count))
-            nodes.append((key, [compiled[str(i)] for i in range(count)]))
-        else:
-            raise ValueError('act_range_plan: {}: {} quantisers for {} BatchNorm layers'.format(key, count, len(bn_list)))
-    return nodes
-
-
-class BatchActRangePlan:
+class BatchActRangePlan(_BatchPlan):
     """The analytic activation ranges of every network of a NetworkBatch (dfq_batch_act_plan, include/dfq_hip.h): the program
     compiled from network 0's graph plus the batch's base addresses.  ``run()`` enqueues on the current stream; it reads the
     BatchNorm proxies (and, for a conv / linear without BatchNorm in front of a quantiser, that layer's weight and bias) and
     writes only ``self.block``, float32 [n_nets, n_results, 2]: the packed (min, max) pairs in the layout ``QuantMeasure``
     keeps its range in.  The block is a torch tensor and outlives ``close()``."""
+    _c = 'dfq_batch_act_plan'
 
     def __init__(self, batch, is_detection, N, tensor_ops):
-        try:
-            n_sigma = float(N)
-        except (TypeError, ValueError):
-            raise ValueError('act_range_plan: N {!r} is not a number'.format(N)) from None
-        if isinstance(N, bool) or not math.isfinite(n_sigma):
-            raise ValueError('act_range_plan: N {!r} is not a finite number'.format(N))
+        n_sigma = _finite(N, 'act_range_plan')
         g0, b0, _ = batch.nets[0]
         ops = OrderedDict()
         for key, count in (tensor_ops or {}).items():
@@ -672,21 +557,16 @@ class BatchActRangePlan:
             if isinstance(count, bool) or not isinstance(count, (int, np.integer)) or count <= 0:
                 raise ValueError('act_range_plan: tensor_ops[{!r}] = {!r} is not a positive count'.format(key, count))
             ops[key] = int(count)
-        self._batch = batch
+        super().__init__(batch)
         self.is_detection, self.n_sigma, self.eps = bool(is_detection), n_sigma, 1e-6          # eps: layer_transform.py:349
-        nodes = _act_program(g0, b0, batch.bn_type, batch.targ_type, ops, self.is_detection)
+        try:
+            nodes = _act_program(g0, b0, batch.bn_type, batch.targ_type, ops, self.is_detection)
+        except _WalkError as e:                 # what set_quant_minmax asserts, or cannot evaluate
+            raise ValueError('act_range_plan: {}: {}'.format(e.key, e)) from None
         if not nodes:
             raise ValueError('act_range_plan: the graph has no quantised node')
         key_of = {id(m): k for k, m in g0.items() if isinstance(m, torch.nn.Module)}
-        slot_lo, slot_hi = int(batch.bases[0]), int(batch.bases[0]) + 4 * batch.stride
-
-        def in_slot(key, name, t):
-            """network n's copy is found at t's address + bases[n] - bases[0]: t has to be network 0's slot"""
-            p = t.data_ptr()
-            if not (t.dtype is torch.float32 and t.is_contiguous() and slot_lo <= p and p + 4 * t.numel() <= slot_hi):
-                raise RuntimeError('NetworkBatch: {} of {} in network 0 no longer lives in its slot of the batch allocation'.format(
-                    name, key))
-            return p
+        in_slot = batch._in_slot
 
         def proxies(bn):
             key = key_of.get(id(bn), '?')
@@ -698,9 +578,9 @@ class BatchActRangePlan:
             return key, fw, fb
         results, steps, sources = [], [], []
         self._views = []                       # (graph key, first result, number of results, is a tensor op)
-        for key, node_results in nodes:
+        for key, _, node_results in nodes:
             self._views.append((key, len(results), len(node_results), isinstance(g0[key], str)))
-            for prog in node_results:
+            for _, prog in sorted(node_results, key=lambda r: r[0]):     # the quantisers' order; the walk gives evaluation order
                 results.append(_ffi.DfqBatchActResult(len(steps), len(prog)))
                 channels = None                # of the moment vectors of this result
                 for (op, bn, relu, operand, through) in prog:
@@ -741,20 +621,8 @@ class BatchActRangePlan:
         res_arr = (_ffi.DfqBatchActResult * len(results))(*results)
         step_arr = (_ffi.DfqBatchActStep * len(steps))(*steps)
         src_arr = (_ffi.DfqBatchActSource * len(sources))(*sources) if sources else None
-        self._plan = ctypes.c_void_p()
-        _ffi.check(_ffi.lib().dfq_batch_act_plan_create(
-            res_arr, len(results), step_arr, len(steps), src_arr, len(sources),
-            batch.bases.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)), self.n_nets, ctypes.c_float(n_sigma), ctypes.c_float(self.eps),
-            self.block.data_ptr(), 2 * self.n_results, ctypes.byref(self._plan)))
-        self.launches = int(_ffi.lib().dfq_batch_act_plan_launches(self._plan))
-
-    def run(self):
-        """Compute every range of every network, asynchronously on the current stream."""
-        if self._batch.storage is None:
-            raise RuntimeError('NetworkBatch: the batch has been released')
-        if not self._plan:
-            raise RuntimeError('BatchActRangePlan: the plan has been closed')
-        _ffi.check(_ffi.lib().dfq_batch_act_plan_run(self._plan, _ffi.stream_arg()))
+        self._create((res_arr, len(results), step_arr, len(steps), src_arr, len(sources)), ctypes.c_float(n_sigma),
+                     ctypes.c_float(self.eps), self.block.data_ptr(), 2 * self.n_results)
 
     def ranges(self, n):
         """OrderedDict graph key -> float32 [2] view (min, max) of network n's part of the block, in set_quant_minmax's
@@ -788,14 +656,3 @@ class BatchActRangePlan:
                     _rebind(q, 'running_min', rows[first + i, 0:1])
                     _rebind(q, 'running_max', rows[first + i, 1:2])
                     batch._act_bound[id(q)] = (q, self.block)
-
-    def close(self):
-        if self._plan:
-            _ffi.lib().dfq_batch_act_plan_destroy(self._plan)
-            self._plan = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

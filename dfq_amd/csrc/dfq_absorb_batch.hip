@@ -21,7 +21,7 @@
 
 #include <vector>
 
-#include "dfq_common.hpp"
+#include "dfq_batch_shared.hpp"
 
 namespace dfq {
 
@@ -249,12 +249,7 @@ int dfq_batch_absorb_plan_elements(const dfq_batch_absorb_plan* p, int64_t* abso
     return DFQ_OK;
 }
 
-void dfq_batch_absorb_plan_destroy(dfq_batch_absorb_plan* p) {
-    if (!p) return;
-    dfq::dev_quiesce();                                  // nothing in flight may still use the blocks released below
-    p->mem.release();
-    delete p;
-}
+void dfq_batch_absorb_plan_destroy(dfq_batch_absorb_plan* p) { batch_plan_destroy(p); }
 
 int dfq_batch_absorb_plan_create(const dfq_batch_absorb_relation* relations, int32_t n_relations, const dfq_batch_absorb_clip* clips,
                                  int32_t n_clips, const void* const* bases, int32_t n_nets, float n_sigma, float lo, float hi,
@@ -263,9 +258,7 @@ int dfq_batch_absorb_plan_create(const dfq_batch_absorb_relation* relations, int
     if (!out_plan) return fail_arg("%s: no place for the plan", me);
     if (n_relations < 0 || n_clips < 0 || (n_relations > 0 && !relations) || (n_clips > 0 && !clips))
         return fail_arg("%s: a table is null or its count negative", me);
-    if (!bases || n_nets <= 0) return fail_arg("%s: no networks (n_nets %d)", me, (int)n_nets);
-    for (int n = 0; n < n_nets; ++n)
-        if (!bases[n]) return fail_arg("%s: base address of network %d is null", me, n);
+    if (const int rc = batch_check_bases(me, bases, n_nets)) return rc;
     if (n_relations > 0 && !isfinite(n_sigma)) return fail_arg("%s: n_sigma is not finite", me);
     if (n_clips > 0 && !(lo <= hi)) return fail_arg("%s: clip range [%g, %g] is empty or not a number", me, (double)lo, (double)hi);
     if (n_relations > 0 && (!shifts || shift_stride <= 0)) return fail_arg("%s: no block for the shift vectors", me);
@@ -355,8 +348,6 @@ int dfq_batch_absorb_plan_create(const dfq_batch_absorb_relation* relations, int
         clip_only += L.n;
     }
     if (blocks * n_nets > 0x7fffffff) return fail_arg("%s: too much work for one launch", me);
-    std::vector<int64_t> delta(n_nets);
-    for (int n = 0; n < n_nets; ++n) delta[n] = (int64_t)((uintptr_t)bases[n] - (uintptr_t)bases[0]);
 
     dfq_batch_absorb_plan* p = new dfq_batch_absorb_plan();
     AbArgs& a = p->args;
@@ -369,26 +360,16 @@ int dfq_batch_absorb_plan_create(const dfq_batch_absorb_relation* relations, int
     p->shift_blocks = (int)((a.c_stride * n_nets + kBlock - 1) / kBlock);
     p->absorbed_elems = absorbed;
     p->clip_only_elems = clip_only;
-    void *d_layers = nullptr, *d_bl = nullptr, *d_rels = nullptr, *d_cr = nullptr, *d_delta = nullptr;
-    hipError_t e = hipSuccess;
-    auto put = [&](void** d, const void* h, size_t bytes) {
-        if (e != hipSuccess || bytes == 0) return;
-        if ((e = p->mem.alloc(d, bytes)) == hipSuccess) e = hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice);
-    };
-    put(&d_layers, layers.data(), sizeof(AbLayerDev) * layers.size());
-    put(&d_bl, block_layer.data(), sizeof(int32_t) * block_layer.size());
-    put(&d_rels, rels.data(), sizeof(AbRelDev) * rels.size());
-    put(&d_cr, chan_rel.data(), sizeof(int32_t) * chan_rel.size());
-    put(&d_delta, delta.data(), sizeof(int64_t) * delta.size());
-    if (e != hipSuccess) {
-        dfq_batch_absorb_plan_destroy(p);
-        return fail_hip(e, "batch absorb plan allocation", __FILE__, __LINE__);
+    BatchUpload up{p->mem};
+    a.layers = up.put(layers);
+    a.block_layer = up.put(block_layer);
+    a.rels = up.put(rels);
+    a.chan_rel = up.put(chan_rel);
+    a.delta = up.put(batch_delta(bases, n_nets));
+    if (up.err != hipSuccess) {
+        batch_plan_destroy(p);
+        return fail_hip(up.err, "batch absorb plan allocation", __FILE__, __LINE__);
     }
-    a.layers = (const AbLayerDev*)d_layers;
-    a.block_layer = (const int32_t*)d_bl;
-    a.rels = (const AbRelDev*)d_rels;
-    a.chan_rel = (const int32_t*)d_cr;
-    a.delta = (const int64_t*)d_delta;
     *out_plan = p;
     return DFQ_OK;
 }

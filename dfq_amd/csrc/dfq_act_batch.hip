@@ -22,7 +22,7 @@
 #include <vector>
 
 #include "dfq_act_shared.hpp"
-#include "dfq_common.hpp"
+#include "dfq_batch_shared.hpp"
 
 namespace dfq {
 
@@ -195,12 +195,7 @@ extern "C" {
 
 int32_t dfq_batch_act_plan_launches(const dfq_batch_act_plan* p) { return p ? (p->source_blocks > 0) + (p->range_blocks > 0) : 0; }
 
-void dfq_batch_act_plan_destroy(dfq_batch_act_plan* p) {
-    if (!p) return;
-    dfq::dev_quiesce();                                  // nothing in flight may still use the blocks released below
-    p->mem.release();
-    delete p;
-}
+void dfq_batch_act_plan_destroy(dfq_batch_act_plan* p) { batch_plan_destroy(p); }
 
 int dfq_batch_act_plan_create(const dfq_batch_act_result* results, int32_t n_results, const dfq_batch_act_step* steps, int32_t n_steps,
                               const dfq_batch_act_source* sources, int32_t n_sources, const void* const* bases, int32_t n_nets,
@@ -209,9 +204,7 @@ int dfq_batch_act_plan_create(const dfq_batch_act_result* results, int32_t n_res
     if (!out_plan) return fail_arg("%s: no place for the plan", me);
     if (!results || n_results <= 0 || !steps || n_steps <= 0) return fail_arg("%s: the result or the step table is null or empty", me);
     if (n_sources < 0 || (n_sources > 0 && !sources)) return fail_arg("%s: the source table is null or its count negative", me);
-    if (!bases || n_nets <= 0) return fail_arg("%s: no networks (n_nets %d)", me, (int)n_nets);
-    for (int n = 0; n < n_nets; ++n)
-        if (!bases[n]) return fail_arg("%s: base address of network %d is null", me, n);
+    if (const int rc = batch_check_bases(me, bases, n_nets)) return rc;
     if (!isfinite(n_sigma) || !isfinite(eps)) return fail_arg("%s: n_sigma or eps is not finite", me);
     if (!out || out_stride < 2 * (int64_t)n_results) return fail_arg("%s: no block for the ranges, or a stride below 2 * n_results", me);
     if ((int64_t)n_results * n_nets > 0x7fffffff) return fail_arg("%s: too much work for one launch", me);
@@ -292,8 +285,6 @@ int dfq_batch_act_plan_create(const dfq_batch_act_result* results, int32_t n_res
         }
         if (!ok) return fail_arg("%s: result %d: its steps are not CONST, RANGE [CAT | ONE | DIV]... or MOM [ADD | RELU]... MOM_RANGE", me, r);
     }
-    std::vector<int64_t> delta(n_nets);
-    for (int n = 0; n < n_nets; ++n) delta[n] = (int64_t)((uintptr_t)bases[n] - (uintptr_t)bases[0]);
 
     dfq_batch_act_plan* p = new dfq_batch_act_plan();
     ActArgs& a = p->args;
@@ -307,28 +298,17 @@ int dfq_batch_act_plan_create(const dfq_batch_act_result* results, int32_t n_res
     a.src_blocks_pn = (int32_t)src_blocks;
     p->range_blocks = n_results * n_nets;
     p->source_blocks = (int)(src_blocks * n_nets);
-    void *d_res = nullptr, *d_steps = nullptr, *d_srcs = nullptr, *d_bs = nullptr, *d_delta = nullptr, *d_blk = nullptr;
-    hipError_t e = hipSuccess;
-    auto put = [&](void** dst, const void* h, size_t bytes) {
-        if (e != hipSuccess || bytes == 0) return;
-        if ((e = p->mem.alloc(dst, bytes)) == hipSuccess) e = hipMemcpy(*dst, h, bytes, hipMemcpyHostToDevice);
-    };
-    put(&d_res, dres.data(), sizeof(ActResultDev) * dres.size());
-    put(&d_steps, dsteps.data(), sizeof(ActStepDev) * dsteps.size());
-    put(&d_srcs, srcs.data(), sizeof(ActSourceDev) * srcs.size());
-    put(&d_bs, block_source.data(), sizeof(int32_t) * block_source.size());
-    put(&d_delta, delta.data(), sizeof(int64_t) * delta.size());
-    if (e == hipSuccess && src_stride > 0) e = p->mem.alloc(&d_blk, sizeof(float) * (size_t)src_stride * n_nets);
-    if (e != hipSuccess) {
-        dfq_batch_act_plan_destroy(p);
-        return fail_hip(e, "batch activation-range plan allocation", __FILE__, __LINE__);
+    BatchUpload up{p->mem};
+    a.results = up.put(dres);
+    a.steps = up.put(dsteps);
+    a.sources = up.put(srcs);
+    a.block_source = up.put(block_source);
+    a.delta = up.put(batch_delta(bases, n_nets));
+    a.src_block = (float*)up.raw(nullptr, sizeof(float) * (size_t)src_stride * n_nets);
+    if (up.err != hipSuccess) {
+        batch_plan_destroy(p);
+        return fail_hip(up.err, "batch activation-range plan allocation", __FILE__, __LINE__);
     }
-    a.results = (const ActResultDev*)d_res;
-    a.steps = (const ActStepDev*)d_steps;
-    a.sources = (const ActSourceDev*)d_srcs;
-    a.block_source = (const int32_t*)d_bs;
-    a.delta = (const int64_t*)d_delta;
-    a.src_block = (float*)d_blk;
     *out_plan = p;
     return DFQ_OK;
 }

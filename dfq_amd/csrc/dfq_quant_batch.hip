@@ -17,7 +17,7 @@
 // table of network 0's waves (one load; a binary search over the tensors cost a chain of dependent loads per wave).
 #include <vector>
 
-#include "dfq_common.hpp"
+#include "dfq_batch_shared.hpp"
 
 namespace dfq {
 
@@ -271,21 +271,14 @@ int64_t dfq_batch_quant_register_elements(void) { return kRegElems; }
 
 int32_t dfq_batch_quant_plan_launches(const dfq_batch_quant_plan* p) { return p ? p->launches : 0; }
 
-void dfq_batch_quant_plan_destroy(dfq_batch_quant_plan* p) {
-    if (!p) return;
-    dfq::dev_quiesce();                                  // nothing in flight may still use the blocks released below
-    p->mem.release();
-    delete p;
-}
+void dfq_batch_quant_plan_destroy(dfq_batch_quant_plan* p) { batch_plan_destroy(p); }
 
 int dfq_batch_quant_plan_create(const dfq_batch_quant_tensor* tensors, int32_t n_tensors, const void* const* bases, int32_t n_nets,
                                 void* codes, int32_t code_bytes, int64_t code_stride, float* ranges, int64_t range_stride,
                                 dfq_batch_quant_plan** out_plan) {
     const char* me = "dfq_batch_quant_plan_create";
     if (!tensors || n_tensors <= 0 || !out_plan) return fail_arg("%s: no tensors", me);
-    if (!bases || n_nets <= 0) return fail_arg("%s: no networks (n_nets %d)", me, (int)n_nets);
-    for (int n = 0; n < n_nets; ++n)
-        if (!bases[n]) return fail_arg("%s: base address of network %d is null", me, n);
+    if (const int rc = batch_check_bases(me, bases, n_nets)) return rc;
     if (code_stride < 0 || range_stride < 0) return fail_arg("%s: negative stride", me);
     std::vector<BqRowDev> rows;
     std::vector<BqChunkDev> chunks;
@@ -344,8 +337,6 @@ int dfq_batch_quant_plan_create(const dfq_batch_quant_tensor* tensors, int32_t n
     }
     const int64_t row_blocks = (waves * n_nets + kBlock / kWave - 1) / (kBlock / kWave);
     if (row_blocks + nchunks * n_nets > 0x7fffffff) return fail_arg("%s: too much work for one launch", me);
-    std::vector<int64_t> delta(n_nets);
-    for (int n = 0; n < n_nets; ++n) delta[n] = (int64_t)((uintptr_t)bases[n] - (uintptr_t)bases[0]);
 
     dfq_batch_quant_plan* p = new dfq_batch_quant_plan();
     BqArgs& a = p->args;
@@ -360,28 +351,17 @@ int dfq_batch_quant_plan_create(const dfq_batch_quant_tensor* tensors, int32_t n
     a.chunk_blocks = (int32_t)(nchunks * n_nets);
     a.chunk_tensors = (int32_t)chunks.size();
     p->launches = chunks.empty() ? 1 : 2;
-    void *d_rows = nullptr, *d_wt = nullptr, *d_chunks = nullptr, *d_ct = nullptr, *d_delta = nullptr, *d_part = nullptr;
-    hipError_t e = hipSuccess;
-    auto put = [&](void** d, const void* h, size_t bytes) {
-        if (e != hipSuccess || bytes == 0) return;
-        if ((e = p->mem.alloc(d, bytes)) == hipSuccess && h) e = hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice);
-    };
-    put(&d_rows, rows.data(), sizeof(BqRowDev) * rows.size());
-    put(&d_wt, wave_tensor.data(), sizeof(int32_t) * wave_tensor.size());
-    put(&d_chunks, chunks.data(), sizeof(BqChunkDev) * chunks.size());
-    put(&d_ct, chunk_tensor.data(), sizeof(int32_t) * chunk_tensor.size());
-    put(&d_delta, delta.data(), sizeof(int64_t) * delta.size());
-    put(&d_part, nullptr, sizeof(uint32_t) * 2 * (size_t)a.chunk_tensors * n_nets);
-    if (e != hipSuccess) {
-        dfq_batch_quant_plan_destroy(p);
-        return fail_hip(e, "batch quant plan allocation", __FILE__, __LINE__);
+    BatchUpload up{p->mem};
+    a.rows = up.put(rows);
+    a.wave_tensor = up.put(wave_tensor);
+    a.chunks = up.put(chunks);
+    a.chunk_tensor = up.put(chunk_tensor);
+    a.delta = up.put(batch_delta(bases, n_nets));
+    a.slots = (uint32_t*)up.raw(nullptr, sizeof(uint32_t) * 2 * (size_t)a.chunk_tensors * n_nets);
+    if (up.err != hipSuccess) {
+        batch_plan_destroy(p);
+        return fail_hip(up.err, "batch quant plan allocation", __FILE__, __LINE__);
     }
-    a.rows = (const BqRowDev*)d_rows;
-    a.wave_tensor = (const int32_t*)d_wt;
-    a.chunks = (const BqChunkDev*)d_chunks;
-    a.chunk_tensor = (const int32_t*)d_ct;
-    a.delta = (const int64_t*)d_delta;
-    a.slots = (uint32_t*)d_part;
     *out_plan = p;
     return DFQ_OK;
 }

@@ -6,6 +6,10 @@ reference's ``utils/layer_transform.py``:
   find_prev_bn         <- utils/layer_transform.py:299-344   (host graph walk, O(#nodes))
   set_quant_minmax     <- utils/layer_transform.py:347-609   (engine: dfq_bn_ranges, dfq_relu_moments, ...)
 
+The graph walk of set_quant_minmax is ``_act_program``: it compiles a graph into steps, which
+set_quant_minmax executes one launch at a time and ``arena.BatchActRangePlan`` hands to one plan for
+a whole batch.
+
 The graph model is the reference's: ``graph`` maps key -> nn.Module | str (tensor ops are strings whose
 key contains 'add' / 'cat' / ...), ``bottoms`` maps key -> list of input keys | None.
 """
@@ -238,6 +242,125 @@ def find_prev_bn(bn_module, relu_attached, graph, bottoms, bot):
 _RELU_MODE = {'none': 0, 'relu': 1, 'relu6': 2}
 
 
+class _WalkError(AssertionError):
+    """A graph the walk of set_quant_minmax refuses: the reference's assertion text (or the walk's own) and the key of the
+    node it was met at."""
+
+    def __init__(self, key, text):
+        super().__init__(text)
+        self.key = key
+
+
+def _act_program(graph, bottoms, bn_type, targ_type, tensor_ops, is_detection):
+    """The walk of set_quant_minmax (layer_transform.py:347-609) over ONE graph, compiled: [(graph key, one to one, results)]
+    in the order the reference meets the quantised nodes.  A result is (index of the node's quantiser, steps) and stands for
+    one (min, max); the results of a node come in the order the reference evaluates them.  A step is (opcode of _ffi.ACT_*,
+    bn or None, relu mode, operand, case-(d) layer or None) and stands for one launch of the per-network entry points
+    (ACT_CONST and ACT_RANGE_DIV: none).  ``one to one`` marks the nodes of :444-474, whose single-step results the
+    per-network function resolves together at the end.
+
+    Which nodes get results: layers with a ``.quant``, layers of a type in ``targ_type`` (their input range), and the tensor
+    ops in ``tensor_ops = {graph key: number of quantisers}``.  Raises _WalkError where the reference asserts, and for the
+    branches it cannot evaluate (it would trip over a missing moment vector or range there)."""
+    A = _ffi
+    tt = tuple(targ_type)
+    bn_module, relu_attached, nodes = {}, {}, []
+    for key in graph:
+        bot = bottoms[key]
+        if bot is None:
+            continue
+        layer = graph[key]
+        if type(layer) == bn_type:
+            bn_module[key] = layer
+            relu_attached[key] = 'none'
+            continue
+        if type(layer) == torch.nn.ReLU:
+            relu_attached[bot[0]] = 'relu'
+        elif type(layer) == torch.nn.ReLU6:
+            relu_attached[bot[0]] = 'relu6'
+        if isinstance(layer, str):
+            count = tensor_ops.get(key)
+        elif hasattr(layer, 'quant') or type(layer) in tt:
+            count = 1
+        else:
+            count = None
+        if count is None:
+            continue
+        if len(bot) == 1 and bot[0] == 'Data':                     # :443-449 (only the first quantiser of the node is set)
+            lo, hi = (-1.0, 1.0) if is_detection else (-2.11790393, 2.64)   # (x - mean) / std of the data pre-processing
+            nodes.append((key, False, [(0, [(A.ACT_CONST, None, 0, (lo, hi), None)])]))
+            continue
+        try:
+            bn_list, relu_list, connect_list, no_bn = find_prev_bn(bn_module, relu_attached, graph, bottoms, bot[:])
+        except AssertionError as e:
+            raise _WalkError(key, str(e)) from e
+        if count == len(bn_list):                                   # 1 to 1 mapping (:444-474)
+            results = []
+            for (bn, bid), relu in zip(bn_list, relu_list):
+                if bid[0] in no_bn:                                 # case (d): no ReLU clamp in the reference
+                    results.append((len(results), [(A.ACT_RANGE, bn, 0, 0, no_bn[bid[0]])]))
+                else:
+                    results.append((len(results), [(A.ACT_RANGE, bn, _RELU_MODE[relu], 0, None)]))
+            nodes.append((key, True, results))
+            continue
+        # ---- 1 to many / many to many (:476-601) ----
+        branches = {}
+        for ent, relu, ctype in zip(bn_list, relu_list, connect_list):
+            branches.setdefault(ent[1][0], []).append((ent, relu, ctype))
+        compiled = {}
+        for bkey, items in branches.items():
+            def bad(why):
+                return _WalkError(key, 'branch {} {}'.format(bkey, why))
+            items = sorted(items, key=lambda x: len(x[0][1]), reverse=True)
+            (bn, bid), use_relu, connect_type = items.pop(0)
+            depth = len(bid)
+            moments = 'add' in connect_type
+            steps = [(A.ACT_MOM if moments else A.ACT_RANGE, bn, _RELU_MODE[use_relu], 0, None)]
+            while items:
+                bound = 0
+                while bound < len(items) and len(items[bound][0][1]) == depth:
+                    bound += 1
+                if bound == 0:
+                    depth = len(items[0][0][1])                     # cut depth
+                    continue
+                for (bn, bid), relu_t, connect_type in items[:bound]:
+                    if 'add' in connect_type:
+                        if not moments:
+                            raise bad('meets an add after a cat / plain connection')
+                        steps.append((A.ACT_MOM_ADD, bn, _RELU_MODE[relu_t], 0, None))
+                        if 'relu6' in connect_type:
+                            steps.append((A.ACT_MOM_RELU, None, 2, 0, None))
+                        elif 'relu' in connect_type:
+                            steps.append((A.ACT_MOM_RELU, None, 1, 0, None))
+                    elif moments:
+                        raise bad('meets a cat / plain connection after an add')
+                    elif connect_type == 'cat':
+                        steps.append((A.ACT_RANGE_CAT, bn, _RELU_MODE[relu_t], 0, None))
+                    else:   # `if use_relu_tmp` of the reference is always true (a non-empty string): no ReLU mode, clamp at 0
+                        steps.append((A.ACT_RANGE_ONE, bn, 0, 0, None))
+                items = items[bound:]
+                if connect_type == 'one':                           # (of the LAST item, as in the reference)
+                    if moments:
+                        raise bad('meets a cat / plain connection after an add')
+                    steps.append((A.ACT_RANGE_DIV, None, 0, bound + 1, None))
+            if ('add' in connect_type) != moments:
+                raise bad('mixes adds with cat / plain connections')
+            if moments:
+                steps.append((A.ACT_MOM_RANGE, None, 0, 0, None))
+            compiled[bkey] = steps
+        if count == 1 and count < len(bn_list):                     # 1 to many
+            if len(compiled) != 1:
+                raise _WalkError(key, 'Error occurs when setting min/max, should be 1 to many')
+            nodes.append((key, False, [(0, steps)]))
+        elif count < len(bn_list):                                  # many to many
+            if len(compiled) != count or any(str(i) not in compiled for i in range(count)):
+                raise _WalkError(key, 'LENGTH NOT EQUAL {} vs {}'.format(len(compiled), count))
+            nodes.append((key, False, [(int(bkey), steps) for bkey, steps in compiled.items()]))
+        else:
+            raise _WalkError(key, 'Unknown error occured while setting min/max')
+    return nodes
+
+
 class _Moments:
     """(mean, var) channel vectors of one branch, living on the device (layer_transform.py:494-540)."""
 
@@ -247,10 +370,10 @@ class _Moments:
         self.mean = stage.new((n,))
         self.var = stage.new((n,))
 
-    def add_source(self, bn, relu, accumulate):
+    def add_source(self, bn, relu_mode, accumulate):
         lib = _ffi.lib()
         w, b = self.stage.bind(bn.fake_weight), self.stage.bind(bn.fake_bias)
-        _ffi.check(lib.dfq_relu_moments(_ffi.ptr(w), _ffi.ptr(b), self.n, _RELU_MODE[relu], _ffi.ptr(self.mean),
+        _ffi.check(lib.dfq_relu_moments(_ffi.ptr(w), _ffi.ptr(b), self.n, relu_mode, _ffi.ptr(self.mean),
                                         _ffi.ptr(self.var), int(accumulate), _ffi.stream_arg()))
 
     def relu_after_add(self, mode, eps):
@@ -266,16 +389,16 @@ class _Moments:
 
 
 def _bn_ranges(stage, reqs, n_sigma):
-    """[(fake_weight, fake_bias, relu)] -> [(min, max)] with the ReLU clamps: ONE launch, one read-back."""
+    """[(fake_weight, fake_bias, relu mode)] -> [(min, max)] with the ReLU clamps: ONE launch, one read-back."""
     if not reqs:
         return []
     lib = _ffi.lib()
     arr = (_ffi.DfqBnRangeReq * len(reqs))()
     keep = []
-    for i, (fw, fb, relu) in enumerate(reqs):
+    for i, (fw, fb, relu_mode) in enumerate(reqs):
         w, b = stage.bind(fw).reshape(-1), stage.bind(fb).reshape(-1)
         keep.append((w, b))
-        arr[i] = _ffi.DfqBnRangeReq(w.data_ptr(), b.data_ptr(), w.numel(), _RELU_MODE[relu])
+        arr[i] = _ffi.DfqBnRangeReq(w.data_ptr(), b.data_ptr(), w.numel(), relu_mode)
     out = stage.new((len(reqs), 2))
     scratch = stage.new((int(lib.dfq_bn_ranges_scratch_bytes(len(reqs))) // 4 + 1,), dtype=torch.int32)
     _ffi.check(lib.dfq_bn_ranges(arr, len(reqs), float(n_sigma), _ffi.ptr(out), _ffi.ptr(scratch), _ffi.stream_arg()))
@@ -305,117 +428,63 @@ def set_quant_minmax(graph, bottoms, is_detection=False, bn_type=torch.nn.BatchN
     ``tensor_op_quant = {graph key of the op: [QuantMeasure, ...]}``.  Same cases as the reference:
     1 BN -> 1 quantiser (:444-474), 1 quantiser fed by several BNs through add / cat (:476-580), several
     quantisers of one tensor op (:582-601), and a conv / linear without BN in between (case d).
+
+    The walk is ``_act_program``; this function executes its steps, one launch each, except that the
+    1-to-1 results of the whole graph share ONE launch at the end.
     """
     if verbose:
         print("SET QUANT MIN MAX")
+    A = _ffi
     eps = 1e-6
-    bn_module, relu_attached = {}, {}
     stage = _ffi.entry_stage()
-    one_to_one = []          # (quantiser, fake_weight, fake_bias, relu) resolved with one launch at the end
+    op_quant = {k: v for k, v in (tensor_op_quant or {}).items() if v is not None}
+    one_to_one = []          # (quantiser, fake_weight, fake_bias, relu mode) resolved with one launch at the end
+
+    def fill(q, lo, hi):
+        q.running_max.fill_(hi)
+        q.running_min.fill_(lo)
     with torch.no_grad():
-        for key in graph:
-            bot = bottoms[key]
-            if bot is None:
-                continue
-            layer = graph[key]
-            if type(layer) == bn_type:
-                bn_module[key] = layer
-                relu_attached[key] = 'none'
-                continue
-            if type(layer) == torch.nn.ReLU:
-                relu_attached[bot[0]] = 'relu'
-            elif type(layer) == torch.nn.ReLU6:
-                relu_attached[bot[0]] = 'relu6'
-            if isinstance(layer, str):
-                quant_module = (tensor_op_quant or {}).get(key)
-            elif hasattr(layer, 'quant'):
-                quant_module = [layer.quant]
-            else:
-                quant_module = None
-            if len(bot) == 1 and bot[0] == 'Data':
-                if quant_module is None:
-                    continue
-                if is_detection:
-                    quant_module[0].running_max.fill_(1)
-                    quant_module[0].running_min.fill_(-1)
-                else:                                           # (x - mean) / std of the data pre-processing
-                    quant_module[0].running_max.fill_(2.64)
-                    quant_module[0].running_min.fill_(-2.11790393)
-                continue
-            if quant_module is None:
-                continue
-            bn_list, relu_list, connect_list, no_bn = find_prev_bn(bn_module, relu_attached, graph, bottoms, bot[:])
-            if len(quant_module) == len(bn_list):               # 1 to 1 mapping
-                for q, (bn, bid), relu in zip(quant_module, bn_list, relu_list):
-                    if bid[0] in no_bn:                         # case (d): no ReLU clamp in the reference
-                        kind, obj = no_bn[bid[0]]
-                        fb = _through_layer(stage, obj, kind, bn.fake_bias)
-                        fw = _through_layer(stage, obj, kind, bn.fake_weight)
-                        one_to_one.append((q, fw, fb, 'none'))
+        for key, is_one_to_one, results in _act_program(graph, bottoms, bn_type, (), {k: len(v) for k, v in op_quant.items()},
+                                                        is_detection):
+            quant_module = op_quant[key] if isinstance(graph[key], str) else [graph[key].quant]
+            values = {}
+            for idx, steps in results:
+                mom = lo = hi = None
+                for op, bn, relu, operand, through in steps:
+                    if op == A.ACT_CONST:
+                        lo, hi = operand
+                    elif is_one_to_one:
+                        fw, fb = bn.fake_weight, bn.fake_bias
+                        if through is not None:                     # case (d)
+                            kind, obj = through
+                            fb = _through_layer(stage, obj, kind, bn.fake_bias)
+                            fw = _through_layer(stage, obj, kind, bn.fake_weight)
+                        one_to_one.append((quant_module[idx], fw, fb, relu))
+                    elif op == A.ACT_MOM:
+                        mom = _Moments(stage, bn.fake_bias.numel())
+                        mom.add_source(bn, relu, accumulate=False)
+                    elif op == A.ACT_MOM_ADD:
+                        mom.add_source(bn, relu, accumulate=True)
+                    elif op == A.ACT_MOM_RELU:
+                        mom.relu_after_add(relu, eps)
+                    elif op == A.ACT_MOM_RANGE:
+                        lo, hi = mom.value_range(eps, N)
+                    elif op == A.ACT_RANGE_DIV:
+                        lo /= operand
+                        hi /= operand
                     else:
-                        one_to_one.append((q, bn.fake_weight, bn.fake_bias, relu))
-                continue
-            # ---- 1 to many / many to many ----
-            branches = {}
-            for ent, relu, ctype in zip(bn_list, relu_list, connect_list):
-                branches.setdefault(ent[1][0], []).append((ent, relu, ctype))
-            results = {}
-            for bkey, items in branches.items():
-                items = sorted(items, key=lambda x: len(x[0][1]), reverse=True)
-                (bn, bid), use_relu, connect_type = items.pop(0)
-                depth = len(bid)
-                mom = None
-                value_min = value_max = None
-                if 'add' in connect_type:
-                    mom = _Moments(stage, bn.fake_bias.numel())
-                    mom.add_source(bn, use_relu, accumulate=False)
-                else:
-                    (value_min, value_max), = _bn_ranges(stage, [(bn.fake_weight, bn.fake_bias, use_relu)], N)
-                while items:
-                    bound = 0
-                    while bound < len(items) and len(items[bound][0][1]) == depth:
-                        bound += 1
-                    if bound == 0:
-                        depth = len(items[0][0][1])             # cut depth
-                        continue
-                    for (bn, bid), relu_t, connect_type in items[:bound]:
-                        if 'add' in connect_type:
-                            mom.add_source(bn, relu_t, accumulate=True)
-                            if 'relu6' in connect_type:
-                                mom.relu_after_add(2, eps)
-                            elif 'relu' in connect_type:
-                                mom.relu_after_add(1, eps)
-                        elif connect_type == 'cat':
-                            (lo, hi), = _bn_ranges(stage, [(bn.fake_weight, bn.fake_bias, relu_t)], N)
-                            value_min = min(value_min, lo)
-                            value_max = max(value_max, hi)
-                        else:
-                            # `if use_relu_tmp` of the reference is always true (a non-empty string): clamp at 0
-                            (lo, hi), = _bn_ranges(stage, [(bn.fake_weight, bn.fake_bias, 'none')], N)
-                            value_min += max(0., lo)
-                            value_max += hi
-                    items = items[bound:]
-                    if connect_type == 'one':
-                        value_min /= (bound + 1)
-                        value_max /= (bound + 1)
-                if 'add' in connect_type:
-                    results[bkey] = mom.value_range(eps, N)
-                else:
-                    results[bkey] = (value_min, value_max)
-            if len(quant_module) == 1 and len(quant_module) < len(bn_list):     # 1 to many
-                assert len(results) == 1, "Error occurs when setting min/max, should be 1 to many"
-                value_min, value_max = list(results.values())[0]
-                quant_module[0].running_max.fill_(value_max)
-                quant_module[0].running_min.fill_(value_min)
-            elif len(quant_module) < len(bn_list):                              # many to many
-                assert len(results) == len(quant_module), 'LENGTH NOT EQUAL {} vs {}'.format(len(results), len(quant_module))
-                for idx, q in enumerate(quant_module):
-                    value_min, value_max = results[str(idx)]
-                    q.running_max.fill_(value_max)
-                    q.running_min.fill_(value_min)
-            else:
-                assert False, "Unknown error occured while setting min/max"
+                        (r_lo, r_hi), = _bn_ranges(stage, [(bn.fake_weight, bn.fake_bias, relu)], N)
+                        if op == A.ACT_RANGE:
+                            lo, hi = r_lo, r_hi
+                        elif op == A.ACT_RANGE_CAT:
+                            lo, hi = min(lo, r_lo), max(hi, r_hi)
+                        else:                                       # ACT_RANGE_ONE
+                            lo += max(0., r_lo)
+                            hi += r_hi
+                if lo is not None:
+                    values[idx] = (lo, hi)
+            for idx in sorted(values):
+                fill(quant_module[idx], *values[idx])
         ranges = _bn_ranges(stage, [(fw, fb, relu) for (_, fw, fb, relu) in one_to_one], N)
         for (q, _, _, _), (lo, hi) in zip(one_to_one, ranges):
-            q.running_max.fill_(hi)
-            q.running_min.fill_(lo)
+            fill(q, lo, hi)

@@ -21,20 +21,18 @@ Kernel durations and the loop's launch count as the device saw them come from a 
 import argparse
 import contextlib
 import io
-import json
 import os
 import statistics
 import subprocess
 import sys
-import time
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from dfq_amd import _ffi, arena, synthetic                              # noqa: E402
+from dfq_amd import _ffi, arena                                        # noqa: E402
 from dfq_amd.utils import layer_transform as lt                          # noqa: E402
-from dfq_amd.utils import relation as rel                                # noqa: E402
+from batch_bench_common import alternate as _alternate, emit, events as _events, nets as _nets, wall as _wall   # noqa: E402
 from dfq_amd.utils.quantize import QConv2d, QLinear                      # noqa: E402
 
 QTARG = [QConv2d, QLinear]
@@ -55,50 +53,6 @@ def _q_graph(graph, dev):
         if m.bias is not None:
             q.bias.data.copy_(m.bias.data)
         out[k] = q.to(dev)
-    return out
-
-
-def _nets(n, dev):
-    out = []
-    for s in range(n):
-        model, graph, bottoms = synthetic.build('mobilenet_v2', seed=s % 4)
-        model.to(dev)
-        graph = _q_graph(graph, dev)
-        lt.merge_batchnorm(model, graph, bottoms, QTARG)
-        out.append((graph, bottoms, rel.create_relation(graph, bottoms, QTARG, delete_single=False)))
-    return out
-
-
-def _wall(fn):
-    torch.cuda.synchronize()
-    t = time.perf_counter()
-    fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t) * 1e6             # us
-
-
-def _events(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    a.record()
-    fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e3                     # us
-
-
-def _alternate(fns, reps, warmup):
-    """{name: (fn, timer)} -> {name: samples}, the order rotated from repetition to repetition"""
-    names = list(fns)
-    for _ in range(warmup):
-        for k in names:
-            fns[k][0]()
-    torch.cuda.synchronize()
-    out = {k: [] for k in names}
-    for i in range(reps):
-        for k in names[i % len(names):] + names[:i % len(names)]:
-            fn, timer = fns[k]
-            out[k].append(timer(fn))
     return out
 
 
@@ -138,7 +92,7 @@ def _stat(samples):
 
 
 def bench(n, dev, reps, warmup):
-    nets = _nets(n, dev)
+    nets = _nets(n, dev, QTARG, _q_graph)
     batch = arena.NetworkBatch(nets, QTARG)
     le = batch.le_plan()
     le.run()
@@ -196,12 +150,7 @@ def main(argv=None):
         res['commit'] = subprocess.run(['git', '-C', root, 'rev-parse', '--short', 'HEAD'], capture_output=True, text=True).stdout.strip() or None
     except OSError:
         res['commit'] = None
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(args.out) or '.', exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write(line + '\n')
+    emit(res, args.out)
 
 
 if __name__ == '__main__':

@@ -16,7 +16,6 @@ Kernel durations come from a separate `rocprofv3 --kernel-trace --stats -- pytho
 import argparse
 import contextlib
 import io
-import json
 import os
 import statistics
 import sys
@@ -26,48 +25,11 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from dfq_amd import arena, synthetic                                  # noqa: E402
+from dfq_amd import arena                                            # noqa: E402
 from dfq_amd.utils import layer_transform as lt                        # noqa: E402
-from dfq_amd.utils import relation as rel                              # noqa: E402
+from batch_bench_common import ab, emit, nets as _nets               # noqa: E402
 
 TARG = [torch.nn.Conv2d, torch.nn.Linear]
-
-
-def _nets(n, dev):
-    out = []
-    for s in range(n):
-        model, graph, bottoms = synthetic.build('mobilenet_v2', seed=s % 4)
-        model.to(dev)
-        lt.merge_batchnorm(model, graph, bottoms, TARG)
-        out.append((graph, bottoms, rel.create_relation(graph, bottoms, TARG, delete_single=False)))
-    return out
-
-
-def _time(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e3                     # us
-
-
-def ab(name_a, fa, name_b, fb, reps, warmup):
-    for _ in range(warmup):
-        fa()
-        fb()
-    torch.cuda.synchronize()
-    ta, tb = [], []
-    for i in range(reps):
-        if i % 2 == 0:
-            ta.append(_time(fa))
-            tb.append(_time(fb))
-        else:
-            tb.append(_time(fb))
-            ta.append(_time(fa))
-    ma, mb = statistics.median(ta), statistics.median(tb)
-    return {name_a + '_us': ma, name_b + '_us': mb, 'ratio': ma / mb,
-            name_a + '_spread_us': [min(ta), max(ta)], name_b + '_spread_us': [min(tb), max(tb)], 'reps': reps}
 
 
 def main(argv=None):
@@ -78,7 +40,7 @@ def main(argv=None):
     ap.add_argument('--out', default=None)
     args = ap.parse_args(argv)
     dev = torch.device('cuda', 0)
-    nets = _nets(args.batch, dev)
+    nets = _nets(args.batch, dev, TARG)
     batch = arena.NetworkBatch(nets, TARG)
     weights = sum(m.weight.numel() for m in nets[0][0].values() if type(m) in TARG)
     res = {'networks': args.batch, 'weights_per_network': weights}
@@ -121,12 +83,7 @@ def main(argv=None):
     for p in plans.values():
         p.close()
     res['device'] = torch.cuda.get_device_name(0)
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(args.out) or '.', exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write(line + '\n')
+    emit(res, args.out)
 
 
 if __name__ == '__main__':
