@@ -71,6 +71,11 @@ class DfqBatchAbsorbClip(Structure):
     _fields_ = [('data', c_void_p), ('n', c_int64)]
 
 
+class DfqBatchFoldPair(Structure):
+    _fields_ = [('w', c_void_p), ('b', c_void_p), ('gamma', c_void_p), ('beta', c_void_p), ('mean', c_void_p), ('var', c_void_p),
+                ('fake_weight', c_void_p), ('fake_bias', c_void_p), ('row_len', c_int64), ('out_ch', c_int32), ('eps', c_float)]
+
+
 class DfqBatchActResult(Structure):
     _fields_ = [('step_begin', c_int32), ('step_count', c_int32)]
 
@@ -191,6 +196,11 @@ SIGNATURES = {
     'dfq_batch_absorb_plan_run': (c_int32, [c_void_p, c_void_p]),
     'dfq_batch_absorb_plan_launches': (c_int32, [c_void_p]),
     'dfq_batch_absorb_plan_elements': (c_int32, [c_void_p, POINTER(c_int64), POINTER(c_int64)]),
+    'dfq_batch_fold_plan_create': (c_int32, [POINTER(DfqBatchFoldPair), c_int32, POINTER(c_void_p), c_int32, POINTER(c_void_p)]),
+    'dfq_batch_fold_plan_run': (c_int32, [c_void_p, c_void_p]),
+    'dfq_batch_fold_plan_destroy': (None, [c_void_p]),
+    'dfq_batch_fold_plan_launches': (c_int32, [c_void_p]),
+    'dfq_batch_fold_plan_elements': (c_int64, [c_void_p]),
     'dfq_batch_act_plan_create': (c_int32, [POINTER(DfqBatchActResult), c_int32, POINTER(DfqBatchActStep), c_int32,
                                             POINTER(DfqBatchActSource), c_int32, POINTER(c_void_p), c_int32, c_float, c_float,
                                             c_void_p, c_int64, POINTER(c_void_p)]),

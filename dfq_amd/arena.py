@@ -23,7 +23,11 @@ activation ranges: the graph walk both share (``utils.layer_transform._act_progr
 is made once, on network 0, and one launch (two with a conv / linear without BatchNorm in front of a quantiser) fills one
 block of packed (min, max) pairs the quantisers are then pointed at (tests/test_batch_act.py).  With them the default
 calibration sequence main_cls.py:149-190 runs on a batch as le_plan -> absorb_plan -> bc_plan -> quant_plan ->
-act_range_plan.
+act_range_plan.  ``NetworkBatch.from_unfolded`` takes the networks as they are loaded, BatchNorm not yet folded, and
+``fold_plan`` is the batch form of ``merge_batchnorm`` (layer_transform.py:231-276, main_cls.py:149): the pairs are found
+once, on network 0, by the walk merge_batchnorm itself uses (``utils.layer_transform._fold_pairs``), the BatchNorm vectors get
+slots behind those of the ordinary layout, and two launches fold every network (tests/test_batch_fold.py).  The sequence then
+starts with fold_plan: fold_plan -> le_plan -> absorb_plan -> bc_plan -> quant_plan -> act_range_plan.
 """
 from __future__ import annotations
 
@@ -36,9 +40,10 @@ import torch
 
 from . import _ffi
 from . import dfq as _dfq
-from .utils.layer_transform import _WalkError, _act_program, _ensure_bias
+from .utils.layer_transform import _WalkError, _act_program, _ensure_bias, _fold_pairs
 
 _ALIGN = 64            # floats: every tensor starts on a 256-byte boundary (vector loads, the alignment hipMalloc gives)
+_BN_VECTORS = ('weight', 'bias', 'running_mean', 'running_var')      # of a BatchNorm that fold_plan folds
 
 
 def _rebind(mod, name, view):
@@ -55,9 +60,80 @@ def _rebind(mod, name, view):
 class NetworkBatch:
     """``nets``: list of (graph, bottoms, relations) of networks with the same graph (keys, node types, tensor shapes,
     relation triples), BatchNorm already folded (``merge_batchnorm``) and relations created, tensors float32 on the target
-    device.  After construction every tensor the equalisation and the bias correction touch lives in ``self.storage``."""
+    device.  After construction every tensor the equalisation and the bias correction touch lives in ``self.storage``.
+    ``NetworkBatch.from_unfolded`` takes networks whose BatchNorm is still to be folded; ``self.folded`` says which state
+    the batch is in, ``self.offsets`` where every slot lies."""
 
     def __init__(self, nets, targ_type, bn_type=torch.nn.BatchNorm2d, stage=None):
+        self._layout(nets, targ_type, bn_type, stage, None)
+
+    @classmethod
+    def from_unfolded(cls, nets, targ_type, bn_type=torch.nn.BatchNorm2d, stage=None):
+        """A batch of networks whose BatchNorm has NOT been folded yet: ``nets`` as for the constructor, the relations created
+        on the unfolded graph (``create_relation`` reads no tensor).  The (layer, BatchNorm) pairs ``merge_batchnorm`` would
+        fold are found on network 0 (``_fold_pairs``); every folded layer gets its bias, every folded BatchNorm its
+        ``fake_weight`` / ``fake_bias`` buffers (contents irrelevant until the fold), the ordinary layout is made, and the
+        BatchNorm vectors get slots behind it.  The batch is ``folded == False`` until ``fold_plan().run()`` /
+        ``merge_batchnorm()``; the other plans raise RuntimeError until then.  ValueError, before anything is touched and
+        naming the graph key: a BatchNorm that already has proxies (it has been folded: use the constructor), one without
+        running statistics or affine parameters, a layer two BatchNorms claim, networks whose pairs or ``eps`` differ from
+        network 0's, a tensor of a pair that is not float32 on the batch's device."""
+        nets = list(nets)
+        if not nets:
+            raise ValueError('NetworkBatch: no networks')
+        stage = stage or _ffi.Stage()
+        dev = stage.device
+        who = 'NetworkBatch.from_unfolded'
+        g0, b0, _ = nets[0]
+        pairs = _fold_pairs(g0, b0, targ_type)
+        claimed = {}
+        for lk, bk in pairs:
+            if lk in claimed:
+                raise ValueError('{}: layer {} is claimed by two BatchNorms ({} and {}): one launch cannot order two folds of '
+                                 'one weight'.format(who, lk, claimed[lk], bk))
+            claimed[lk] = bk
+        eps0 = [g0[bk].eps for _, bk in pairs]
+        for n, (graph, bottoms, _) in enumerate(nets):
+            mine = _fold_pairs(graph, bottoms, targ_type) if n else pairs
+            if mine != pairs:
+                odd = next((q for q in mine if q not in pairs), None) or next(q for q in pairs if q not in mine)
+                raise ValueError('{}: network {} does not fold the pairs of network 0 (BatchNorm {} behind layer {})'.format(
+                    who, n, odd[1], odd[0]))
+            for (lk, bk), eps in zip(pairs, eps0):
+                layer, bn = graph[lk], graph[bk]
+                if _dfq._attr(bn, 'fake_weight') is not None or _dfq._attr(bn, 'fake_bias') is not None:
+                    raise ValueError('{}: BatchNorm {} of network {} already has fake_weight / fake_bias: it has been folded '
+                                     '(use the constructor)'.format(who, bk, n))
+                if bn.eps != eps:
+                    raise ValueError('{}: BatchNorm {} of network {} has eps {!r}, network 0 has {!r}'.format(who, bk, n, bn.eps, eps))
+                tensors = [(lk, 'weight', layer.weight), (lk, 'bias', layer.bias)]
+                for name in _BN_VECTORS:
+                    t = _dfq._attr(bn, name)
+                    if t is None:
+                        raise ValueError('{}: BatchNorm {} of network {} has no {} (a folded BatchNorm needs running statistics '
+                                         'and affine parameters)'.format(who, bk, n, name))
+                    if t.numel() != layer.weight.shape[0]:
+                        raise ValueError('{}: {} of BatchNorm {} of network {} has {} channels, layer {} has {}'.format(
+                            who, name, bk, n, t.numel(), lk, layer.weight.shape[0]))
+                    tensors.append((bk, name, t))
+                for key, name, t in tensors:
+                    if t is not None and (t.dtype is not torch.float32 or t.device != dev):
+                        raise ValueError('{}: {} of {} of network {} is {} on {}; the batch wants float32 on {}'.format(
+                            who, name, key, n, t.dtype, t.device, dev))
+        for graph, _, _ in nets:
+            for lk, bk in pairs:
+                _ensure_bias(graph[lk])                                 # layer_transform.py:253-254
+                bn = graph[bk]
+                c = bn.weight.numel()
+                bn.register_buffer('fake_weight', torch.empty(c, dtype=torch.float32, device=dev))     # :264-265; filled by the fold
+                bn.register_buffer('fake_bias', torch.empty(c, dtype=torch.float32, device=dev))
+        self = cls.__new__(cls)
+        self._layout(nets, targ_type, bn_type, stage, pairs)
+        return self
+
+    def _layout(self, nets, targ_type, bn_type, stage, fold):
+        """what the constructor does; ``fold``: the (layer key, BatchNorm key) pairs of a batch that is still to be folded,
+        whose BatchNorm vectors (and proxies no table refers to) get slots BEHIND the ordinary ones"""
         if not nets:
             raise ValueError('NetworkBatch: no networks')
         self.stage = stage or _ffi.Stage()
@@ -108,7 +184,19 @@ class NetworkBatch:
                 out.append((rr, 'S', rr.S if rr.S is not None else o1))
             return out
 
+        def fold_slots_of(graph):
+            """the slots of an unfolded batch behind the ordinary ones: the four vectors of every folded BatchNorm and those
+            of its proxies that no LE / BC table refers to"""
+            out = []
+            for _, bk in fold or ():
+                bn = graph[bk]
+                for name in _BN_VECTORS + tuple(nm for nm in ('fake_weight', 'fake_bias') if (bk, nm) not in seen):
+                    out.append((bn, name, _dfq._attr(bn, name)))
+            return out
+
         per_net = [slots_of(*net) for net in self.nets]
+        n_ordinary = len(per_net[0])
+        per_net = [slots + fold_slots_of(net[0]) for slots, net in zip(per_net, self.nets)]
         numel = [t.numel() if torch.is_tensor(t) else int(t) for (_, _, t) in per_net[0]]
         for n, slots in enumerate(per_net):
             if [t.numel() if torch.is_tensor(t) else int(t) for (_, _, t) in slots] != numel:
@@ -122,6 +210,7 @@ class NetworkBatch:
             offs.append(total)
             total += -(-c // _ALIGN) * _ALIGN
         self.stride = total                                            # floats per network
+        self.offsets = offs                                            # of every slot, floats from a network's base
         self.storage = torch.empty(len(self.nets) * total, dtype=torch.float32, device=dev)
         rows = self.storage.view(len(self.nets), total)
         srcs, dsts = [], []
@@ -160,8 +249,10 @@ class NetworkBatch:
         self._base_ints = [int(v) for v in self.bases]
         self._scale_cum = [rr.S for (_, _, rels) in self.nets for rr in rels]
         # first weight, last relation of every network (None: a network without relations, ReLU6 kept, has no scale vectors)
-        self._probe = [(slots[0][2], slots[-1][0] if r0 else None) for slots in per_net]
+        self._probe = [(slots[0][2], slots[n_ordinary - 1][0] if r0 else None) for slots in per_net]
         self._act_bound = {}                  # id -> (quantiser module, range block) of every BatchActRangePlan.bind_quantisers
+        self._fold = fold                     # None: the networks came folded
+        self.folded = not fold                # False until fold_plan().run(): the proxies hold nothing yet
 
     def release(self):
         """Give every tensor a storage of its own again (a copy of its slot) and drop the batch allocation.  The models' tensors
@@ -246,16 +337,46 @@ class NetworkBatch:
                                 if not np.array_equal(a[field], want):
                                     raise RuntimeError('NetworkBatch: {} of network {} is not where the batch put it'.format(field, n))
 
+    def _ready(self, who):
+        """check(), and RuntimeError for a batch from_unfolded made that has not been folded yet"""
+        self.check()
+        if not self.folded:
+            raise RuntimeError('NetworkBatch: {} on a batch whose BatchNorm has not been folded yet (fold_plan().run() or '
+                               'merge_batchnorm() first)'.format(who))
+
+    def fold_plan(self):
+        """One plan (BatchFoldPlan) for ``merge_batchnorm(model, graph, bottoms, targ_type)`` on every network of a batch
+        made by ``from_unfolded``, bit for bit: two launches.  RuntimeError on a batch made by the constructor (its networks
+        came folded) and for a tensor of network 0 that has left its slot.  The plan runs once: ``run()`` sets
+        ``self.folded`` and raises RuntimeError on a folded batch."""
+        self.check()
+        if self._fold is None:
+            raise RuntimeError('NetworkBatch: fold_plan on a batch of folded networks (NetworkBatch.from_unfolded takes unfolded ones)')
+        return BatchFoldPlan(self)
+
+    def merge_batchnorm(self):
+        """fold_plan + run + synchronise + close, then ``eps = 1e-12`` on every folded BatchNorm (what merge_batchnorm sets,
+        utils/layer_transform.py): afterwards every network is in the state ``merge_batchnorm`` leaves it in."""
+        plan = self.fold_plan()
+        try:
+            plan.run()
+            _ffi.synchronize()
+        finally:
+            plan.close()
+        for graph, _, _ in self.nets:
+            for _, bk in self._fold:
+                graph[bk].eps = 1e-12
+
     def le_plan(self):
         """One equalisation plan over the whole batch (LEPlan): the first network's tables + a base address per network."""
-        self.check()
+        self._ready('le_plan')
         t = self._tables(self._le)
         t.n_relations, t.scale_cum = self._le.n_relations, self._scale_cum
         return _dfq.LEPlan(t, None, stage=self.stage)
 
     def bc_plan(self):
         """One bias-correction plan over the whole batch (BCPlan)."""
-        self.check()
+        self._ready('bc_plan')
         t = self._tables(self._bc)
         t.n_steps, t.n_sources = self._bc.n_steps, self._bc.n_sources
         t.step_out_ch, t.step_in = self._bc.step_out_ch, self._bc.step_in
@@ -272,7 +393,7 @@ class NetworkBatch:
         inside the library (a per-tensor width outside [1, 30]) this raises ValueError up front.  Every tensor of network 0
         must still lie in its slot of the batch allocation (RuntimeError otherwise: the plan writes every network at network
         0's addresses moved by a fixed offset)."""
-        self.check()
+        self._ready('quant_plan')
         return BatchQuantPlan(self, bit_weight, bits_bias, per_channel, signed, codes)
 
     def quantize(self, bit_weight=8, bits_bias=16, per_channel=False, signed=False, codes='int32'):
@@ -294,7 +415,7 @@ class NetworkBatch:
         bias_absorption skips them (the walk is made on network 0).  ValueError for an ``N`` that is not a finite number, a
         ``range_clip`` that is not a pair lo <= hi, and a second layer of an absorbed relation whose bias has no slot in the
         batch allocation; RuntimeError for a tensor of network 0 that has left its slot."""
-        self.check()
+        self._ready('absorb_plan')
         return BatchAbsorbPlan(self, N, range_clip, absorb)
 
     def absorb(self, N=3, range_clip=None, absorb=True):
@@ -315,7 +436,7 @@ class NetworkBatch:
         function.  ValueError for an ``N`` that is not a finite number, an unknown key or a non-positive count in
         ``tensor_ops``, a BatchNorm without proxies, and a graph set_quant_minmax itself would refuse; RuntimeError for a
         tensor of network 0 that has left its slot."""
-        self.check()
+        self._ready('act_range_plan')
         return BatchActRangePlan(self, is_detection, N, tensor_ops)
 
     def set_quant_minmax(self, is_detection=False, N=6, tensor_op_quant=None):
@@ -473,6 +594,45 @@ class BatchQuantPlan(_BatchPlan):
         """{graph key: float32 [O, 2] (per channel) or [2]} of network n's weights, {key + '.bias': [2]} of its biases"""
         row = self.range_block[n]
         return {key: row[off:off + 2 * (shape[0] if len(shape) == 2 else 1)].view(shape) for (key, off, shape) in self._range_views}
+
+
+class BatchFoldPlan(_BatchPlan):
+    """BatchNorm folding of every network of a NetworkBatch made by ``from_unfolded`` (dfq_batch_fold_plan,
+    include/dfq_hip.h): network 0's (layer, BatchNorm) pair table plus the batch's base addresses.  ``run()`` enqueues two
+    launches on the current stream -- the weights, then the per-channel vectors -- and marks the batch folded; weights,
+    biases, the proxies and the BatchNorm vectors change in place.  ``bn.eps`` is read here, when the plan is made, and left
+    alone (``NetworkBatch.merge_batchnorm`` sets it)."""
+    _c = 'dfq_batch_fold_plan'
+
+    def __init__(self, batch):
+        super().__init__(batch)
+        g0 = batch.nets[0][0]
+
+        def at(key, name):
+            t = _dfq._attr(g0[key], name)
+            if t is None:
+                raise RuntimeError('NetworkBatch: {} of {} in network 0 no longer lives in its slot of the batch allocation'.format(
+                    name, key))
+            return batch._in_slot(key, name, t)
+        entries = []
+        for lk, bk in batch._fold:
+            w = g0[lk].weight
+            entries.append(_ffi.DfqBatchFoldPair(at(lk, 'weight'), at(lk, 'bias'), *[at(bk, name) for name in _BN_VECTORS],
+                                                 at(bk, 'fake_weight'), at(bk, 'fake_bias'), w[0].numel(), int(w.shape[0]),
+                                                 float(g0[bk].eps)))
+        if not entries:
+            raise ValueError('fold_plan: no BatchNorm of the batch follows a {} layer'.format(tuple(batch.targ_type)))
+        self.n_nets, self.n_pairs = len(batch.nets), len(entries)
+        self._create(((_ffi.DfqBatchFoldPair * len(entries))(*entries), len(entries)))
+        self.elements = int(_ffi.lib().dfq_batch_fold_plan_elements(self._plan))      # folded weights per network
+
+    def run(self):
+        batch = self._batch
+        if batch.storage is not None and self._plan and batch.folded:
+            raise RuntimeError('BatchFoldPlan: the batch is folded already (a second fold would take the identity BatchNorms '
+                               'for the real ones and overwrite the proxies with 1 and 0)')
+        super().run()
+        batch.folded = True
 
 
 class BatchAbsorbPlan(_BatchPlan):

@@ -1,7 +1,8 @@
 """Graph-level passes around the equalisation/correction core, with the call surface of the
 reference's ``utils/layer_transform.py``:
 
-  merge_batchnorm      <- utils/layer_transform.py:231-276   (engine: dfq_fold_batchnorm)
+  merge_batchnorm      <- utils/layer_transform.py:231-276   (engine: dfq_fold_batchnorm; its graph walk is
+                                                              ``_fold_pairs``, which ``arena.NetworkBatch.from_unfolded`` shares)
   quantize_targ_layer  <- utils/layer_transform.py:279-296   (engine: dfq_quant_plan_*)
   find_prev_bn         <- utils/layer_transform.py:299-344   (host graph walk, O(#nodes))
   set_quant_minmax     <- utils/layer_transform.py:347-609   (engine: dfq_bn_ranges, dfq_relu_moments, ...)
@@ -38,6 +39,25 @@ def _ensure_bias(layer):
     return layer.bias
 
 
+def _fold_pairs(graph, bottoms, targ_type):
+    """[(layer key, BatchNorm key)] of the pairs merge_batchnorm folds, in graph order (layer_transform.py:239-244, :274): a
+    node of exact type nn.BatchNorm2d with a ``targ_type`` layer among its bottoms; the first such bottom wins.  Structural:
+    no tensor is read and nothing is changed.  ``merge_batchnorm`` and ``arena.NetworkBatch.from_unfolded`` share it."""
+    pairs = []
+    for key in graph:
+        bots = bottoms[key]
+        if bots is None:
+            continue
+        if type(graph[key]) != nn.BatchNorm2d:
+            continue
+        for bk in bots:
+            if type(graph[bk]) not in targ_type:
+                continue
+            pairs.append((bk, key))
+            break
+    return pairs
+
+
 def merge_batchnorm(model, graph, bottoms, targ_type=[QConv2d]):
     """Fold every BatchNorm2d that directly follows a targ layer into that layer.
 
@@ -49,20 +69,9 @@ def merge_batchnorm(model, graph, bottoms, targ_type=[QConv2d]):
     with torch.no_grad():
         stage = _ffi.entry_stage()
         pairs = []
-        for key in graph:
-            bots = bottoms[key]
-            if bots is None:
-                continue
-            bn = graph[key]
-            if type(bn) != nn.BatchNorm2d:
-                continue
-            for bk in bots:
-                layer = graph[bk]
-                if type(layer) not in targ_type:
-                    continue
-                _ensure_bias(layer)
-                pairs.append((layer, bn))
-                break
+        for lk, bk in _fold_pairs(graph, bottoms, targ_type):
+            _ensure_bias(graph[lk])
+            pairs.append((graph[lk], graph[bk]))
         # a model that lives on the host crosses PCIe once each way: every tensor of every pair in one packed copy, the new
         # per-channel vectors of all BatchNorms in one flat buffer that comes back in one copy
         stage.prefetch([t for layer, bn in pairs for t in (layer.weight, layer.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)])

@@ -456,6 +456,44 @@ int32_t dfq_batch_absorb_plan_launches(const dfq_batch_absorb_plan* plan);
 /* weights per network that are read for a row sum, and weights that are only clipped (either pointer may be null) */
 int dfq_batch_absorb_plan_elements(const dfq_batch_absorb_plan* plan, int64_t* absorbed, int64_t* clip_only);
 
+/* BatchNorm folding of a whole batch of networks of one architecture (extension; merge_batchnorm,
+ * utils/layer_transform.py:246-272, main_cls.py:149, for every network of a batch at once).  `pairs` lists the (layer,
+ * BatchNorm) pairs of the FIRST of `n_nets` networks; network n's copy of a tensor lies bases[n] - bases[0] bytes further.
+ * One run does for each pair, in every network, what dfq_fold_batchnorm does (utils/layer_transform.py:246-272):
+ *   sd = sqrtf(var + eps);  k = gamma / sd;  w[o, :] *= k[o];  b = b * k + (beta - (gamma * mean) / sd);
+ *   fake_weight = |gamma|;  fake_bias = beta;  gamma = var = 1;  beta = mean = 0
+ * every operation rounded on its own, in that order: bit-identical to dfq_fold_batchnorm on that network alone.  Two
+ * launches: one pass over the weights that only reads gamma / var (flat pieces of a tensor, 16-byte accesses, any row
+ * length), then a thread per channel; no atomics, no workgroup waits for another.  create: DFQ_ERR_ARG (and dfq_last_error)
+ * for a null or empty table, a null tensor, out_ch <= 0 or row_len <= 0, a weight that is not 16-byte aligned, two pairs
+ * sharing a weight, a bias or a BatchNorm vector, null bases, networks that are not 16-byte aligned to network 0.  Every
+ * tensor of network 0 must lie inside network 0's slot: nothing here can check that.  A second run folds the identity
+ * BatchNorms the first one left (the proxies become 1 and 0): the caller runs a plan once.  Synchronises (create only); run
+ * is asynchronous on `stream`. */
+typedef struct dfq_batch_fold_plan dfq_batch_fold_plan;
+typedef struct dfq_batch_fold_pair { /* addresses in network 0 */
+    float* w;               /* the layer's weight [out_ch, row_len], scaled in place (layer_transform.py:246-251)   */
+    float* b;               /* its bias [out_ch] (:253-261)                                                        */
+    float* gamma;           /* bn.weight [out_ch]; 1 afterwards (:268)                                             */
+    float* beta;            /* bn.bias; 0 afterwards (:270)                                                        */
+    float* mean;            /* bn.running_mean; 0 afterwards (:271)                                                */
+    float* var;             /* bn.running_var; 1 afterwards (:269)                                                 */
+    float* fake_weight;     /* |gamma| (:264)                                                                      */
+    float* fake_bias;       /* beta (:265)                                                                         */
+    int64_t row_len;
+    int32_t out_ch;
+    float eps;              /* bn.eps (:249)                                                                       */
+} dfq_batch_fold_pair;
+
+int dfq_batch_fold_plan_create(const dfq_batch_fold_pair* pairs, int32_t n_pairs, const void* const* bases, int32_t n_nets,
+                               dfq_batch_fold_plan** out_plan);
+int dfq_batch_fold_plan_run(dfq_batch_fold_plan* plan, void* stream);
+void dfq_batch_fold_plan_destroy(dfq_batch_fold_plan* plan);
+/* launches per run (2) */
+int32_t dfq_batch_fold_plan_launches(const dfq_batch_fold_plan* plan);
+/* folded weights per network (each is read once and written once: 8 B) */
+int64_t dfq_batch_fold_plan_elements(const dfq_batch_fold_plan* plan);
+
 /* Analytic activation ranges of a whole batch of networks of one architecture (extension; set_quant_minmax,
  * utils/layer_transform.py:347-609, main_cls.py:188, for every network of a batch at once).  The caller walks the graph of
  * the FIRST network once (find_prev_bn, :299-344, and the branch grouping of :476-580) and hands over what the walk found
