@@ -76,6 +76,10 @@ class DfqBatchFoldPair(Structure):
                 ('fake_weight', c_void_p), ('fake_bias', c_void_p), ('row_len', c_int64), ('out_ch', c_int32), ('eps', c_float)]
 
 
+class DfqBatchTableTensor(Structure):
+    _fields_ = [('data', c_void_p), ('rows', c_int64), ('row_len', c_int64), ('range_offset', c_int64), ('row_offset', c_int64)]
+
+
 class DfqBatchActResult(Structure):
     _fields_ = [('step_begin', c_int32), ('step_count', c_int32)]
 
@@ -201,6 +205,11 @@ SIGNATURES = {
     'dfq_batch_fold_plan_destroy': (None, [c_void_p]),
     'dfq_batch_fold_plan_launches': (c_int32, [c_void_p]),
     'dfq_batch_fold_plan_elements': (c_int64, [c_void_p]),
+    'dfq_batch_table_plan_create': (c_int32, [POINTER(DfqBatchTableTensor), c_int32, POINTER(c_void_p), c_int32, c_void_p, c_int64,
+                                              POINTER(c_void_p)]),
+    'dfq_batch_table_plan_run': (c_int32, [c_void_p, c_void_p]),
+    'dfq_batch_table_plan_destroy': (None, [c_void_p]),
+    'dfq_batch_table_plan_launches': (c_int32, [c_void_p]),
     'dfq_batch_act_plan_create': (c_int32, [POINTER(DfqBatchActResult), c_int32, POINTER(DfqBatchActStep), c_int32,
                                             POINTER(DfqBatchActSource), c_int32, POINTER(c_void_p), c_int32, c_float, c_float,
                                             c_void_p, c_int64, POINTER(c_void_p)]),

@@ -28,6 +28,12 @@ act_range_plan.  ``NetworkBatch.from_unfolded`` takes the networks as they are l
 once, on network 0, by the walk merge_batchnorm itself uses (``utils.layer_transform._fold_pairs``), the BatchNorm vectors get
 slots behind those of the ordinary layout, and two launches fold every network (tests/test_batch_fold.py).  The sequence then
 starts with fold_plan: fold_plan -> le_plan -> absorb_plan -> bc_plan -> quant_plan -> act_range_plan.
+``table_plan`` is the batch form of the last step of the reference's OTHER driver, convert_ncnn.py:106-201, whose product is
+the int8 calibration table ncnn2int8 takes (``ncnn_table``; convert_ncnn.py:178-201): one read of every weight of every
+network gives each tensor's (min, max) and each output row's max|w|, and ``calibration_tables`` formats them, with the
+activation ranges, into one table per network (tests/test_batch_table.py).  That driver then runs on a batch as
+fold_plan -> le_plan().run(signed=True) -> absorb_plan(absorb=False, range_clip=...) -> bc_plan().run(signed=True) ->
+act_range_plan -> calibration_tables.
 """
 from __future__ import annotations
 
@@ -40,6 +46,7 @@ import torch
 
 from . import _ffi
 from . import dfq as _dfq
+from . import ncnn_table as _ncnn
 from .utils.layer_transform import _WalkError, _act_program, _ensure_bias, _fold_pairs
 
 _ALIGN = 64            # floats: every tensor starts on a 256-byte boundary (vector loads, the alignment hipMalloc gives)
@@ -463,6 +470,107 @@ class NetworkBatch:
             plan.close()
         return plan
 
+    def table_plan(self):
+        """One plan (BatchTablePlan) for the weight statistics of the ncnn int8 calibration table (``ncnn_table``,
+        convert_ncnn.py:178-201) of every network of the batch: ``run()`` reads every ``targ_type`` weight once, writes none,
+        and fills one block with each tensor's (min, max) -- ``ncnn_table.weight_ranges`` -- and each output row's max|w| --
+        ``prims.row_range(w, signed=True)`` -- exactly.  RuntimeError for a weight of network 0 that has left its slot."""
+        self._ready('table_plan')
+        return BatchTablePlan(self)
+
+    def calibration_tables(self, act=None, names=None, per_channel=False):
+        """The lines of ``model_int8_tensor.table`` of every network: a list with one list of lines per network, each equal,
+        string for string, to ``ncnn_table.calibration_table(graph, targ_type, names, per_channel)`` on that network alone.
+        table_plan + run + synchronise + ONE device-to-host copy of the block + close.  ``act``: a BatchActRangePlan of this
+        batch that has run, open or closed (what ``set_quant_minmax()`` returns): the activation range of layer k is the one
+        that plan holds for key k, read with one more copy.  ``act=None``: the quantisers ``graph[k].quant`` of every network
+        are read as the single-network function reads them (min of ``running_min``, max of ``running_max``), gathered on the
+        device into one tensor first.  ``names``: one list for the whole batch, the weight block's names first, then the
+        activation block's (2 x layers of them, ValueError otherwise); None: the graph keys.  ZeroDivisionError, naming
+        network, key and row, where the single-network function raises it: an all-zero tensor, or row with ``per_channel``,
+        or an activation range of zeros."""
+        self._ready('calibration_tables')
+        keys = self._table_keys()
+        if names is None:
+            names = ['{}_param_0'.format(k) for k in keys] + [str(k) for k in keys]
+        names = list(names)
+        if len(names) != 2 * len(keys):
+            raise ValueError('calibration_tables: need one name per layer for the weight block and one for the activation block '
+                             '({}), got {}'.format(2 * len(keys), len(names)))
+        return self._format_tables(names, per_channel, *self._table_statistics(act))
+
+    def _table_keys(self):
+        g0, tt = self.nets[0][0], tuple(self.targ_type)
+        return [k for k in g0 if type(g0[k]) in tt]
+
+    def _table_statistics(self, act):
+        """the device side of ``calibration_tables``: (the table plan's views, its block as nested lists of Python floats, the
+        (min, max) of every layer's activation range per network); two blocking copies"""
+        keys, n_nets = self._table_keys(), len(self.nets)
+        if act is not None:
+            if not isinstance(act, BatchActRangePlan) or act._batch is not self:
+                raise ValueError('calibration_tables: act is not an act_range_plan of this batch')
+            at = {key: first for (key, first, _, is_op) in act._views if not is_op}
+            missing = [k for k in keys if k not in at]
+            if missing:
+                raise ValueError('calibration_tables: the act_range_plan holds no range for {}'.format(missing[0]))
+        else:
+            mins, maxs = [], []
+            for n, (graph, _, _) in enumerate(self.nets):
+                for k in keys:
+                    q = getattr(graph[k], 'quant', None)
+                    if q is None:
+                        raise AttributeError('calibration_tables: {} of network {} has no quantiser (.quant); pass act= an '
+                                             'act_range_plan'.format(k, n))
+                    lo, hi = q.running_min, q.running_max
+                    mins.append(lo.reshape(1) if lo.numel() == 1 else torch.min(lo).reshape(1))
+                    maxs.append(hi.reshape(1) if hi.numel() == 1 else torch.max(hi).reshape(1))
+        plan = self.table_plan()
+        try:
+            plan.run()
+            _ffi.synchronize()
+            block = plan.block.cpu().tolist()                          # Python floats: str() gives the reference's digits
+        finally:
+            plan.close()
+        if act is not None:
+            pairs = act.block.cpu().tolist()
+            act_of = [[tuple(pairs[n][at[k]]) for k in keys] for n in range(n_nets)]
+        else:
+            both = torch.stack([torch.cat(mins), torch.cat(maxs)]).cpu().tolist()       # gathered on the device: one copy
+            act_of = [[(both[0][n * len(keys) + i], both[1][n * len(keys) + i]) for i in range(len(keys))] for n in range(n_nets)]
+        return plan._views, block, act_of
+
+    def _format_tables(self, names, per_channel, views, block, act_of):
+        """the host side of ``calibration_tables``: the strings, by the recipe the single-network function uses"""
+        tables = []
+        for n in range(len(self.nets)):
+            row, lines = block[n], []
+            for i, (k, r_off, a_off, rows) in enumerate(views):
+                if per_channel:
+                    lines.append(_ncnn._table_line(names[i], [(a, a) for a in row[a_off:a_off + rows]], 1,
+                                                   lambda j, n=n, k=k: 'network {}, weight of {}, row {}'.format(n, k, j)))
+                else:
+                    lines.append(_ncnn._table_line(names[i], [(row[r_off], row[r_off + 1])], rows,
+                                                   lambda j, n=n, k=k: 'network {}, weight of {}'.format(n, k)))
+            for i, (k, _, _, _) in enumerate(views):
+                lines.append(_ncnn._table_line(names[len(views) + i], [act_of[n][i]], 1,
+                                               lambda j, n=n, k=k: 'network {}, activation range of {}'.format(n, k)))
+            tables.append(lines)
+        return tables
+
+    def write_calibration_tables(self, paths, act=None, names=None, per_channel=False):
+        """``calibration_tables`` written to one file per network (``paths``: one per network, ValueError otherwise), as
+        ``ncnn_table.write_calibration_table`` writes one; returns the lines.  Nothing is written if a table cannot be made."""
+        paths = list(paths)
+        if len(paths) != len(self.nets):
+            raise ValueError('write_calibration_tables: need one path per network ({}), got {}'.format(len(self.nets), len(paths)))
+        tables = self.calibration_tables(act, names, per_channel)
+        for path, lines in zip(paths, tables):
+            with open(path, 'w') as f:
+                for line in lines:
+                    f.write(line + '\n')
+        return tables
+
 
 def _check_bits(bits, per_channel, what):
     """a bit width as quantize_targ_layer takes it: per channel an integer in [2, 16] (_quantize_targ_layer_rows), per tensor
@@ -633,6 +741,45 @@ class BatchFoldPlan(_BatchPlan):
                                'for the real ones and overwrite the proxies with 1 and 0)')
         super().run()
         batch.folded = True
+
+
+class BatchTablePlan(_BatchPlan):
+    """The weight statistics of the ncnn calibration table for every network of a NetworkBatch (dfq_batch_table_plan,
+    include/dfq_hip.h): network 0's table of ``targ_type`` weights plus the batch's base addresses.  ``run()`` enqueues on
+    the current stream -- a clear of ``self.block`` and two launches; it reads every weight once and writes only
+    ``self.block``, float32 [n_nets, stride]: per weight its (min, max), per output row its max|w|.  The block is a torch
+    tensor and outlives ``close()``."""
+    _c = 'dfq_batch_table_plan'
+
+    def __init__(self, batch):
+        super().__init__(batch)
+        g0 = batch.nets[0][0]
+        tt = tuple(batch.targ_type)
+        layers = [(key, layer.weight) for key, layer in g0.items() if type(layer) in tt]
+        if not layers:
+            raise ValueError('table_plan: the batch has no {} layer'.format(tt))
+        entries, self._views = [], []          # (graph key, offset of (min, max), offset of the rows' max|w|, rows)
+        stride = 2 * len(layers)               # the pairs first, then the rows of every weight
+        for i, (key, w) in enumerate(layers):
+            rows = int(w.shape[0])
+            entries.append(_ffi.DfqBatchTableTensor(batch._in_slot(key, 'weight', w), rows, w.numel() // rows, 2 * i, stride))
+            self._views.append((key, 2 * i, stride, rows))
+            stride += rows
+        self.keys = [key for key, _ in layers]
+        self.n_nets, self.n_tensors = len(batch.nets), len(entries)
+        self.elements = sum(w.numel() for _, w in layers)               # weights per network, each read once (4 B)
+        self.block = torch.zeros((self.n_nets, stride), dtype=torch.float32, device=batch.stage.device)
+        self._create(((_ffi.DfqBatchTableTensor * len(entries))(*entries), len(entries)), self.block.data_ptr(), stride)
+
+    def ranges(self, n):
+        """{graph key: float32 [2] view (min, max) of network n's weight} -- what ``ncnn_table.weight_ranges`` gives"""
+        row = self.block[n]
+        return OrderedDict((key, row[r_off:r_off + 2]) for (key, r_off, _, _) in self._views)
+
+    def row_absmax(self, n):
+        """{graph key: float32 [O] view, max|w| of every output row of network n's weight} -- ``prims.row_range(w, signed=True)``"""
+        row = self.block[n]
+        return OrderedDict((key, row[a_off:a_off + rows]) for (key, _, a_off, rows) in self._views)
 
 
 class BatchAbsorbPlan(_BatchPlan):

@@ -9,7 +9,8 @@ The reference takes the line names from the table ncnn2table wrote for the same 
 that table pass its first column as ``names`` (weights block first, then activations), otherwise the graph keys
 are used.  Weight ranges of the whole network come from one multi-tensor min/max launch (dfq_quant_plan_measure).
 ``per_channel=True`` (extension) writes a genuine scale per output channel from
-dfq_row_range's |max| per row.
+dfq_row_range's |max| per row.  ``arena.NetworkBatch.calibration_tables`` writes the tables of a whole batch of networks from
+one plan (dfq_batch_table_plan); the strings of both come from ``_table_line``.
 """
 from __future__ import annotations
 
@@ -45,6 +46,22 @@ def weight_ranges(graph, targ_type=(nn.Conv2d, nn.Linear)):
     return {k: (vals[2 * i], vals[2 * i + 1]) for i, k in enumerate(keys)}
 
 
+def _table_line(name, ranges, repeat=1, where=None):
+    """One line of the table (convert_ncnn.py:191-196): ``name``, then for every (min, max) of ``ranges`` -- Python floats --
+    ``str(128. / max(abs(ma), abs(mi)))``, written ``repeat`` times.  A pair of zeros raises ZeroDivisionError, as the
+    reference's expression does; ``where(j)``, if given, says in the message which pair it was."""
+    toks = [name]
+    for j, (mi, ma) in enumerate(ranges):
+        try:
+            scale = 128. / (max(abs(ma), abs(mi)))
+        except ZeroDivisionError:
+            if where is None:
+                raise
+            raise ZeroDivisionError('float division by zero: {}'.format(where(j))) from None
+        toks += [str(scale)] * repeat
+    return ' '.join(toks)
+
+
 def calibration_table(graph, targ_type=(nn.Conv2d, nn.Linear), names=None, per_channel=False):
     """Lines of ``model_int8_tensor.table`` (convert_ncnn.py:180-201)."""
     keys = [k for k in graph if type(graph[k]) in tuple(targ_type)]
@@ -57,17 +74,14 @@ def calibration_table(graph, targ_type=(nn.Conv2d, nn.Linear), names=None, per_c
         layer = graph[k]
         if per_channel:
             amax = prims.row_range(layer.weight, signed=True).tolist()
-            lines.append(' '.join([names[i]] + [str(128. / a) for a in amax]))
+            lines.append(_table_line(names[i], [(a, a) for a in amax]))          # max(|a|, |a|) of a row's |max| a >= 0 is a
         else:
-            mi, ma = ranges[k]
-            scale = 128. / (max(abs(ma), abs(mi)))
-            lines.append(' '.join([names[i]] + [str(scale)] * layer.weight.shape[0]))
+            lines.append(_table_line(names[i], [ranges[k]], layer.weight.shape[0]))
     for i, k in enumerate(keys):
         q = graph[k].quant
         mi = float(torch.min(q.running_min))
         ma = float(torch.max(q.running_max))
-        scale = 128. / (max(abs(ma), abs(mi)))
-        lines.append(' '.join([names[len(keys) + i], str(scale)]))
+        lines.append(_table_line(names[len(keys) + i], [(mi, ma)]))
     return lines
 
 

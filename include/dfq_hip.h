@@ -494,6 +494,38 @@ int32_t dfq_batch_fold_plan_launches(const dfq_batch_fold_plan* plan);
 /* folded weights per network (each is read once and written once: 8 B) */
 int64_t dfq_batch_fold_plan_elements(const dfq_batch_fold_plan* plan);
 
+/* Weight statistics of the ncnn int8 calibration table for a whole batch of networks of one architecture (extension; the
+ * weight block of model_int8_tensor.table, convert_ncnn.py:178-201, for every network of a batch at once).  `tensors` lists
+ * the weights of the FIRST of `n_nets` networks; network n's copy of a tensor lies bases[n] - bases[0] bytes further.  One
+ * run reads every weight of every network once, writes no weight, and fills the caller's float32 block [n_nets, stride]:
+ * per tensor (min, max) at `range_offset` -- the pair dfq_quant_plan_measure gives, the `mi, ma` of convert_ncnn.py:186-187
+ * -- and per output row max|w| at `row_offset` (`rows` floats) -- what dfq_row_range(signed) gives: the per-channel form of
+ * the same scale.  Both come from the same read; they are selections, so every value is exact (the sign of a zero is +
+ * for a row's maximum and either for a tensor's bound), infinities included.  NaN is skipped; a tensor of nothing but NaN
+ * gives (NaN, NaN), a row of nothing but NaN gives 0.  A run clears the WHOLE block, then two launches: one pass over the
+ * weights (flat pieces of a tensor, 16-byte loads, any row length; partial results are merged with atomicMax of
+ * order-preserving words, which is deterministic for min / max), then a thread per tensor and network that turns the merged
+ * words into floats; no workgroup waits for another.  Offsets are in floats from a network's part of the block; the slots of
+ * different tensors must not overlap (not checked).  create: DFQ_ERR_ARG (and dfq_last_error) for a null or empty table, a
+ * null weight, rows <= 0 or row_len <= 0, a weight that is not 16-byte aligned, a null block, stride <= 0, an offset outside
+ * the stride, null bases, networks that are not 16-byte aligned to network 0.  Every tensor of network 0 must lie inside
+ * network 0's slot: nothing here can check that.  Synchronises (create only); run is asynchronous on `stream`. */
+typedef struct dfq_batch_table_plan dfq_batch_table_plan;
+typedef struct dfq_batch_table_tensor { /* addresses in network 0 */
+    const float* data;      /* the layer's weight [rows, row_len], only read (convert_ncnn.py:186-187)              */
+    int64_t rows;           /* output channels: the scale is written once per row (:194)                            */
+    int64_t row_len;
+    int64_t range_offset;   /* floats into a network's part of the block: (min, max)                                */
+    int64_t row_offset;     /* floats into a network's part of the block: max|w| of every row                       */
+} dfq_batch_table_tensor;
+
+int dfq_batch_table_plan_create(const dfq_batch_table_tensor* tensors, int32_t n_tensors, const void* const* bases, int32_t n_nets,
+                                float* out, int64_t stride, dfq_batch_table_plan** out_plan);
+int dfq_batch_table_plan_run(dfq_batch_table_plan* plan, void* stream);
+void dfq_batch_table_plan_destroy(dfq_batch_table_plan* plan);
+/* kernel launches per run (2); the clear of the block in front of them is a memset */
+int32_t dfq_batch_table_plan_launches(const dfq_batch_table_plan* plan);
+
 /* Analytic activation ranges of a whole batch of networks of one architecture (extension; set_quant_minmax,
  * utils/layer_transform.py:347-609, main_cls.py:188, for every network of a batch at once).  The caller walks the graph of
  * the FIRST network once (find_prev_bn, :299-344, and the branch grouping of :476-580) and hands over what the walk found
