@@ -9,6 +9,17 @@
 // iteration; here it is ONE read of x for the forward (row sums in float64: mean, std and both losses) and one
 // read + one write for the backward (the gradient is an affine function of x per (n, c) row).  HBM-bound:
 // 4 B per element forward, 8 B backward.  The convolutions around it stay in MIOpen.
+//
+// Loads of x, counted: the forward has ONE streaming load per element (`row[i]` in bn_stat_rows_kernel) plus the row's
+// first element once per lane (`row[0]`, the variance shift: one cache line per row, no second pass); the backward has ONE
+// load per element (`x[r * hw + i]` in the store loop) and one store -- it reads x a second time only in the [C, N] view of
+// the H*W == 1 branch, whose row means the forward did not keep (N*C values, not an activation).
+//
+// Degenerate rows.  The variance is taken from float64 sums of d = e - e0, e = x + eps rounded in float32 and e0 the row's
+// first e: the difference of two float32 values is exact in float64, so a large common offset (|mean| >> std) cancels
+// before anything is squared, a spatially constant row has d == 0 throughout and a standard deviation of exactly 0, and
+// the argument of the square root is clamped at 0.  In the backward a row whose stored standard deviation is 0 gets no
+// std-term gradient (torch's std backward: `masked_fill_(result == 0, 0)`) instead of 0 / 0; its mean term is unchanged.
 #include <algorithm>
 
 #include "dfq_common.hpp"
@@ -29,13 +40,15 @@ __global__ __launch_bounds__(kBlock) void bn_stat_rows_kernel(const float* __res
     const int lanes = (kRowsPerBlock == 1) ? kBlock : kWave;
     const int t = (kRowsPerBlock == 1) ? threadIdx.x : threadIdx.x % kWave;
     const float* row = x + (live ? r : 0) * hw;
+    const float e0 = row[0] + eps;                     // the shift of the variance sums (same address in every lane of the row)
     double s0 = 0.0, s1 = 0.0, s2 = 0.0;
     for (int64_t i = t; i < hw; i += lanes) {
-        const float v = row[i];
+        const float v = row[i];                        // the one read of x
         const float e = v + eps;                       // torch.std(x + eps): the shift is rounded in float32
+        const double d = (double)e - (double)e0;       // exact
         s0 += (double)v;
-        s1 += (double)e;
-        s2 += (double)e * (double)e;
+        s1 += d;
+        s2 += d * d;
     }
     s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2);
     if (kRowsPerBlock == 1) {
@@ -59,17 +72,17 @@ __global__ __launch_bounds__(kBlock) void bn_stat_rows_kernel(const float* __res
         const double n = (double)hw;
         const int c = (int)(r % channels);
         if (terms & 1) {
-            const float mean = (float)(s0 / n);
-            row_mean[r] = mean;
-            const float dm = bn_mean[c] - mean;
-            row_terms[2 * r + 0] = (double)dm * (double)dm;
+            const double mean = s0 / n;
+            row_mean[r] = (float)mean;
+            const double dm = (double)bn_mean[c] - mean;                   // the loss terms see the unrounded statistics
+            row_terms[2 * r + 0] = dm * dm;
         }
         if (terms & 2) {
-            const double me = s1 / n;
-            const float sd = (float)sqrt((s2 - s1 * me) / (n - 1.0));      // unbiased, like torch.std
-            row_std[r] = sd;
-            const float ds = bn_std[c] - sd;
-            row_terms[2 * r + 1] = (double)ds * (double)ds;
+            const double var = (s2 - s1 * (s1 / n)) / (n - 1.0);           // unbiased, like torch.std; shift-invariant
+            const double sd = sqrt(var < 0.0 ? 0.0 : var);                 // (a NaN stays a NaN)
+            row_std[r] = (float)sd;
+            const double ds = (double)bn_std[c] - sd;
+            row_terms[2 * r + 1] = ds * ds;
         }
     }
 }
@@ -87,6 +100,7 @@ __global__ __launch_bounds__(kBlock) void bn_stat_reduce_kernel(const double* __
 }
 
 // d(mean_loss)/dx = 2 (mean - bn_mean) / (C * HW);   d(std_loss)/dx = 2 (std - bn_std) / C * (x + eps - mean_e) / ((HW-1) std)
+// (0 where std == 0).  One read of x and one write of grad per element.
 __global__ __launch_bounds__(kBlock) void bn_stat_backward_kernel(const float* __restrict__ x, int64_t rows, int64_t hw,
                                                                   int32_t channels, const float* __restrict__ bn_mean,
                                                                   const float* __restrict__ bn_std, float eps,
@@ -109,7 +123,8 @@ __global__ __launch_bounds__(kBlock) void bn_stat_backward_kernel(const float* _
     }
     const float sd = (terms & 2) ? row_std[r] : 1.0f;
     const float a = (terms & 1) ? g_mean * 2.0f * (mean - bn_mean[c]) / (denom * (float)hw) : 0.0f;
-    const float b = (terms & 2) ? g_std * 2.0f * (sd - bn_std[c]) / (denom * ((float)hw - 1.0f) * sd) : 0.0f;
+    // sd == 0 (a constant row): no std-term gradient, like torch's masked_fill_(result == 0, 0); a NaN sd stays in its row
+    const float b = ((terms & 2) && sd != 0.0f) ? g_std * 2.0f * (sd - bn_std[c]) / (denom * ((float)hw - 1.0f) * sd) : 0.0f;
     const float mean_e = mean + eps;
     for (int64_t i = threadIdx.x; i < hw; i += kBlock) {
         const float g = a + b * ((x[r * hw + i] + eps) - mean_e);

@@ -863,6 +863,11 @@ int dfq_bn_through_layer(const float* weight, int32_t out_ch, int32_t in_per_gro
  * (n, c) value, the std term over the contiguous [N, C] block REINTERPRETED as C rows of N values (row r against
  * bn_std[r]); row_std then holds C entries.  The `_dev` backward reads the two upstream gradients from device memory
  * (grad_pair[0] = d/d loss2[0], grad_pair[1] = d/d loss2[1]): no host synchronisation inside an autograd backward.
+ * Degenerate rows: the variance comes from float64 sums of (x + eps) minus the row's first (x + eps), so a large common
+ * offset cancels exactly and a spatially constant row has row_std == 0 exactly (never NaN; the square root's argument is
+ * clamped at 0).  A row whose row_std is 0 gets NO std-term gradient -- torch's std backward, masked_fill_(result == 0, 0),
+ * not 0 / 0 -- in both row views of the H*W == 1 branch; its mean-term gradient is unchanged.  A NaN or inf in x stays in
+ * its own row's statistics and gradient (and in the losses).
  * ---------------------------------------------------------------------------------------- */
 size_t dfq_bn_stat_loss_scratch_bytes(int64_t rows);
 int dfq_bn_stat_loss_forward(const float* x, int64_t rows, int64_t hw, int32_t channels, const float* bn_mean,

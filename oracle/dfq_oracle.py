@@ -932,22 +932,38 @@ def zeroq_quant_rows(x, num_bits=8, return_codes=False):
 # --------------------------------------------------------------------------------------------
 # f2  BatchNorm-statistics loss of ZeroQ's distillation (ZeroQ/distill_data.py:40-45, :172-196)
 # --------------------------------------------------------------------------------------------
+def bn_stat_rows(x, eps=1e-6):
+    """x [N, C, H, W] -> (row mean [N, C], row std, e - mean(e), length of a std row), float64.  The std rows are the
+    (n, c) rows, or for H*W == 1 the contiguous [N, C] block viewed as [C, N] (distill_data.py:181-182; std is [1, C]
+    then).  e = x + eps rounded in float32; it is centred on the row's first element before anything is summed (exact
+    in float64), so a spatially constant row has a std of exactly 0 whatever its value."""
+    x32 = np.asarray(x, dtype=F32)
+    n, c = x32.shape[:2]
+    flat = x32.reshape(n, c, -1)
+    e = (flat + F32(eps)).astype(F32).astype(np.float64)
+    if flat.shape[-1] == 1:
+        e = e.reshape(1, c, n)                       # `tmp_output.view(C, -1)`
+    d = e - e[..., :1]
+    d = d - d.mean(-1, keepdims=True)
+    std = np.sqrt((d ** 2).sum(-1) / (e.shape[-1] - 1))
+    return flat.astype(np.float64).mean(-1), std, d, e.shape[-1]
+
+
 def bn_stat_losses(x, bn_mean, bn_std, eps=1e-6, denom=None):
     """x [N, C, H, W] -> (mean_loss, std_loss, dmean_loss/dx, dstd_loss/dx), evaluated in float64 (the reference
-    computes in float32 with an unspecified reduction order; parity is a 1e-5 contract)."""
-    x64 = np.asarray(x, dtype=F32).astype(np.float64)
-    n, c = x64.shape[:2]
-    flat = x64.reshape(n, c, -1)
-    hw = flat.shape[-1]
+    computes in float32 with an unspecified reduction order; parity is a 1e-5 contract).  A row whose std is exactly 0
+    (spatially constant) gets no std-term gradient: torch's std backward, `masked_fill_(result == 0, 0)`, not 0 / 0."""
+    shape = np.asarray(x).shape
+    n, c = shape[:2]
+    hw = int(np.prod(shape[2:]))
     denom = float(c if denom is None else denom)
-    e = (np.asarray(x, dtype=F32).reshape(n, c, -1) + F32(eps)).astype(F32).astype(np.float64)   # x + eps is rounded in float32
-    mean = flat.mean(-1)
-    me = e.mean(-1)
-    std = np.sqrt(((e - me[..., None]) ** 2).sum(-1) / (hw - 1))
+    mean, std, d, hw_std = bn_stat_rows(x, eps)
     bm = np.asarray(bn_mean, dtype=np.float64).reshape(1, c)
     bs = np.asarray(bn_std, dtype=np.float64).reshape(1, c)
     mean_loss = ((bm - mean) ** 2).sum() / denom
     std_loss = ((bs - std) ** 2).sum() / denom
-    g_mean = np.broadcast_to((2.0 * (mean - bm) / (denom * hw))[..., None], flat.shape).reshape(x64.shape)
-    g_std = ((2.0 * (std - bs) / denom)[..., None] * (e - me[..., None]) / ((hw - 1) * std[..., None])).reshape(x64.shape)
+    g_mean = np.broadcast_to((2.0 * (mean - bm) / (denom * hw))[..., None], (n, c, hw)).reshape(shape)
+    live = std != 0
+    scale = np.where(live, 2.0 * (std - bs) / denom / ((hw_std - 1) * np.where(live, std, 1.0)), 0.0)
+    g_std = (scale[..., None] * d).reshape(shape)
     return float(mean_loss), float(std_loss), g_mean, g_std

@@ -12,7 +12,12 @@ module is imported as it is.  Three module globals of the imported module are re
 source): `getRandomData` returns the seeded start batch of the fixture instead of a DataLoader over torch's global RNG,
 `range` caps the hard-coded 1000 iterations (distill_data.py:159) at k, ReduceLROnPlateau.step records the loss
 it is given and its constructor swallows the `verbose=` argument this torch no longer has.  The network is a small conv/BN stack whose last BN sits on 1x1 feature maps, so the reference's
-H*W == 1 branch (:181-182) is on the path.
+H*W == 1 branch (:181-182) is on the path.  The `_dead` case zeroes one output filter of the second convolution (its bias
+stays), so that channel's BN input rows are spatially constant: torch's std backward gives such a row a zero gradient, and
+the reference's losses and refined batch stay finite (asserted here).
+
+    python oracle/make_golden_zeroq.py                  writes every case
+    python oracle/make_golden_zeroq.py zeroq_s2_dead    writes the named cases only
 """
 from __future__ import annotations
 
@@ -54,9 +59,12 @@ from common import build_distill_net           # noqa: E402  (the same builder t
 GOLD = os.path.join(ROOT, 'tests', 'golden')
 
 
-def run_case(seed, k, shape, with_pixel_bn):
+def run_case(seed, k, shape, with_pixel_bn, dead_filter=None):
     g = torch.Generator().manual_seed(seed)
     net = build_distill_net(g, with_pixel_bn)
+    if dead_filter is not None:
+        with torch.no_grad():
+            net[3].weight[dead_filter].zero_()
     start = ((torch.randint(high=255, size=shape, generator=g).float() - 127.) / 128.) * 3.0   # UniformDataset, data_utils.py:47
     losses = []
     Plateau = torch.optim.lr_scheduler.ReduceLROnPlateau
@@ -77,18 +85,30 @@ def run_case(seed, k, shape, with_pixel_bn):
         Plateau.__init__, Plateau.step = orig_init, orig_step
         del ref_dd.range
     assert len(out) == 1 and len(losses) == k
+    if dead_filter is not None:
+        with torch.no_grad():
+            rows = net[:4](start)[:, dead_filter].reshape(shape[0], -1)
+        assert bool((rows == rows[:, :1]).all()), 'the dead channel is not spatially constant'
+        assert np.isfinite(losses).all() and bool(torch.isfinite(out[0]).all()), 'the reference itself went non-finite'
     rec = {'start': start.numpy().copy(), 'refined': out[0].numpy().copy(), 'losses': np.array(losses, dtype=np.float64),
            'cfg': np.array([seed, k, int(with_pixel_bn)])}
     for name, v in net.state_dict().items():
         rec['param.' + name] = v.numpy().copy()
-    tag = 'zeroq_s{}{}'.format(seed, '_px' if with_pixel_bn else '')
+    tag = 'zeroq_s{}{}{}'.format(seed, '_px' if with_pixel_bn else '', '_dead' if dead_filter is not None else '')
     np.savez_compressed(os.path.join(GOLD, tag + '.npz'), **rec)
     print('{}: {} iterations, loss {:.4f} -> {:.4f}'.format(tag, k, losses[0], losses[-1]))
 
 
+CASES = {
+    'zeroq_s0': (0, 8, (4, 3, 16, 16), False),
+    'zeroq_s1_px': (1, 8, (4, 3, 16, 16), True),
+    'zeroq_s2_dead': (2, 8, (4, 3, 16, 16), False, 5),
+}
+
+
 def main():
-    run_case(0, 8, (4, 3, 16, 16), False)
-    run_case(1, 8, (4, 3, 16, 16), True)
+    for tag in (sys.argv[1:] or CASES):
+        run_case(*CASES[tag])
 
 
 if __name__ == '__main__':

@@ -93,16 +93,23 @@ def test_unused_output_gets_zero_gradient(engine):
     np.testing.assert_allclose(npy(xe.grad), xr.grad.numpy(), rtol=1e-4, atol=1e-6)
 
 
-@pytest.mark.parametrize('case', ['zeroq_s0', 'zeroq_s1_px'])
+@pytest.mark.parametrize('case', ['zeroq_s0', 'zeroq_s1_px', 'zeroq_s2_dead'])
 def test_distillation_against_reference(engine, case):
-    """k iterations of the reference's getDistilData vs dfq_amd.zeroq.getDistilData from the same start batch."""
+    """k iterations of the reference's getDistilData vs dfq_amd.zeroq.getDistilData from the same start batch.
+    `_dead`: one output filter of the second convolution is zero, so that channel's BN input rows are spatially constant
+    (std == 0: no std-term gradient, like torch's std backward; 0 / 0 there would turn the whole batch into NaN)."""
     import os
     gold = np.load(os.path.join(GOLD, case + '.npz'))
     seed, k, px = (int(v) for v in gold['cfg'])
     net = build_distill_net(torch.Generator().manual_seed(seed), bool(px))
     net.load_state_dict({n[len('param.'):]: torch.from_numpy(gold[n]) for n in gold.files if n.startswith('param.')})
-    net.to(engine.device)
     start = torch.from_numpy(gold['start'])
+    if case.endswith('_dead'):
+        with torch.no_grad():
+            rows = net[:4](start)
+        dead = [c for c in range(rows.shape[1]) if bool((rows[:, c] == rows[:, c, :1, :1]).all())]
+        assert len(dead) == 1 and not bool(net[3].weight[dead[0]].any()), 'the fixture has no spatially constant BN input channel'
+    net.to(engine.device)
     losses = []
     out = zeroq.getDistilData(net, tuple(start.shape), num_batch=1, iterations=k, init=[start], early_break_factor=0.0,
                               loss_log=losses)
@@ -110,6 +117,7 @@ def test_distillation_against_reference(engine, case):
     np.testing.assert_allclose(np.array(losses), gold['losses'], rtol=1e-4)
     # Adam's first steps are +-lr regardless of the gradient's size, so the batches stay together to float32 noise
     np.testing.assert_allclose(npy(out[0]), gold['refined'], rtol=0, atol=1e-4)
+    assert np.isfinite(losses).all() and np.isfinite(npy(out[0])).all()
 
 
 def test_distillation_loop_reduces_the_loss(engine):
