@@ -253,6 +253,18 @@ __device__ __forceinline__ float slot_min(uint32_t slot) { return dec_ord(~slot)
 // a signalling NaN: three instructions per min or max.  In the hot loops (eight per register slot, plus the
 // shuffle butterflies) that was a quarter of all vector instructions.  v_min_f32 / v_max_f32 themselves
 // already return the non-NaN operand, which is all these reductions rely on.
+// "The non-NaN operand" holds for QUIET NaNs only.  Every kernel of this library runs in IEEE mode, and there a SIGNALLING NaN
+// operand makes v_min_f32 / v_max_f32 return that NaN, quieted -- the next step then keeps its other operand, and what the lane
+// had accumulated so far is gone.  Results of these instructions are never signalling, so only values that come straight from
+// memory need care: quiet_nan() (one v_max_f32 x, x, x; every other value, denormals included, passes unchanged) in front of
+// the first min / max that sees them.
+__device__ __forceinline__ float quiet_nan(float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_canonicalizef(v);
+#else
+    return v;                            // fminf / fmaxf skip a NaN of either kind
+#endif
+}
 __device__ __forceinline__ float vmin_raw(float a, float b) {
 #if defined(__HIP_DEVICE_COMPILE__)
     float r;

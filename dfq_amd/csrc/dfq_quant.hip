@@ -19,6 +19,13 @@ constexpr int kChunk = kBlock * 16;   // elements one workgroup owns in the mult
 // ---------------------------------------------------------------------------------------------
 // device bodies
 // ---------------------------------------------------------------------------------------------
+// one 16-byte vector into a lane's running (min, max): NaN of either kind is skipped (quiet_nan, dfq_common.hpp)
+__device__ __forceinline__ void fold_vec(const float4& raw, float& mn, float& mx) {
+    const float x = quiet_nan(raw.x), y = quiet_nan(raw.y), z = quiet_nan(raw.z), w = quiet_nan(raw.w);
+    mn = vmin_raw(vmin_raw(mn, x), vmin_raw(y, vmin_raw(z, w)));
+    mx = vmax_raw(vmax_raw(mx, x), vmax_raw(y, vmax_raw(z, w)));
+}
+
 __device__ __forceinline__ void thread_minmax_range(const float* __restrict__ x, int64_t begin,
                                                     int64_t end, float& mn, float& mx) {
     const int tid = threadIdx.x;
@@ -28,7 +35,7 @@ __device__ __forceinline__ void thread_minmax_range(const float* __restrict__ x,
         const int64_t n4 = len >> 2;
         const float4* p4 = reinterpret_cast<const float4*>(p);
         // four independent 16-byte loads per trip (a read-only pass with one load in flight per lane leaves most of
-        // the memory pipeline idle), raw v_min / v_max (no canonicalisation prologue)
+        // the memory pipeline idle), raw v_min / v_max on values quieted once (fold_vec)
         int64_t i = tid;
         for (; i + 7 * kBlock < n4; i += 8 * kBlock) {              // eight 16-byte loads in flight per lane
             float4 v[8];
@@ -38,25 +45,17 @@ __device__ __forceinline__ void thread_minmax_range(const float* __restrict__ x,
                 else v[u] = p4[i + u * kBlock];
             }
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                mn = vmin_raw(vmin_raw(mn, v[u].x), vmin_raw(v[u].y, vmin_raw(v[u].z, v[u].w)));
-                mx = vmax_raw(vmax_raw(mx, v[u].x), vmax_raw(v[u].y, vmax_raw(v[u].z, v[u].w)));
-            }
+            for (int u = 0; u < 8; ++u) fold_vec(v[u], mn, mx);
         }
         for (; i + 3 * kBlock < n4; i += 4 * kBlock) {
             float4 v[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) v[u] = p4[i + u * kBlock];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                mn = vmin_raw(vmin_raw(mn, v[u].x), vmin_raw(v[u].y, vmin_raw(v[u].z, v[u].w)));
-                mx = vmax_raw(vmax_raw(mx, v[u].x), vmax_raw(v[u].y, vmax_raw(v[u].z, v[u].w)));
-            }
+            for (int u = 0; u < 4; ++u) fold_vec(v[u], mn, mx);
         }
         for (; i < n4; i += kBlock) {
-            const float4 v = p4[i];
-            mn = vmin_raw(vmin_raw(mn, v.x), vmin_raw(v.y, vmin_raw(v.z, v.w)));
-            mx = vmax_raw(vmax_raw(mx, v.x), vmax_raw(v.y, vmax_raw(v.z, v.w)));
+            fold_vec(p4[i], mn, mx);
         }
         for (int64_t i = (n4 << 2) + tid; i < len; i += kBlock) {
             const float v = p[i];
@@ -529,6 +528,7 @@ int dfq_fake_quant(const float* x, float* y, int64_t n, int32_t num_bits, int32_
                    int32_t* codes, void* stream) {
     if (!x || !y || n < 0) return fail_arg("dfq_fake_quant: bad argument");
     if (num_bits < 1 || num_bits > 30) return fail_arg("dfq_fake_quant: num_bits=%d out of range", num_bits);
+    if (symmetric && num_bits == 1) return fail_arg("dfq_fake_quant: symmetric with num_bits=1 has qmax = 0 (the scale would be max / 0)");
     if (range_mode < 0 || range_mode > 2) return fail_arg("dfq_fake_quant: range_mode=%d", range_mode);
     if (range_mode != 0 && !minmax_dev) return fail_arg("dfq_fake_quant: range_mode %d needs minmax_dev", range_mode);
     if (n == 0) return DFQ_OK;
@@ -661,6 +661,8 @@ int dfq_quant_plan_create(const dfq_segment* segs, int32_t n_segs, dfq_quant_pla
     for (int i = 0; i < n_segs; ++i) {
         if (!segs[i].data || segs[i].n <= 0) return fail_arg("dfq_quant_plan_create: segment %d is empty", i);
         if (segs[i].num_bits < 1 || segs[i].num_bits > 30) return fail_arg("dfq_quant_plan_create: segment %d bits", i);
+        if (segs[i].symmetric && segs[i].num_bits == 1)
+            return fail_arg("dfq_quant_plan_create: segment %d: symmetric with num_bits=1 has qmax = 0 (the scale would be max / 0)", i);
         h[i].data = segs[i].data;
         h[i].codes = segs[i].codes;
         h[i].n = segs[i].n;
@@ -737,6 +739,7 @@ int dfq_quant_error(const float* x, int64_t n, int64_t rows, int32_t num_bits, i
                     int32_t reduction, float* out, void* scratch, void* stream) {
     if (!x || !out || !scratch || n <= 0) return fail_arg("dfq_quant_error: bad argument");
     if (reduction < 0 || reduction > 4) return fail_arg("dfq_quant_error: reduction=%d", reduction);
+    if (symmetric && num_bits == 1) return fail_arg("dfq_quant_error: symmetric with num_bits=1 has qmax = 0 (the scale would be max / 0)");
     hipStream_t st = as_stream(stream);
     uint32_t* slots = reinterpret_cast<uint32_t*>(scratch);
     double* partial = reinterpret_cast<double*>(reinterpret_cast<char*>(scratch) + 16);

@@ -292,6 +292,7 @@ int dfq_batch_quant_plan_create(const dfq_batch_quant_tensor* tensors, int32_t n
         const int lo = t.per_row ? 2 : 1, hi = t.per_row ? 16 : 30;
         if (t.num_bits < lo || t.num_bits > hi)
             return fail_arg("%s: tensor %d: num_bits %d outside [%d, %d] (%s)", me, i, (int)t.num_bits, lo, hi, t.per_row ? "per row" : "per tensor");
+        if (t.symmetric && t.num_bits == 1) return fail_arg("%s: tensor %d: symmetric with num_bits=1 has qmax = 0 (the scale would be max / 0)", me, i);
         if (t.code_offset < -1 || t.range_offset < -1) return fail_arg("%s: tensor %d: negative offset", me, i);
         if (t.code_offset >= 0) {
             if (!codes) return fail_arg("%s: tensor %d writes codes, but the code block is null", me, i);

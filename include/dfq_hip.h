@@ -284,7 +284,14 @@ int dfq_le_trace_blocks(dfq_le_plan* plan, const dfq_le_config* cfg, int32_t lau
  * Tensor primitives -- utils/quantize.py:23-76 (UniformQuantize.forward), :102-119 (QuantMeasure)
  * ---------------------------------------------------------------------------------------- */
 
-/* out2[0] = min(x), out2[1] = max(x) as float32 (device).  `scratch2` is a device uint32[2] that
+/* Special values in the reductions of this section and of dfq_quant_plan_* (the rule dfq_batch_table_plan states too): a
+ * NaN of any payload, quiet or signalling, is SKIPPED; a tensor, sample or segment of nothing but NaN gives (NaN, NaN);
+ * infinities and denormals are ordinary values; min / max are selections, so every result is exact and only the sign of a
+ * zero result is free.  The same on the 16-byte path and on the scalar path (unaligned pointers, tails).  torch's min() /
+ * max() would PROPAGATE the NaN instead: a documented divergence -- one NaN weight does not cost a layer its range.
+ * tests/test_quant_adversarial.py holds the cases. */
+
+/* out2[0] = min(x), out2[1] = max(x) as float32 (device), NaN skipped (above).  `scratch2` is a device uint32[2] that
  * the call zeroes and uses for the order-preserving atomic reduction. */
 int dfq_tensor_minmax(const float* x, int64_t n, float* out2, uint32_t* scratch2, void* stream);
 
@@ -296,7 +303,11 @@ int dfq_tensor_minmax(const float* x, int64_t n, float* out2, uint32_t* scratch2
  *                 in float64 on the device (same values as mode 0 without a host round trip).
  *   range_mode 2: min/max from `minmax_dev`, recipe entirely in float32 -- the `min_value=None`
  *                 tensor path of quantize.py:24-35 (bias fake-quant call sites :198,:226,:311,:335).
- * `codes` (device int32[n]) receives the integer codes when not NULL.  x == y (in place) is allowed. */
+ * `codes` (device int32[n]) receives the integer codes when not NULL.  x == y (in place) is allowed.
+ * A NaN input gives a NaN output (its integer code is unspecified); an infinite input clamps to qmin / qmax.
+ * DFQ_ERR_ARG (and dfq_last_error) for num_bits outside [1, 30] and for symmetric with num_bits == 1: qmax = 2^0 - 1 = 0
+ * and the scale would be max / 0 -- the reference raises ZeroDivisionError there (quantize.py:56).  The same refusal in
+ * dfq_quant_plan_create, dfq_quant_error and, for per-tensor tensors, dfq_batch_quant_plan_create. */
 int dfq_fake_quant(const float* x, float* y, int64_t n, int32_t num_bits, int32_t symmetric,
                    int32_t range_mode, double min_value, double max_value,
                    const float* minmax_dev, int32_t* codes, void* stream);
@@ -304,7 +315,9 @@ int dfq_fake_quant(const float* x, float* y, int64_t n, int32_t num_bits, int32_
 /* QuantMeasure statistics (quantize.py:103-107): out2[0] = mean_n(min over chw of x[n]),
  * out2[1] = mean_n(max over chw of x[n]).  If `running2` (device float[2] = {running_min,
  * running_max}) is not NULL it is updated in place: running_min = min(running_min, out2[0]),
- * running_max = max(running_max, out2[1]).  `scratch` is a device uint32[2*n_samples]. */
+ * running_max = max(running_max, out2[1]).  `scratch` is a device uint32[2*n_samples].
+ * NaN is skipped inside a sample (above); a sample of nothing but NaN has extrema (NaN, NaN), which makes BOTH means NaN and
+ * leaves running2 as it was (Python min(r, nan) keeps r). */
 int dfq_sample_minmax_mean(const float* x, int32_t n_samples, int64_t sample_len, float* out2,
                            float* running2, uint32_t* scratch, void* stream);
 /* QuantMeasure.forward with update_stat (utils/quantize.py:102-119; improve_dfq.py:280-297 runs it for every activation of
@@ -312,7 +325,9 @@ int dfq_sample_minmax_mean(const float* x, int32_t n_samples, int64_t sample_len
  * (as dfq_sample_minmax_mean does), folds it into running2 = (running_min, running_max) (quantize.py:106-107) and quantises
  * x -> y with the folded range (float64 recipe, asymmetric).  scratch: 4 * n_samples uint32 owned by the caller, ZERO before the
  * first call; parity alternates 0, 1, 0, ... from call to call on the same scratch (each call clears the half the next one
- * accumulates into).  Same numbers as dfq_sample_minmax_mean(running2) + dfq_fake_quant(range_mode 1). */
+ * accumulates into).  Same numbers as dfq_sample_minmax_mean(running2) + dfq_fake_quant(range_mode 1), special values
+ * included: NaN skipped inside a sample, NaN means leave running2 alone and x is quantised with the range it had.  Always
+ * asymmetric, so num_bits == 1 is allowed. */
 int dfq_quant_measure(const float* x, float* y, int32_t n_samples, int64_t sample_len, int32_t num_bits, float* running2,
                       uint32_t* scratch, int32_t parity, void* stream);
 /* The same in ONE launch (round 4 experiment, OPT-IN through DFQ_QM_FUSED=1 in the Python layer: measured slower than the two
@@ -336,7 +351,9 @@ int dfq_quant_measure_fused_status(const uint32_t* scratch, int32_t n_samples, v
 typedef struct dfq_quant_plan dfq_quant_plan;
 
 /* One plan over a table of tensors ("segments"): per-tensor min/max in one launch, fake-quant of
- * all tensors in a second launch. */
+ * all tensors in a second launch.  The min/max of a segment skips NaN (see "Special values" above; a segment of nothing
+ * but NaN reports (NaN, NaN) and is quantised to NaN); segments do not see each other.  create: DFQ_ERR_ARG (and
+ * dfq_last_error) for a null or empty segment, num_bits outside [1, 30], symmetric with num_bits == 1 (qmax = 0). */
 typedef struct dfq_segment {
     float* data;            /* device                                                    */
     int64_t n;
@@ -386,7 +403,7 @@ int dfq_row_quant_plan_run(dfq_row_quant_plan* plan, void* stream);
  * tensors of at most dfq_batch_quant_register_elements() elements take one launch, longer per-tensor ones a min/max
  * launch in front of it (folding every chunk into one pair of slots per tensor and network, cleared first).  Every
  * tensor of network 0 must lie inside network 0's slot: nothing here can check that.  create: DFQ_ERR_ARG (and dfq_last_error) for empty / null arguments, bit widths outside
- * [2, 16] (per row) or [1, 30] (per tensor), 1-byte codes of more than 8 bits, offsets that overflow their stride.
+ * [2, 16] (per row) or [1, 30] (per tensor), a symmetric per-tensor tensor of 1 bit (qmax = 0), 1-byte codes of more than 8 bits, offsets that overflow their stride.
  * Synchronises (create only); run is asynchronous on `stream`. */
 typedef struct dfq_batch_quant_plan dfq_batch_quant_plan;
 typedef struct dfq_batch_quant_tensor {
@@ -718,7 +735,8 @@ int32_t dfq_bc_plan_chain_steps(const dfq_bc_plan* plan);
  *   reduction 3: 'channel' -> out[0] = sum_o | sum_rest eps |      (rows = shape[0])
  *   reduction 4: 'spatial' -> out[0] = sum_{o,i} | sum_khkw eps |  (rows = shape[0]*shape[1])
  * `rows` is the number of leading-dimension groups for reductions 3/4 (ignored otherwise).
- * `scratch` is device memory of dfq_quant_error_scratch_bytes(n, rows) bytes. */
+ * `scratch` is device memory of dfq_quant_error_scratch_bytes(n, rows) bytes.  DFQ_ERR_ARG (and dfq_last_error) for
+ * symmetric with num_bits == 1 (qmax = 0, see dfq_fake_quant). */
 size_t dfq_quant_error_scratch_bytes(int64_t n, int64_t rows);
 int dfq_quant_error(const float* x, int64_t n, int64_t rows, int32_t num_bits, int32_t symmetric,
                     int32_t reduction, float* out, void* scratch, void* stream);
