@@ -80,6 +80,14 @@ class DfqBatchTableTensor(Structure):
     _fields_ = [('data', c_void_p), ('rows', c_int64), ('row_len', c_int64), ('range_offset', c_int64), ('row_offset', c_int64)]
 
 
+class DfqBatchErrorTensor(Structure):
+    _fields_ = [('data', c_void_p), ('rows', c_int64), ('row_len', c_int64), ('out_offset', c_int64)]
+
+
+class DfqBatchErrorConfig(Structure):
+    _fields_ = [('num_bits', c_int32), ('symmetric', c_int32), ('per_row', c_int32), ('pad', c_int32)]
+
+
 class DfqBatchActResult(Structure):
     _fields_ = [('step_begin', c_int32), ('step_count', c_int32)]
 
@@ -210,6 +218,11 @@ SIGNATURES = {
     'dfq_batch_table_plan_run': (c_int32, [c_void_p, c_void_p]),
     'dfq_batch_table_plan_destroy': (None, [c_void_p]),
     'dfq_batch_table_plan_launches': (c_int32, [c_void_p]),
+    'dfq_batch_error_plan_create': (c_int32, [POINTER(DfqBatchErrorTensor), c_int32, POINTER(DfqBatchErrorConfig), c_int32,
+                                              POINTER(c_void_p), c_int32, c_void_p, c_int64, POINTER(c_void_p)]),
+    'dfq_batch_error_plan_run': (c_int32, [c_void_p, c_void_p]),
+    'dfq_batch_error_plan_destroy': (None, [c_void_p]),
+    'dfq_batch_error_plan_launches': (c_int32, [c_void_p]),
     'dfq_batch_act_plan_create': (c_int32, [POINTER(DfqBatchActResult), c_int32, POINTER(DfqBatchActStep), c_int32,
                                             POINTER(DfqBatchActSource), c_int32, POINTER(c_void_p), c_int32, c_float, c_float,
                                             c_void_p, c_int64, POINTER(c_void_p)]),

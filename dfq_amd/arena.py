@@ -34,6 +34,12 @@ network gives each tensor's (min, max) and each output row's max|w|, and ``calib
 activation ranges, into one table per network (tests/test_batch_table.py).  That driver then runs on a batch as
 fold_plan -> le_plan().run(signed=True) -> absorb_plan(absorb=False, range_clip=...) -> bc_plan().run(signed=True) ->
 act_range_plan -> calibration_tables.
+``error_plan`` is the batch form of the reference's quality signal, ``_quantize_error(param, num_bits, reduction, signed)``
+(dfq.py:8-25), which both of its drivers import: three launches read every weight of every network twice, write none, and
+leave per weight the float64 sums of w^2 and of e, |e|, e^2 for one to four quantiser configurations, e = Q(w) - w being bit
+for bit what ``quant_plan`` would store minus w; ``quantize_error`` turns them into the reference's 'sum' and 'mean', the mean
+squared error and the SQNR (tests/test_batch_error.py).  It changes nothing, so it can stand anywhere in the sequence -- in
+front of ``le_plan`` and behind it shows what equalisation bought.
 """
 from __future__ import annotations
 
@@ -540,6 +546,44 @@ class NetworkBatch:
             act_of = [[(both[0][n * len(keys) + i], both[1][n * len(keys) + i]) for i in range(len(keys))] for n in range(n_nets)]
         return plan._views, block, act_of
 
+    def error_plan(self, configs=((8, False, False),)):
+        """One plan (BatchErrorPlan) for the weight quantisation error of every ``targ_type`` weight of every network under
+        one to four quantiser configurations, each ``(bit_weight, per_channel, signed)`` as ``quant_plan`` takes them: the
+        batch form of ``_quantize_error(param, num_bits, reduction, signed)`` (dfq.py:8-25).  ``run()`` reads every weight
+        twice and writes none; ``errors(n)`` gives per weight ``sum w^2`` and, per configuration, ``sum e``, ``sum |e|`` and
+        ``sum e^2`` of e = Q(w) - w, where Q(w) is bit for bit the value ``quant_plan`` with that configuration would store.
+        The 'channel' and 'spatial' reductions of dfq.py:20-23 have no caller in the reference and are not offered; biases
+        (16 bits per tensor, a negligible error) are not included.  ValueError for a bad configuration, RuntimeError for a
+        weight of network 0 that has left its slot."""
+        self._ready('error_plan')
+        return BatchErrorPlan(self, configs)
+
+    def quantize_error(self, bit_weight=8, per_channel=False, signed=False):
+        """error_plan + run + synchronise + close for one configuration: one ``OrderedDict[key -> dict]`` per network with
+        ``sum`` = sum |e| (``_quantize_error(w, bits, 'sum')``), ``mean`` = sum e / numel (its ``'mean'``), ``mse`` =
+        sum e^2 / numel and ``sqnr_db`` = 10 log10(sum w^2 / sum e^2), ``inf`` where sum e^2 is 0; Python floats from
+        float64 sums."""
+        plan = self.error_plan(((bit_weight, per_channel, signed),))
+        try:
+            plan.run()
+            _ffi.synchronize()
+            block = plan.block.cpu()
+        finally:
+            plan.close()
+        out = []
+        for n in range(len(self.nets)):
+            res = OrderedDict()
+            for key, e in plan.errors(n, block).items():
+                numel, s, s_abs, s_sq = e['numel'], float(e['sum'][0]), float(e['sum_abs'][0]), float(e['sum_sq'][0])
+                if s_sq == 0:
+                    sqnr = math.inf
+                else:
+                    ratio = e['sum_sq_w'] / s_sq
+                    sqnr = 10.0 * math.log10(ratio) if ratio > 0 else (-math.inf if ratio == 0 else math.nan)
+                res[key] = {'sum': s_abs, 'mean': s / numel, 'mse': s_sq / numel, 'sqnr_db': sqnr}
+            out.append(res)
+        return out
+
     def _format_tables(self, names, per_channel, views, block, act_of):
         """the host side of ``calibration_tables``: the strings, by the recipe the single-network function uses"""
         tables = []
@@ -780,6 +824,63 @@ class BatchTablePlan(_BatchPlan):
         """{graph key: float32 [O] view, max|w| of every output row of network n's weight} -- ``prims.row_range(w, signed=True)``"""
         row = self.block[n]
         return OrderedDict((key, row[a_off:a_off + rows]) for (key, _, a_off, rows) in self._views)
+
+
+class BatchErrorPlan(_BatchPlan):
+    """The weight quantisation error of every network of a NetworkBatch under one to four quantiser configurations
+    (dfq_batch_error_plan, include/dfq_hip.h): network 0's table of ``targ_type`` weights plus the batch's base addresses.
+    ``run()`` enqueues on the current stream -- a clear of the plan's range words and three launches; it reads every weight
+    twice and writes only ``self.block``, float64 [n_nets, stride]: per weight ``1 + 3 * len(configs)`` sums.  Two runs give
+    bit-equal blocks, and a network's part does not depend on the others.  The block is a torch tensor and outlives
+    ``close()``.  ``self.configs``: the configurations as (bit_weight, per_channel, signed) with the bit width as an int."""
+    _c = 'dfq_batch_error_plan'
+
+    def __init__(self, batch, configs):
+        try:
+            configs = [tuple(c) for c in configs]
+        except TypeError:
+            raise ValueError('error_plan: configs must be a sequence of (bit_weight, per_channel, signed)') from None
+        if not 1 <= len(configs) <= 4 or any(len(c) != 3 for c in configs):
+            raise ValueError('error_plan: one to four configurations (bit_weight, per_channel, signed), got {!r}'.format(configs))
+        checked = []
+        for bits, per_channel, signed in configs:
+            bits = _check_bits(bits, per_channel, 'bit_weight')
+            if signed and bits == 1:
+                raise ValueError('error_plan: signed with bit_weight 1 has qmax = 0')
+            checked.append((bits, bool(per_channel), bool(signed)))
+        super().__init__(batch)
+        g0 = batch.nets[0][0]
+        tt = tuple(batch.targ_type)
+        layers = [(key, layer.weight) for key, layer in g0.items() if type(layer) in tt]
+        if not layers:
+            raise ValueError('error_plan: the batch has no {} layer'.format(tt))
+        self.configs = checked
+        n_vals = 1 + 3 * len(checked)
+        entries, self._views = [], []          # (graph key, offset of the sums, numel)
+        for i, (key, w) in enumerate(layers):
+            rows = int(w.shape[0])
+            entries.append(_ffi.DfqBatchErrorTensor(batch._in_slot(key, 'weight', w), rows, w.numel() // rows, n_vals * i))
+            self._views.append((key, n_vals * i, w.numel()))
+        stride = n_vals * len(layers)
+        self.keys = [key for key, _ in layers]
+        self.n_nets, self.n_tensors = len(batch.nets), len(entries)
+        self.elements = sum(w.numel() for _, w in layers)               # weights per network, each read twice (8 B)
+        self.block = torch.zeros((self.n_nets, stride), dtype=torch.float64, device=batch.stage.device)
+        cfg = (_ffi.DfqBatchErrorConfig * len(checked))(*[_ffi.DfqBatchErrorConfig(b, int(s), int(pc), 0) for b, pc, s in checked])
+        self._create(((_ffi.DfqBatchErrorTensor * len(entries))(*entries), len(entries), cfg, len(checked)),
+                     self.block.data_ptr(), stride)
+
+    def errors(self, n, block=None):
+        """``OrderedDict[graph key -> dict]`` of network n: ``numel``, ``sum_sq_w`` = sum w^2 and, as float64 arrays with one
+        entry per configuration, ``sum`` = sum e, ``sum_abs`` = sum |e|, ``sum_sq`` = sum e^2.  One device-to-host copy
+        (of the network's part of the block); ``block``: a host copy of ``self.block`` the caller made already."""
+        row = (self.block[n].cpu() if block is None else block[n]).numpy()
+        out, k = OrderedDict(), len(self.configs)
+        for key, off, numel in self._views:
+            sums = row[off + 1:off + 1 + 3 * k].reshape(k, 3)
+            out[key] = {'numel': numel, 'sum_sq_w': float(row[off]), 'sum': sums[:, 0].copy(), 'sum_abs': sums[:, 1].copy(),
+                        'sum_sq': sums[:, 2].copy()}
+        return out
 
 
 class BatchAbsorbPlan(_BatchPlan):

@@ -543,6 +543,47 @@ void dfq_batch_table_plan_destroy(dfq_batch_table_plan* plan);
 /* kernel launches per run (2); the clear of the block in front of them is a memset */
 int32_t dfq_batch_table_plan_launches(const dfq_batch_table_plan* plan);
 
+/* Weight quantisation error of a whole batch of networks of one architecture (extension; the batch form of
+ * _quantize_error(param, num_bits, reduction, signed), dfq.py:8-25, for every weight of every network and up to four
+ * quantiser configurations from the same reads).  `tensors` lists the weights of the FIRST of `n_nets` networks; network
+ * n's copy of a tensor lies bases[n] - bases[0] bytes further.  A run reads every weight twice (ranges, then errors),
+ * writes no weight, and writes, for network n and tensor t, 1 + 3 * n_configs float64 values from
+ * out + n * stride + out_offset on: sum w^2, then for every configuration sum e, sum |e|, sum e^2 with
+ * e = fake_quant(w; qparams(min, max, num_bits, symmetric)) - w in float32 (dfq.py:15), (min, max) being the tensor's pair,
+ * or the row's for a `per_row` configuration: bit for bit the value dfq_batch_quant_plan_run would store, minus w.  A
+ * constant tensor or row takes the max(scale, 1e-8) branch of the recipe.  Every sum is a float64 accumulation of float32
+ * terms (e^2 and w^2 formed in float64, exactly) in an order of the plan's own that is fixed: two runs are bit-identical,
+ * network n's values do not depend on n_nets or on n's place in the batch, no floating-point atomic is used.  NaN is
+ * skipped by the ranges (the rule stated above); a tensor holding NaN gets NaN sums, nothing else does.  Nothing else in
+ * the block is touched.  A clear of the plan's own range words, then three launches (ranges, errors, a fold of the
+ * pieces' sums in rising order); no workgroup waits for another.  Offsets are in doubles from a network's part of the
+ * block; the slots of different tensors must not overlap (not checked).  create: DFQ_ERR_ARG (and dfq_last_error) for null
+ * or empty tables, n_configs outside 1..4, num_bits outside [2, 16] (per row) or [1, 30] (per tensor), symmetric with 1 bit,
+ * a null weight, rows <= 0 or row_len <= 0, a weight that is not 16-byte aligned, a null block, stride <= 0, an offset
+ * outside the stride, null bases, networks that are not 16-byte aligned to network 0.  Every tensor of network 0 must lie
+ * inside network 0's slot: nothing here can check that.  Synchronises (create only); run is asynchronous on `stream`. */
+typedef struct dfq_batch_error_plan dfq_batch_error_plan;
+typedef struct dfq_batch_error_tensor { /* addresses in network 0 */
+    const float* data;      /* the layer's weight [rows, row_len], only read                                        */
+    int64_t rows;
+    int64_t row_len;
+    int64_t out_offset;     /* doubles into a network's part of the block: 1 + 3 * n_configs sums                   */
+} dfq_batch_error_tensor;
+typedef struct dfq_batch_error_config {
+    int32_t num_bits;
+    int32_t symmetric;      /* the signed recipe                                                                     */
+    int32_t per_row;        /* ranges per output row instead of per tensor                                           */
+    int32_t pad;
+} dfq_batch_error_config;
+
+int dfq_batch_error_plan_create(const dfq_batch_error_tensor* tensors, int32_t n_tensors, const dfq_batch_error_config* configs,
+                                int32_t n_configs, const void* const* bases, int32_t n_nets, double* out, int64_t stride,
+                                dfq_batch_error_plan** out_plan);
+int dfq_batch_error_plan_run(dfq_batch_error_plan* plan, void* stream);
+void dfq_batch_error_plan_destroy(dfq_batch_error_plan* plan);
+/* kernel launches per run (3); the clear of the range words in front of them is a memset */
+int32_t dfq_batch_error_plan_launches(const dfq_batch_error_plan* plan);
+
 /* Analytic activation ranges of a whole batch of networks of one architecture (extension; set_quant_minmax,
  * utils/layer_transform.py:347-609, main_cls.py:188, for every network of a batch at once).  The caller walks the graph of
  * the FIRST network once (find_prev_bn, :299-344, and the branch grouping of :476-580) and hands over what the walk found
