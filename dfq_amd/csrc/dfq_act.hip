@@ -9,7 +9,7 @@
 //                         (layer_transform.py:407-418), optionally accumulated (residual adds);
 //   * dfq_moments_after_add   the same transform applied to an accumulated (mean, var) pair when the
 //                         add node itself is followed by a ReLU / ReLU6 (:533-540);
-//   * dfq_moment_range    min(mean - N*sd), max(mean + N*sd) with sd = sqrt(var + eps) (:571-573);
+//   * dfq_moment_range    min(mean - N*sd), max(mean + N*sd) with sd = sqrt(max(var + eps, 0)) (:571-573, sd_of);
 //   * dfq_bn_through_layer    a BN proxy vector pushed through a conv / linear layer that has no BN
 //                         of its own (case d, :451-466).
 // Float32 arithmetic in the reference's operation order; pdf / cdf in float64 rounded to float32.
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(kBlock) void moments_after_add_kernel(float* __rest
                                                                    int64_t n, int mode, float eps) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    const float sd = sqrtf(var[i] + eps);
+    const float sd = sd_of(var[i], eps);
     float m, v;
     moments_of(mode, sd, mean[i], m, v);                     // :533-540
     mean[i] = m;
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(kBlock) void moment_range_kernel(const float* __res
     __shared__ float sh[2 * (kBlock / kWave)];
     float mn = INFINITY, mx = -INFINITY;
     for (int64_t i = threadIdx.x; i < n; i += kBlock) {
-        const float nw = n_sigma * sqrtf(var[i] + eps);
+        const float nw = n_sigma * sd_of(var[i], eps);
         mn = nan_min(mean[i] - nw, mn);
         mx = nan_max(mean[i] + nw, mx);
     }

@@ -124,7 +124,7 @@ __global__ __launch_bounds__(kBlock) void act_range_kernel(ActArgs a) {
                 for (int t = s; t < e; ++t) {
                     const ActStepDev T = a.steps[t];
                     if (T.opcode == DFQ_ACT_MOM_RELU) {
-                        const float sd = sqrtf(var + a.eps);
+                        const float sd = sd_of(var, a.eps);
                         float m, v;
                         moments_of(T.relu_mode, sd, mean, m, v);                 // moments_after_add_kernel
                         mean = m;
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(kBlock) void act_range_kernel(ActArgs a) {
                         var = v;
                     }
                 }
-                const float nw = a.n_sigma * sqrtf(var + a.eps);                 // moment_range_kernel
+                const float nw = a.n_sigma * sd_of(var, a.eps);                 // moment_range_kernel
                 mn = nan_min(mean - nw, mn);
                 mx = nan_max(mean + nw, mx);
             }

@@ -26,6 +26,15 @@ __device__ __forceinline__ void block_minmax(float& mn, float& mx, float* sh) {
     for (int w = 1; w < kBlock / kWave; ++w) { mn = nan_min(mn, sh[2 * w]); mx = nan_max(mx, sh[2 * w + 1]); }
 }
 
+// sd = sqrt(var + eps) of an accumulated variance (:533-540, :571-573), the one statement of all four sites that take it.  The
+// float32 ReLU6 variance of a narrow channel on the ceiling (w = 1.04e-3, b = 5.99877: -6.8e-6, in truth 8.7e-7) cancels to a
+// number below -eps, and the reference's sqrt is NaN there: the whole quantiser's range.  The radicand is clamped at 0 -- by
+// a comparison, not fmaxf, so that a NaN variance still propagates.  Bit-identical to the reference wherever that is finite.
+__device__ __forceinline__ float sd_of(float var, float eps) {
+    const float r = var + eps;
+    return sqrtf((r < 0.0f) ? 0.0f : r);
+}
+
 // calculate_mean / calculate_var (:407-410)
 __device__ __forceinline__ void moments_relu(float w, float b, float& mean, float& var) {
     const float t = (-b) / w;

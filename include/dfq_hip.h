@@ -599,6 +599,7 @@ int32_t dfq_batch_error_plan_launches(const dfq_batch_error_plan* plan);
  *   MOM_ADD     mean += mean', var += var' of another BatchNorm (:521-531)
  *   MOM_RELU    (mean, var) of N(mean, var + eps) behind ReLU / ReLU6 (:533-540); what dfq_moments_after_add computes
  *   MOM_RANGE   (min, max) = (min_c mean - N sqrt(var + eps), max_c mean + N sqrt(var + eps)) (:571-573); dfq_moment_range
+ *               (both with var + eps clamped at 0, see dfq_moments_after_add)
  * A result is CONST alone, or RANGE followed by RANGE_CAT / RANGE_ONE / RANGE_DIV steps, or MOM followed by MOM_ADD /
  * MOM_RELU steps of the same channel count and closed by MOM_RANGE.  A RANGE* step with `source_weight >= 0` reads its two
  * vectors not from a BatchNorm but from SOURCES (case d, :451-466): a proxy vector pushed through a conv / linear layer that
@@ -903,9 +904,16 @@ int dfq_bn_ranges(const dfq_bn_range_req* reqs, int32_t n_reqs, float n_sigma, f
  * (2, :411-418), per channel; accumulate != 0 adds into mean/var (residual adds, :521-531). */
 int dfq_relu_moments(const float* weight, const float* bias, int64_t n, int32_t relu_mode, float* mean, float* var,
                      int32_t accumulate, void* stream);
-/* an add node followed by ReLU (1) / ReLU6 (2): (mean, var) <- moments(sqrt(var + eps), mean) (:533-540) */
+/* Convention for sd = sqrt(var + eps) in dfq_moments_after_add, dfq_moment_range and the MOM_RELU / MOM_RANGE steps of
+ * dfq_batch_act_plan_*: the radicand is clamped at 0, sd = sqrt(var + eps < 0 ? 0 : var + eps).  The float32 ReLU6 variance of
+ * a narrow channel on the ceiling cancels to a number below -eps (gamma~ = 1.04e-3, beta~ = 5.99877: -6.8e-6, in truth
+ * 8.7e-7), where the reference's sqrt is NaN and with it the quantiser's whole range.  Bit-identical to the reference
+ * wherever that is finite; a NaN variance still gives NaN.  dfq_relu_moments itself returns the variance as the reference
+ * computes it, negative values included. */
+/* an add node followed by ReLU (1) / ReLU6 (2): (mean, var) <- moments(sd, mean), sd as above (:533-540); other modes:
+ * DFQ_ERR_ARG */
 int dfq_moments_after_add(float* mean, float* var, int64_t n, int32_t relu_mode, float eps, void* stream);
-/* out2 = (min_c(mean - N*sqrt(var+eps)), max_c(mean + N*sqrt(var+eps))) (:571-573) */
+/* out2 = (min_c(mean - N*sd), max_c(mean + N*sd)), sd as above (:571-573); NaN propagates as in torch.min / torch.max */
 int dfq_moment_range(const float* mean, const float* var, int64_t n, float eps, float n_sigma, float* out2, void* stream);
 /* case (d), :455-463: a BN proxy vector pushed through a conv / linear layer without batch norm:
  * v_out[o] = sum_i (sum_k W[o,i,k]) * v_in[group(o)*I/g + i] + bias[o] (bias may be NULL) */

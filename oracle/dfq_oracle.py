@@ -707,6 +707,15 @@ def moments_relu6(weight, bias):
     return mean, var
 
 
+def moment_sd(var, eps):
+    """sqrt(var + eps) of layer_transform.py:534, :538, :571 in float32, the radicand clamped at 0: the float32 variance of
+    moments_relu6 can round below -eps (a narrow channel on the ReLU6 ceiling), where the reference's sqrt is NaN.  The
+    same values wherever the reference is finite; a NaN variance stays NaN."""
+    with np.errstate(invalid='ignore'):
+        r = (np.asarray(var, dtype=F32) + F32(eps)).astype(F32)
+        return np.sqrt(np.where(r < 0, F32(0), r)).astype(F32)
+
+
 def bn_value_range(bias, weight, n):
     """(get_min_value, get_max_value) of layer_transform.py:403-404 as Python floats."""
     b = np.asarray(bias, dtype=F32)
@@ -769,11 +778,9 @@ def set_quant_minmax(spec, is_detection=False, N=6, tensor_ops=None):
                     mean = (mean + m_t).astype(F32)
                     var = (var + v_t).astype(F32)
                     if 'relu6' in connect_type:
-                        sd = np.sqrt((var + F32(EPS)).astype(F32)).astype(F32)
-                        mean, var = moments_relu6(sd, mean)
+                        mean, var = moments_relu6(moment_sd(var, EPS), mean)
                     elif 'relu' in connect_type:
-                        sd = np.sqrt((var + F32(EPS)).astype(F32)).astype(F32)
-                        mean, var = moments_relu(sd, mean)
+                        mean, var = moments_relu(moment_sd(var, EPS), mean)
                 elif connect_type == 'cat':
                     lo, hi = _clamped_range(bias, weight, N, relu_t)
                     value_min = min(value_min, lo)
@@ -787,8 +794,7 @@ def set_quant_minmax(spec, is_detection=False, N=6, tensor_ops=None):
                 value_min /= (bound + 1)
                 value_max /= (bound + 1)
         if 'add' in connect_type:
-            sd = np.sqrt((var + F32(EPS)).astype(F32)).astype(F32)
-            return bn_value_range(mean, sd, N)
+            return bn_value_range(mean, moment_sd(var, EPS), N)
         return value_min, value_max
 
     for key in spec.order:
