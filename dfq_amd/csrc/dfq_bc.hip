@@ -142,31 +142,33 @@ __device__ __forceinline__ void bc_minmax_block(const BcLayerDev* __restrict__ l
         // 16-byte vectors over the aligned body of the chunk (chunk starts are multiples of 4 floats)
         const int64_t e4 = b + ((e - b) & ~(int64_t)3);
         // four independent 16-byte loads per trip (a read-only pass with one load in flight per lane leaves most of the
-        // memory pipeline idle), raw v_min / v_max (no canonicalisation prologue)
+        // memory pipeline idle), raw v_min / v_max on quieted values (a NaN of either kind is skipped, as dfq_tensor_minmax does)
         int64_t i = b + 4 * (int64_t)threadIdx.x;
         for (; i + 12 * kBlock < e4; i += 16 * kBlock) {
             fvec4 v[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) v[u] = kReadNt ? DFQ_NT_LOAD((const fvec4*)(L.w + i + u * 4 * kBlock)) : *(const fvec4*)(L.w + i + u * 4 * kBlock);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                mn = vmin_raw(vmin_raw(mn, v[u][0]), vmin_raw(v[u][1], vmin_raw(v[u][2], v[u][3])));
-                mx = vmax_raw(vmax_raw(mx, v[u][0]), vmax_raw(v[u][1], vmax_raw(v[u][2], v[u][3])));
+            for (int u = 0; u < 4; ++u) {                  // (straight from memory: quiet_nan, dfq_common.hpp)
+                const float x0 = quiet_nan(v[u][0]), x1 = quiet_nan(v[u][1]), x2 = quiet_nan(v[u][2]), x3 = quiet_nan(v[u][3]);
+                mn = vmin_raw(vmin_raw(mn, x0), vmin_raw(x1, vmin_raw(x2, x3)));
+                mx = vmax_raw(vmax_raw(mx, x0), vmax_raw(x1, vmax_raw(x2, x3)));
             }
         }
         for (; i < e4; i += 4 * kBlock) {
             const fvec4 v = *(const fvec4*)(L.w + i);
-            mn = vmin_raw(vmin_raw(mn, v[0]), vmin_raw(v[1], vmin_raw(v[2], v[3])));
-            mx = vmax_raw(vmax_raw(mx, v[0]), vmax_raw(v[1], vmax_raw(v[2], v[3])));
+            const float x0 = quiet_nan(v[0]), x1 = quiet_nan(v[1]), x2 = quiet_nan(v[2]), x3 = quiet_nan(v[3]);
+            mn = vmin_raw(vmin_raw(mn, x0), vmin_raw(x1, vmin_raw(x2, x3)));
+            mx = vmax_raw(vmax_raw(mx, x0), vmax_raw(x1, vmax_raw(x2, x3)));
         }
         for (int64_t i = e4 + threadIdx.x; i < e; i += kBlock) {
-            const float v = L.w[i];
+            const float v = quiet_nan(L.w[i]);
             mn = fminf(mn, v);
             mx = fmaxf(mx, v);
         }
     } else {
         for (int64_t i = b + threadIdx.x; i < e; i += kBlock) {
-            const float v = L.w[i];
+            const float v = quiet_nan(L.w[i]);
             mn = fminf(mn, v);
             mx = fmaxf(mx, v);
         }

@@ -262,7 +262,7 @@ __device__ __forceinline__ float quiet_nan(float v) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_canonicalizef(v);
 #else
-    return v;                            // fminf / fmaxf skip a NaN of either kind
+    return v != v ? __builtin_nanf("") : v;     // (the host's fminf / fmaxf RETURN a NaN for a signalling operand, like the raw instructions)
 #endif
 }
 __device__ __forceinline__ float vmin_raw(float a, float b) {

@@ -1468,16 +1468,17 @@ __global__ __launch_bounds__(kBlock) void le_bootstrap_kernel(const LeRelDev* __
 #pragma unroll
                     for (int u = 0; u < 8; ++u) v[u] = *(const fvec4*)(rows + (int64_t)min(r0 + u * n_rg, r_hi - 1) * R.row_len + pos);
 #pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        mn[u] = vmin_raw(vmin_raw(v[u][0], v[u][1]), vmin_raw(v[u][2], v[u][3]));
-                        mx[u] = vmax_raw(vmax_raw(v[u][0], v[u][1]), vmax_raw(v[u][2], v[u][3]));
+                    for (int u = 0; u < 8; ++u) {          // (straight from memory: quiet_nan, dfq_common.hpp)
+                        const float x0 = quiet_nan(v[u][0]), x1 = quiet_nan(v[u][1]), x2 = quiet_nan(v[u][2]), x3 = quiet_nan(v[u][3]);
+                        mn[u] = vmin_raw(vmin_raw(x0, x1), vmin_raw(x2, x3));
+                        mx[u] = vmax_raw(vmax_raw(x0, x1), vmax_raw(x2, x3));
                     }
                 } else {
                     float v[8];
 #pragma unroll
                     for (int u = 0; u < 8; ++u) v[u] = rows[(int64_t)min(r0 + u * n_rg, r_hi - 1) * R.row_len + pos];
 #pragma unroll
-                    for (int u = 0; u < 8; ++u) { mn[u] = v[u]; mx[u] = v[u]; }
+                    for (int u = 0; u < 8; ++u) { mn[u] = quiet_nan(v[u]); mx[u] = mn[u]; }
                 }
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
@@ -1504,15 +1505,16 @@ __global__ __launch_bounds__(kBlock) void le_bootstrap_kernel(const LeRelDev* __
                         for (int u = 0; u < 8; ++u) v[u] = *(const fvec4*)(row + 4 * min(p0 + u * G, npv - 1));
 #pragma unroll
                         for (int u = 0; u < 8; ++u) {          // positions past the row repeat its last vector: harmless
-                            mn = vmin_raw(vmin_raw(mn, v[u][0]), vmin_raw(v[u][1], vmin_raw(v[u][2], v[u][3])));
-                            mx = vmax_raw(vmax_raw(mx, v[u][0]), vmax_raw(v[u][1], vmax_raw(v[u][2], v[u][3])));
+                            const float x0 = quiet_nan(v[u][0]), x1 = quiet_nan(v[u][1]), x2 = quiet_nan(v[u][2]), x3 = quiet_nan(v[u][3]);
+                            mn = vmin_raw(vmin_raw(mn, x0), vmin_raw(x1, vmin_raw(x2, x3)));
+                            mx = vmax_raw(vmax_raw(mx, x0), vmax_raw(x1, vmax_raw(x2, x3)));
                         }
                     } else {
                         float v[8];
 #pragma unroll
                         for (int u = 0; u < 8; ++u) v[u] = row[min(p0 + u * G, npv - 1)];
 #pragma unroll
-                        for (int u = 0; u < 8; ++u) { mn = vmin_raw(mn, v[u]); mx = vmax_raw(mx, v[u]); }
+                        for (int u = 0; u < 8; ++u) { const float x = quiet_nan(v[u]); mn = vmin_raw(mn, x); mx = vmax_raw(mx, x); }
                     }
                 }
                 xor_lane_minmax<1>(mn, mx); xor_lane_minmax<2>(mn, mx); xor_lane_minmax<4>(mn, mx);
@@ -1553,13 +1555,13 @@ __global__ __launch_bounds__(kBlock) void le_bootstrap_kernel(const LeRelDev* __
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) { cmn[k] = vmin_raw(cmn[k], v[u][k]); cmx[k] = vmax_raw(cmx[k], v[u][k]); }
+                for (int k = 0; k < 4; ++k) { const float x = quiet_nan(v[u][k]); cmn[k] = vmin_raw(cmn[k], x); cmx[k] = vmax_raw(cmx[k], x); }
             }
         }
         for (; j < j_hi; j += n_rg) {
             const fvec4 v = *(const fvec4*)(colp + (int64_t)j * R.i2g);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) { cmn[k] = vmin_raw(cmn[k], v[k]); cmx[k] = vmax_raw(cmx[k], v[k]); }
+            for (int k = 0; k < 4; ++k) { const float x = quiet_nan(v[k]); cmn[k] = vmin_raw(cmn[k], x); cmx[k] = vmax_raw(cmx[k], x); }
         }
         if (on && j_lo + rg < j_hi) {
 #pragma unroll
@@ -1587,10 +1589,10 @@ __global__ __launch_bounds__(kBlock) void le_bootstrap_kernel(const LeRelDev* __
 #pragma unroll
                     for (int u = 0; u < 8; ++u) v[u] = col[(int64_t)(j + u * JL) * col_stride];
 #pragma unroll
-                    for (int u = 0; u < 8; ++u) { mn = fminf(mn, v[u]); mx = fmaxf(mx, v[u]); }
+                    for (int u = 0; u < 8; ++u) { const float x = quiet_nan(v[u]); mn = fminf(mn, x); mx = fmaxf(mx, x); }
                 }
                 for (; j < j_hi; j += JL) {
-                    const float v = col[(int64_t)j * col_stride];
+                    const float v = quiet_nan(col[(int64_t)j * col_stride]);
                     mn = fminf(mn, v); mx = fmaxf(mx, v);
                 }
                 if (mn <= mx) { atomicMax(&sh_mn2[ct], ~enc_ord(mn)); atomicMax(&sh_mx2[ct], enc_ord(mx)); }

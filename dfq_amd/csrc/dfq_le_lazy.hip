@@ -138,7 +138,7 @@ __device__ __forceinline__ void lz_rows(const float* __restrict__ w, int row_len
                 }
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) {
-                    const float y = x[u][k] * fk[k];
+                    const float y = quiet_nan(x[u][k] * fk[k]);         // (free behind a real product; a constant factor of 1 leaves the loaded value)
                     mn = vmin_raw(mn, y); mx = vmax_raw(mx, y);
                 }
                 if (++pi == npi) {                                     // the row is complete: reduce over its G lanes
@@ -199,7 +199,7 @@ __device__ __forceinline__ void lz_cols(const LzRel& R, const LzTile& T, const L
         for (int u = 0; u < kLzTrip; ++u) {                            // rows past the end are clamped duplicates: harmless
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
-                const float y = x[u][k] * f[u];
+                const float y = quiet_nan(x[u][k] * f[u]);
                 cmn[k] = vmin_raw(cmn[k], y); cmx[k] = vmax_raw(cmx[k], y);
             }
         }

@@ -273,10 +273,16 @@ __device__ __forceinline__ TileGeo tile_geo(const ResTile& T) {
     return G;
 }
 __device__ __forceinline__ float abs_f32(float d) { return __uint_as_float(__float_as_uint(d) & 0x7fffffffu); }
+// A NaN is skipped like everywhere else (include/dfq_hip.h, "NaN rule"): its order-preserving word would win the max slot
+// (positive NaN, above +inf) or the min slot (negative NaN), so a NaN end merges as the identity of its reduction (+inf for the
+// minimum, -inf for the maximum) instead -- that loses against every value and still leaves the word non-zero, i.e. "touched"
+// (publish_cols).  The accumulations in front of these merges start at the identities and skip NaN, so this only matters for
+// the single-value merges below; it costs two selects per merged pair, not per element.
 __device__ __forceinline__ void lds_minmax(uint32_t* pair, float mn, float mx) {
-    atomicMax(pair, ~enc_ord(mn));
-    atomicMax(pair + 1, enc_ord(mx));
+    atomicMax(pair, ~enc_ord(mn == mn ? mn : INFINITY));
+    atomicMax(pair + 1, enc_ord(mx == mx ? mx : -INFINITY));
 }
+__device__ __forceinline__ void lds_minmax_one(uint32_t* pair, float y) { lds_minmax(pair, y, y); }
 
 template <int VEC_>
 struct LayGeneral {
@@ -323,7 +329,7 @@ struct LayGeneral {
     // the value an element WILL have: fl(fl(w * 1/s_A) * s_B) with the factors in use (dfq.py:73 then :62, both rounded)
     __device__ __forceinline__ float val(const ResTile& T, const TileGeo& G, float w, bool useA, bool useB, const float* sh_inv,
                                          const float* sh_s, int row, int pos_k) const {
-        const float tt = useA ? w * sh_inv[tab(T, G, row, pos_k)] : w;
+        const float tt = useA ? w * sh_inv[tab(T, G, row, pos_k)] : quiet_nan(w);   // (the first statistics pass sees the loaded value itself)
         return useB ? tt * sh_s[row] : tt;
     }
     // row statistics of the (pending) values into sh_row (zeroed by the caller)
@@ -355,7 +361,7 @@ struct LayGeneral {
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
                 const float y = val(T, G, x[k], useA, useB, sh_inv, sh_s, row, pos + k);
-                lds_minmax(sh_col + 2 * tab(T, G, row, pos + k), y, y);
+                lds_minmax_one(sh_col + 2 * tab(T, G, row, pos + k), y);
             }
         });
     }
@@ -494,7 +500,7 @@ struct LayFixed {
                         double part = 0.0;
 #pragma unroll
                         for (int k = 0; k < 4; ++k) {
-                            const float y = (xv[k] * iv[k]) * sr;        // * 1.0f is exact
+                            const float y = quiet_nan((xv[k] * iv[k]) * sr);   // * 1.0f is exact -- and may be folded away: the loaded value itself (free behind a real product)
                             yv[k] = y;
                             if (kCommit) part += (double)abs_f32(y - xv[k]);
                             mn4[j] = vmin_raw(mn4[j], y); mx4[j] = vmax_raw(mx4[j], y);
@@ -520,7 +526,7 @@ struct LayFixed {
             double part = 0.0;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const float y = (xv[k] * iv[k]) * sr;                // * 1.0f is exact
+                const float y = quiet_nan((xv[k] * iv[k]) * sr);     // * 1.0f is exact (see above)
                 yv[k] = y;
                 if (kCommit) part += (double)abs_f32(y - xv[k]);
                 mn = vmin_raw(mn, y); mx = vmax_raw(mx, y);
@@ -622,7 +628,7 @@ struct LayFixed {
             double part = 0.0;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const float nv = (xv[k] * iv[k]) * sr;            // dfq.py:73 then :62, both rounded
+                const float nv = quiet_nan((xv[k] * iv[k]) * sr); // dfq.py:73 then :62, both rounded (quiet_nan: without factors the product may fold to the loaded value)
                 nw[k] = nv;
                 if (!(DFQ_RES_ABLATE & 1)) part += (double)abs_f32(nv - xv[k]);
                 if (!cols) {
@@ -632,7 +638,7 @@ struct LayFixed {
                     cmn[k] = vmin_raw(cmn[k], nv);
                     cmx[k] = vmax_raw(cmx[k], nv);
                 } else if (on) {
-                    lds_minmax(sh_col + 2 * (gr + tabk[k]), nv, nv);
+                    lds_minmax_one(sh_col + 2 * (gr + tabk[k]), nv);
                 }
             }
             if (commit) *(fvec4*)x = nw;                          // the thread's own slot (padded lanes hold private duplicates)
@@ -728,7 +734,7 @@ struct LayShort {
     __device__ __forceinline__ float fa_of(int j, bool useA, const float* sh_inv) const { return (useA && nci == 1) ? sh_inv[rt[j]] : 1.0f; }
     __device__ __forceinline__ float val(float w, int j, int e, bool useA, float fa, float fb, const float* sh_inv) const {
         const float ia = (useA && nci != 1) ? sh_inv[rt[j] + small_div(e, khkw)] : fa;
-        return (w * ia) * fb;                                        // dfq.py:73 (rounded), then dfq.py:62; * 1.0f is exact
+        return quiet_nan((w * ia) * fb);                             // dfq.py:73 (rounded), then dfq.py:62; * 1.0f is exact (and may fold: quiet_nan)
     }
     __device__ __forceinline__ void row_stats(const ResTile& T, const TileGeo& G, float* tile, bool useA, bool useB,
                                               const float* sh_inv, const float* sh_s, uint32_t* sh_row) const {
@@ -764,7 +770,7 @@ struct LayShort {
                     const float nv = val(x, j, e, useA, fa, fb, sh_inv);
                     part += (double)abs_f32(nv - x);
                     if (commit) base[e * kBlock] = nv;
-                    if (on && cols) lds_minmax(sh_col + 2 * (rt[j] + small_div(e, khkw)), nv, nv);
+                    if (on && cols) lds_minmax_one(sh_col + 2 * (rt[j] + small_div(e, khkw)), nv);
                 });
             }
             acc += on ? part : 0.0;

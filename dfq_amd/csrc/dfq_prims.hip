@@ -26,7 +26,7 @@ __global__ __launch_bounds__(kBlock) void row_range_kernel(const float* __restri
     const float* row = w + r * row_len;
     float mn = INFINITY, mx = -INFINITY;
     for (int64_t i = lane; i < row_len; i += kWave) {
-        const float v = row[i];
+        const float v = quiet_nan(row[i]);            // a NaN of either kind is skipped (include/dfq_hip.h, "NaN rule")
         mn = fminf(mn, v);
         mx = fmaxf(mx, v);
     }
@@ -49,7 +49,7 @@ __global__ __launch_bounds__(kBlock) void col_range_kernel(const float* __restri
     for (int j = 0; j < go; ++j) {
         const float* p = w2 + (((int64_t)g * go + j) * in_per_group + ii) * khkw;
         for (int k = 0; k < khkw; ++k) {
-            const float v = p[k];
+            const float v = quiet_nan(p[k]);
             mn = fminf(mn, v);
             mx = fmaxf(mx, v);
         }

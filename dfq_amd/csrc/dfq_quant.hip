@@ -58,13 +58,13 @@ __device__ __forceinline__ void thread_minmax_range(const float* __restrict__ x,
             fold_vec(p4[i], mn, mx);
         }
         for (int64_t i = (n4 << 2) + tid; i < len; i += kBlock) {
-            const float v = p[i];
+            const float v = quiet_nan(p[i]);             // (nothing on the GPU, where fminf canonicalises; the host's fminf returns a NaN for a signalling operand)
             mn = fminf(mn, v);
             mx = fmaxf(mx, v);
         }
     } else {
         for (int64_t i = tid; i < len; i += kBlock) {
-            const float v = p[i];
+            const float v = quiet_nan(p[i]);             // (nothing on the GPU, where fminf canonicalises; the host's fminf returns a NaN for a signalling operand)
             mn = fminf(mn, v);
             mx = fmaxf(mx, v);
         }

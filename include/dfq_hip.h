@@ -103,6 +103,15 @@ typedef struct dfq_le_result {
     double last_diff_tmp;      /* diff_tmp of the last sweep                                  */
 } dfq_le_result;
 
+/* NaN rule of the channel ranges (every dfq_le_* engine -- resident, streaming, free-running, lazy-scale -- and dfq_row_range /
+ * dfq_col_range / dfq_le_pair): a NaN of any sign or payload, quiet or signalling, takes no part in a channel's min / max, the
+ * rule of the quantisers' ranges ("Special values" below).  A channel with no non-NaN value gets S = s_hi and 1/S = inv_hi
+ * (dfq_row_range / dfq_col_range report -inf for it: the range of the reductions' identities +inf, -inf).  Infinities and
+ * denormals are ordinary values.  The NaN element itself stays NaN; the other elements of its row / column are scaled.
+ * torch's max() / min() in dfq.py:50-55 PROPAGATE a NaN instead -- the channel's range is NaN and S = s_hi: a documented
+ * divergence (one NaN weight does not cost a channel its scale); the oracle states both, channel_ranges(nan=...).
+ * The |dW| mean of a tensor that holds a NaN is NaN in every sweep; the loop's comparisons are the reference's (a NaN never
+ * resets `count`, the loop ends by converge_count). */
 /* Builds the device-side work list: dependency levels of the relation list (Gauss-Seidel order of
  * dfq.py:85 is preserved: of two relations sharing a layer the later one's tiles wait, inside the sweep's
  * single launch, for the tiles of the earlier one they depend on), channel tiles, the per-layer
@@ -842,10 +851,11 @@ int dfq_bias_absorb(const float* w2, int32_t o2, int32_t in_per_group, int32_t k
  * with the plans (same device arithmetic); they cost two passes over the data and four launches per
  * pair, so the plans are the fast path.  All pointers are device pointers, all calls asynchronous.
  * ---------------------------------------------------------------------------------------- */
-/* out[r] = range(W[r, :]): max-min (signed_range 0, dfq.py:54-55) or max|.| (1, dfq.py:50-51) */
+/* out[r] = range(W[r, :]): max-min (signed_range 0, dfq.py:54-55) or max|.| (1, dfq.py:50-51); NaN is skipped, a row of
+ * nothing but NaN gives -inf ("NaN rule of the channel ranges" at dfq_le_plan_create; torch's max() would propagate) */
 int dfq_row_range(const float* w, int64_t rows, int64_t row_len, int32_t signed_range, float* out, void* stream);
 /* out[g*I/g + ii] = range over the O/groups rows of pairing group g and the khkw taps of input channel ii
- * of W2 [O, I/g, khkw] (the view of dfq.py:41-46; `groups` = O1 / (I2/g), 1 for an ordinary pair) */
+ * of W2 [O, I/g, khkw] (the view of dfq.py:41-46; `groups` = O1 / (I2/g), 1 for an ordinary pair); NaN as in dfq_row_range */
 int dfq_col_range(const float* w2, int32_t out_ch, int32_t in_per_group, int32_t khkw, int32_t groups,
                   int32_t signed_range, float* out, void* stream);
 /* S[c] = clamp((1/(r1+eps)) * sqrt(r1*r2+eps)) with the Python max/min semantics of dfq.py:58-59 (NaN ->

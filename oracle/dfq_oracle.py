@@ -221,23 +221,37 @@ def le_solve(r1, r2, s_range=(1e-8, 1e8), eps=0):
     return s_out, inv
 
 
-def channel_ranges(a, signed):
+def channel_ranges(a, signed, nan='propagate'):
+    """Range of every channel (last axis).  nan='propagate' (the default): torch's max() / min(), a NaN anywhere makes the
+    channel's range NaN -- what the reference computes.  nan='skip': the rule of the HIP engines (include/dfq_hip.h, "NaN
+    rule"): a NaN of any sign or payload takes no part in min / max; a channel without a non-NaN value keeps the
+    reductions' identities (min = +inf, max = -inf), whose range makes le_solve return s_range's upper end."""
+    if nan == 'skip':
+        with np.errstate(invalid='ignore', over='ignore'):
+            gone = np.isnan(a)                           # (not np.fmin / np.fmax: the C library's return a NaN for a signalling operand)
+            mn = np.where(gone, F32(np.inf), a).min(-1).astype(F32)
+            mx = np.where(gone, F32(-np.inf), a).max(-1).astype(F32)
+            if signed:                                   # max |.| == max(mx, -mn); + 0 turns the -0 of an all-zero channel into abs()'s +0
+                return (np.maximum(mx, -mn) + F32(0.0)).astype(F32)
+            return (mx - mn).astype(F32)
+    assert nan == 'propagate', nan
     if signed:
         return np.abs(a).max(-1).astype(F32)
     return (a.max(-1) - a.min(-1)).astype(F32)
 
 
 def layer_equalization(w1, w2, b1, bn_weight=None, bn_bias=None, s_range=(1e-8, 1e8),
-                       signed=False, eps=0):
-    """In-place on the numpy arrays; returns S (float32 [O1])."""
+                       signed=False, eps=0, nan='propagate'):
+    """In-place on the numpy arrays; returns S (float32 [O1]).  `nan`: see channel_ranges."""
     a1, w2v, G, gi, go = _pair_views(w1, w2)
     O1 = a1.shape[0]
     # column of channel c=(g,ii): w2v[g, :, ii, :]
     cols = np.transpose(w2v, (0, 2, 1, 3)).reshape(O1, -1)   # copy [O1, go*khkw]
-    r1 = channel_ranges(a1, signed)
-    r2 = channel_ranges(cols, signed)
+    r1 = channel_ranges(a1, signed, nan)
+    r2 = channel_ranges(cols, signed, nan)
     s, inv = le_solve(r1, r2, s_range, eps)
-    a1 *= s[:, None]
+    with np.errstate(invalid='ignore', over='ignore'):
+        a1 *= s[:, None]
     if bn_weight is not None:
         bn_weight *= s
     if bn_bias is not None:
@@ -264,7 +278,7 @@ def layer_absdiff_mean(w, w_prev):
 
 def cross_layer_equalization(spec, relations, s_range=(1e-8, 1e8), converge_thres=2e-7,
                              converge_count=20, signed=False, eps=0, max_sweeps=None,
-                             trace=None):
+                             trace=None, nan='propagate'):
     """Runs on a GraphSpec in place.  relations: list of (first_key, second_key, bn_key).
 
     ``max_sweeps`` (extension; None = reference behaviour) caps the number of sweeps.
@@ -285,7 +299,7 @@ def cross_layer_equalization(spec, relations, s_range=(1e-8, 1e8), converge_thre
             if nf.bias is None:                                       # dfq.py:91-92
                 nf.bias = np.zeros(nf.weight.shape[0], dtype=F32)
             S = layer_equalization(nf.weight, ns.weight, nf.bias, nb.fake_weight, nb.fake_bias,
-                                   s_range=s_range, signed=signed, eps=eps)
+                                   s_range=s_range, signed=signed, eps=eps, nan=nan)
             S_cum[i] = S.copy() if S_cum[i] is None else (S_cum[i] * S).astype(F32)
         diff_tmp = 0.0
         for k in targ_keys:

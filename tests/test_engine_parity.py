@@ -23,8 +23,8 @@ from dfq_amd.utils import layer_transform as lt
 from dfq_amd.utils import quantize as q
 from dfq_amd.utils import relation as rel
 
-from common import (GOLD, NET_FIXTURES, TARG, F32, assert_bitexact, assert_close, compare_stage, load_inputs,
-                    load_stage, net_fixture, npy, snapshot)
+from common import (GOLD, LE_ENGINES, NET_FIXTURES, TARG, F32, _select_le_engine, assert_bitexact, assert_close, compare_stage,
+                    load_inputs, load_stage, net_fixture, npy, snapshot)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -241,42 +241,6 @@ def test_quantize_error_against_reference(engine, name):
 # ---------------------------------------------------------------------------------------------
 def _kat_names():
     return [str(n) for n in np.load(os.path.join(GOLD, 'kat_le_pairs.npz'))['names']]
-
-
-# the equalisation engines a single network can run on: the resident whole-loop launch; the streaming launch of one
-# workgroup per tile (what batched plans use); the opt-in streaming launch of persistent workgroups (DFQ_LE_PERSIST=1;
-# with 3 workgroups every workgroup walks several tiles and tiles wait for tiles of other workgroups)
-# 'streaming': the default streaming engine -- free-running segments on lean tiles, four sweeps per pass (dfq_le_cf.hpp), the other
-# layers on the general tiles; '-cf2' / '-cf8': other group depths; 'streaming-general': every layer on the general tiles
-# (DFQ_LE_CF=0); the persistent-workgroup variants of the general tiles run without free-running segments as well
-# 'streaming-fused': layers scaled along both axes are read once per sweep -- their row tiles merge the rows' statistics over the slabs
-# of a row block inside the launch (DFQ_LE_FUSE=1: the default of batched plans)
-LE_ENGINES = ['resident', 'resident-cf', 'streaming', 'streaming-cf2', 'streaming-cf8', 'streaming-bg2', 'streaming-bg4', 'streaming-bg8', 'streaming-general', 'streaming-fused', 'streaming-persistent', 'streaming-persistent-3wg']
-
-
-def _select_le_engine(monkeypatch, le_engine):
-    for k in ('DFQ_LE_RESIDENT', 'DFQ_LE_PERSIST', 'DFQ_LE_SWEEP_WGS', 'DFQ_LE_TILE_ELEMS', 'DFQ_LE_CF', 'DFQ_LE_CF_GROUP', 'DFQ_LE_CF_BG', 'DFQ_LE_FUSE', 'DFQ_RES_CF'):
-        monkeypatch.delenv(k, raising=False)
-    if le_engine.startswith('streaming-bg'):     # the lean launches in the background: two groups of look-ahead, a second stream (dfq_le_cf.hpp)
-        monkeypatch.setenv('DFQ_LE_CF_GROUP', le_engine[len('streaming-bg'):])
-        monkeypatch.setenv('DFQ_LE_CF_BG', '1')
-    if le_engine == 'resident-cf':              # closed-form column statistics of the chain ends (opt-in, dfq_le_resident.hip)
-        monkeypatch.setenv('DFQ_RES_CF', '1')
-    if le_engine == 'streaming-fused':
-        monkeypatch.setenv('DFQ_LE_FUSE', '1')
-    if not le_engine.startswith('resident'):
-        monkeypatch.setenv('DFQ_LE_RESIDENT', '0')
-    if le_engine.startswith('streaming-cf'):
-        monkeypatch.setenv('DFQ_LE_CF_GROUP', le_engine[len('streaming-cf'):])
-    if le_engine in ('streaming', 'streaming-fused'):
-        monkeypatch.setenv('DFQ_LE_CF_GROUP', '4')    # (the default of a LARGE single network; a small one keeps the general tiles)
-    if le_engine == 'streaming-general' or le_engine.startswith('streaming-persistent'):
-        monkeypatch.setenv('DFQ_LE_CF', '0')
-    if le_engine.startswith('streaming-persistent'):
-        monkeypatch.setenv('DFQ_LE_PERSIST', '1')
-        monkeypatch.setenv('DFQ_LE_TILE_ELEMS', '1024')     # enough tiles for workgroups to walk several (the result does not depend on it)
-    if le_engine == 'streaming-persistent-3wg':
-        monkeypatch.setenv('DFQ_LE_SWEEP_WGS', '3')
 
 
 @pytest.mark.parametrize('name', _kat_names())
