@@ -296,6 +296,9 @@ SIGNATURES = {
     'dfq_bn_stat_loss_backward_dev': (c_int32, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_float, c_float, c_void_p,
                                                 c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
     'dfq_bn_through_layer': (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dfq_channel_sum_scratch_bytes': (c_size_t, [c_int64, c_int64, c_int64]),
+    'dfq_channel_sum_accumulate': (c_int32, [c_void_p, c_int64, c_int64, c_int64, c_double, c_void_p, c_void_p, c_void_p]),
+    'dfq_bias_sub_channel_delta': (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_double, c_void_p]),
 }
 
 

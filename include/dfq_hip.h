@@ -957,6 +957,27 @@ int dfq_bn_stat_loss_backward_dev(const float* x, int64_t rows, int64_t hw, int3
                                   const float* bn_std, float eps, float denom, const float* row_mean, const float* row_std,
                                   const float* grad_pair, float* grad_x, int32_t accumulate, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Empirical bias correction on distilled data -- improve_dfq.py:311-371 (bias_correction_distill): the per-channel sums of
+ * a hooked output, reduced on the device the moment the hook sees it, and the bias update made of them.
+ * ---------------------------------------------------------------------------------------- */
+/* improve_dfq.py:349-355 (`outputs.mean(0)` per batch, summed over the batches) and :365 (`.sum(-1)` over H*W), in one
+ * read of x [n_samples, channels, hw] (contiguous float32, 16-byte aligned; row r has hw floats and channel r % channels):
+ *   acc[c] = acc[c] + weight * sum_n sum_hw x[n, c, hw]
+ * in float64 from the first addition on; weight = 1 / n_samples is the reference's mean(0).  No floating-point atomic: the
+ * order of the additions depends on (n_samples, channels, hw) alone, so two runs are bit-equal wherever x lies.  NaN and
+ * +-inf are data: they reach the sum of their own channel and no other.  `scratch` is device memory of
+ * dfq_channel_sum_scratch_bytes(n_samples, channels, hw) bytes (0 for a shape the call refuses), 8-byte aligned; its
+ * contents need not survive the call.  DFQ_ERR_ARG: a null pointer, a size < 1, x not 16-byte or acc / scratch not 8-byte
+ * aligned, hw above 2^31 - 2^14 or more than 2^31 - 1 pieces of 4096 floats. */
+size_t dfq_channel_sum_scratch_bytes(int64_t n_samples, int64_t channels, int64_t hw);
+int dfq_channel_sum_accumulate(const float* x, int64_t n_samples, int64_t channels, int64_t hw, double weight, double* acc,
+                               void* scratch, void* stream);
+/* improve_dfq.py:361-368: bias[c] = bias[c] - (float)((acc_q[c] - acc_ref[c]) * scale) -- the difference and the product
+ * in float64, ONE rounding of the shift to float32, then ONE float32 subtraction (`module.bias.add_(-error)`). */
+int dfq_bias_sub_channel_delta(float* bias, const double* acc_q, const double* acc_ref, int64_t channels, double scale,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif
