@@ -299,6 +299,8 @@ SIGNATURES = {
     'dfq_channel_sum_scratch_bytes': (c_size_t, [c_int64, c_int64, c_int64]),
     'dfq_channel_sum_accumulate': (c_int32, [c_void_p, c_int64, c_int64, c_int64, c_double, c_void_p, c_void_p, c_void_p]),
     'dfq_bias_sub_channel_delta': (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_double, c_void_p]),
+    'dfq_act_hist_accumulate': (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
+    'dfq_hist_clip_range': (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_double, c_int32, c_void_p, c_void_p]),
 }
 
 

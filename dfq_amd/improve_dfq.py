@@ -328,3 +328,239 @@ def bias_correction_distill(qmodel, model_original, data, targ_type, targ_type_o
         for h in handles:
             h.remove()
     return qmodel
+
+
+class HistogramMeter:
+    """A forward PRE-hook for a QuantMeasure -- it sees the quantiser's input -- that reduces what it sees instead of keeping
+    it, the sibling of ChannelSumMeter.  Two phases, switched by assigning ``meter.phase``:
+
+      'range'  folds the tensor's true (min, max) into ``range2`` (dfq_tensor_minmax, then fmin / fmax on the device: a NaN
+               is skipped, the house rule of include/dfq_hip.h);
+      'count'  adds the tensor's histogram over ``range2`` to ``counts`` (dfq_act_hist_accumulate; the slot rule is in
+               include/dfq_hip.h).
+
+        meter = HistogramMeter(bins=2048)               # or HistogramMeter(range2, counts): slices of tables of yours
+        handle = layer.quant.register_forward_pre_hook(meter.hook)
+        for b in data: model(b)
+        meter.phase = 'count'
+        for b in data: model(b)
+        handle.remove()
+        prims.hist_clip_range(meter.counts, meter.range2, num_bits=8)
+
+    ``range2`` is a float32 [2] on the device, (+inf, -inf) before the first tensor; ``counts`` an int64 [bins + 3] (the bins,
+    then below, above, nan; the library's uint64).  Nothing is kept of the activation, nothing is copied to the host and nothing
+    waits.  An input that is not float32, not contiguous, on another device or not 16-byte aligned is copied first."""
+
+    def __init__(self, range2=None, counts=None, bins=2048, phase='range', scratch=None):
+        bins = int(bins)
+        if not 2 <= bins <= 4096:
+            raise ValueError('HistogramMeter: bins is 2 ... 4096, not {}'.format(bins))
+        if range2 is not None and (range2.dtype is not torch.float32 or range2.dim() != 1 or range2.numel() != 2 or not range2.is_contiguous()):
+            raise ValueError('HistogramMeter: range2 is a contiguous float32 vector [2]')
+        if counts is not None and (counts.dtype is not torch.int64 or counts.dim() != 1 or counts.numel() != bins + 3
+                                   or not counts.is_contiguous()):
+            raise ValueError('HistogramMeter: counts is a contiguous int64 vector [bins + 3]')
+        self.bins = bins
+        self.range2 = range2
+        self.counts = counts
+        self.phase = phase
+        self.calls = 0
+        self._scratch = scratch          # (float32 [2], int32 [2]) of dfq_tensor_minmax, shared by the meters of one pass
+        self._rows = None                # clip_quant_range: a float32 [calls, 2] table, one (min, max) per call of pass A
+        self._row = 0
+        self._dev = _ffi.target_device()
+        self._lib = _ffi.lib()
+
+    def hook(self, module, inputs):
+        self.add(inputs[0])
+
+    def range_rows(self, rows):
+        """Pass A without a torch operation per call: the (min, max) of call i goes to rows[i] (float32 [calls, 2] on the device,
+        (+inf, -inf) where nothing was written) and the caller folds the rows itself; calls beyond the table fold into
+        ``range2`` as usual."""
+        self._rows, self._row = rows, 0
+
+    def add(self, x):
+        if self.phase not in ('range', 'count'):
+            raise ValueError("HistogramMeter: phase is 'range' or 'count', not {!r}".format(self.phase))
+        if not torch.is_tensor(x):
+            raise TypeError('HistogramMeter: the hooked input is a tensor, not {}'.format(type(x).__name__))
+        dev = self._dev
+        with torch.no_grad():
+            if self.range2 is None:
+                self.range2 = torch.tensor([float('inf'), float('-inf')], dtype=torch.float32).to(dev)
+            if self.counts is None:
+                self.counts = torch.zeros(self.bins + 3, dtype=torch.int64, device=dev)
+            if self.range2.device != dev or self.counts.device != dev:
+                raise ValueError('HistogramMeter: range2 and counts live on {}'.format(dev))
+            if x.numel() == 0:
+                return
+            x = x.detach()
+            if x.device != dev or x.dtype is not torch.float32:
+                x = x.to(device=dev, dtype=torch.float32)
+            x = x.contiguous()
+            if x.data_ptr() % 16:
+                x = x.clone()                               # (a view into the middle of a buffer: the kernel's loads are 16-byte)
+            lib = self._lib
+            if self.phase == 'range':
+                if self._scratch is None or self._scratch[0].device != dev:
+                    self._scratch = (torch.empty(2, dtype=torch.float32, device=dev), torch.zeros(2, dtype=torch.int32, device=dev))
+                out, words = self._scratch
+                if self._rows is not None and self._row < self._rows.shape[0]:
+                    _ffi.check(lib.dfq_tensor_minmax(_ffi.ptr(x), x.numel(), self._rows.data_ptr() + 8 * self._row, _ffi.ptr(words),
+                                                     _ffi.stream_arg()))
+                    self._row += 1
+                else:
+                    _ffi.check(lib.dfq_tensor_minmax(_ffi.ptr(x), x.numel(), _ffi.ptr(out), _ffi.ptr(words), _ffi.stream_arg()))
+                    torch.fmin(self.range2[0:1], out[0:1], out=self.range2[0:1])
+                    torch.fmax(self.range2[1:2], out[1:2], out=self.range2[1:2])
+            else:
+                _ffi.check(lib.dfq_act_hist_accumulate(_ffi.ptr(x), x.numel(), _ffi.ptr(self.range2), self.bins, _ffi.ptr(self.counts),
+                                                       _ffi.stream_arg()))
+        self.calls += 1
+
+
+def _data_fed_quantisers(graph, bottoms):
+    """the QuantMeasure of every node fed by 'Data' (update_quant_range pins the same ones)"""
+    pinned = []
+    for key in graph:
+        bot = bottoms[key]
+        first = graph[key].quant if hasattr(graph[key], 'quant') else (graph[key] if isinstance(graph[key], QuantMeasure) else None)
+        if bot is not None and bot[0] == 'Data' and first is not None:
+            pinned.append(first)
+    return pinned
+
+
+def clip_quant_range(model, data, graph, bottoms, method='mse', percentile=0.9999, bins=2048, candidates=None, is_detection=False,
+                     group=None, report=None):
+    """Replace the range of every activation quantiser (QuantMeasure) of ``model`` by a CLIPPED range taken from the histogram
+    of its input over the batches of ``data``: method='mse', the range of least modelled quantisation error at the quantiser's
+    own ``num_bits``, or method='percentile', the central ``percentile`` of the mass on either side (the definitions:
+    dfq_hist_clip_range, include/dfq_hip.h).  An extension: the reference's ranges are min / max rules (the analytic
+    beta +- 6 gamma of set_quant_minmax, the running extrema of update_quant_range), which cannot trade clipping error against
+    rounding error -- what counts below 8 bits and on the heavy-tailed inputs of add / cat nodes.
+
+    Call it after update_quant_range or set_quant_minmax, with ``update_stat`` off (refused otherwise).  The model is taken as
+    it stands: during both passes the activations are quantised with the ranges the model HAS, and all ranges are replaced
+    together at the end.  The procedure is ONE-SHOT: the histograms are those of the inputs under the old ranges, and a second
+    call would see other inputs; it is not iterated to a fixed point here.
+
+      pass A  every batch, the hooks (HistogramMeter) in 'range': each quantiser's true (min, max), NaN skipped;
+      pass B  every batch again, the hooks in 'count': the histogram of each quantiser over its own (min, max), ``bins`` bins,
+              into ONE int64 table on the device;
+      then ONE dfq_hist_clip_range launch for all quantisers, each with its own num_bits, and the results are copied into
+      running_min / running_max on the device (the buffers keep their identity and their shape [1]).
+
+    Nothing is kept of an activation, and nothing is copied to the host or waited for inside the loops.  The quantiser fed by
+    'Data' is pinned as update_quant_range pins it (2.64 / -2.11790393, or +-1 with ``is_detection``), not searched.
+
+    ``report``: a dict that receives, per quantiser (keyed by its module name), 'hist_range' (float32 [2]), 'counts' (int64
+    [bins + 3]: the bins, below, above, nan), 'old_range' and 'new_range' -- device tensors, nothing is waited for -- and
+    'pinned'; a pinned quantiser has the two ranges only.
+
+    ``group`` (as update_quant_range's and bias_correction_distill's): a torch.distributed process group whose ranks hold the
+    same model.  Rank r runs batches r, r + world, ...; ONE all_reduce (MAX of (max, -min)) of the range table follows pass A
+    and ONE all_reduce(SUM) of the int64 count table pass B.  Extrema are selections and counts are integers, so -- unlike the
+    two siblings -- the sharded result is BIT-IDENTICAL to the sequential one, histograms and ranges."""
+    import torch.distributed as dist
+    from . import prims
+    if method not in prims.HIST_METHODS:
+        raise ValueError("clip_quant_range: method is 'mse' or 'percentile', not {!r}".format(method))
+    bins = int(bins)
+    if not 2 <= bins <= prims.HIST_MAX_BINS:
+        raise ValueError('clip_quant_range: bins is 2 ... {}, not {}'.format(prims.HIST_MAX_BINS, bins))
+    if method == 'percentile' and not 0.5 < float(percentile) <= 1.0:
+        raise ValueError('clip_quant_range: percentile is in (0.5, 1], not {}'.format(percentile))
+    if method == 'mse' and candidates is not None and not 1 <= int(candidates) <= bins // 2:
+        raise ValueError('clip_quant_range: candidates is 1 ... bins // 2 = {}, not {}'.format(bins // 2, candidates))
+    world = dist.get_world_size(group) if group is not None else 1
+    rank = dist.get_rank(group) if group is not None else 0
+    dev = _ffi.target_device()
+    named, seen = [], set()
+    for name, m in model.named_modules():
+        if isinstance(m, QuantMeasure) and id(m) not in seen:
+            seen.add(id(m))
+            named.append((name, m))
+    pinned = _data_fed_quantisers(graph, bottoms)
+    pinned_ids = {id(q) for q in pinned}
+    for name, m in named:
+        if m.update_stat:
+            raise ValueError('clip_quant_range: {} still has update_stat on (set_update_stat(model, [QuantMeasure], False) first)'.format(name))
+    searched = [(name, m) for name, m in named if id(m) not in pinned_ids]
+    for name, m in searched:
+        if not 2 <= int(m.num_bits) <= 16:
+            raise ValueError('clip_quant_range: {} has num_bits = {} (2 ... 16)'.format(name, m.num_bits))
+    n_q = len(searched)
+    with torch.no_grad():
+        def current(m):
+            return torch.cat([m.running_min.detach().reshape(1).to(dev), m.running_max.detach().reshape(1).to(dev)])
+        old = {id(m): current(m) for _, m in named}
+        range_table = torch.tensor([float('inf'), float('-inf')], dtype=torch.float32).repeat(max(n_q, 1), 1).to(dev)
+        count_table = torch.zeros((max(n_q, 1), bins + 3), dtype=torch.int64, device=dev)
+        scratch = (torch.empty(2, dtype=torch.float32, device=dev), torch.zeros(2, dtype=torch.int32, device=dev))
+        meters = [HistogramMeter(range_table[i], count_table[i], bins, 'range', scratch) for i in range(n_q)]
+        try:
+            n_local = len(range(rank, len(data), world))
+        except TypeError:                                   # (an iterable without a length: the meters fold call by call)
+            n_local = 0
+        rows = torch.tensor([float('inf'), float('-inf')], dtype=torch.float32).repeat(max(n_q, 1), max(n_local, 1), 1).to(dev)
+        if n_local:
+            for i, meter in enumerate(meters):
+                meter.range_rows(rows[i])                   # pass A: one (min, max) per batch, folded below -- no torch op per hook
+        handles = []
+        try:
+            for (_, m), meter in zip(searched, meters):
+                handles.append(m.register_forward_pre_hook(meter.hook))
+            params = list(model.parameters())
+            mdev = params[0].device if params else dev
+            for phase in ('range', 'count'):
+                for meter in meters:
+                    meter.phase = phase
+                for i, batch in enumerate(data):
+                    if i % world != rank:
+                        continue
+                    model(batch.to(mdev))
+                if phase == 'range' and n_q:
+                    # the batches' extrema into the range table, NaN skipped (a tensor of nothing but NaN has (NaN, NaN))
+                    lo, hi = rows[:, :, 0], rows[:, :, 1]
+                    lo = torch.where(torch.isnan(lo), torch.full_like(lo, float('inf')), lo).amin(dim=1)
+                    hi = torch.where(torch.isnan(hi), torch.full_like(hi, float('-inf')), hi).amax(dim=1)
+                    range_table[:, 0].copy_(torch.fmin(range_table[:, 0], lo))
+                    range_table[:, 1].copy_(torch.fmax(range_table[:, 1], hi))
+                if world > 1 and n_q:
+                    if phase == 'range':
+                        table = torch.stack([range_table[:, 1], -range_table[:, 0]], dim=1)       # max and -min: ONE reduction (MAX)
+                        comm = table if dist.get_backend(group) == 'nccl' else table.cpu()
+                        dist.all_reduce(comm, op=dist.ReduceOp.MAX, group=group)
+                        comm = comm.to(dev)
+                        range_table[:, 1].copy_(comm[:, 0])
+                        range_table[:, 0].copy_(-comm[:, 1])
+                    else:
+                        comm = count_table if dist.get_backend(group) == 'nccl' else count_table.cpu()
+                        dist.all_reduce(comm, op=dist.ReduceOp.SUM, group=group)
+                        count_table.copy_(comm)
+        finally:
+            for h in handles:
+                h.remove()
+        if n_q:
+            new = prims.hist_clip_range(count_table, range_table, [int(m.num_bits) for _, m in searched], method=method,
+                                        percentile=percentile, candidates=candidates)
+            for i, (_, m) in enumerate(searched):
+                m.running_min.copy_(new[i, 0:1].to(m.running_min.device))
+                m.running_max.copy_(new[i, 1:2].to(m.running_max.device))
+        for q in pinned:
+            if is_detection:
+                q.running_max.fill_(1.0)
+                q.running_min.fill_(-1.0)
+            else:
+                q.running_max.fill_(2.64)
+                q.running_min.fill_(-2.11790393)
+        if isinstance(report, dict):
+            index = {id(m): i for i, (_, m) in enumerate(searched)}
+            for name, m in named:
+                entry = {'old_range': old[id(m)], 'new_range': current(m), 'pinned': id(m) in pinned_ids}
+                if id(m) in index:
+                    entry['hist_range'] = range_table[index[id(m)]]
+                    entry['counts'] = count_table[index[id(m)]]
+                report[name] = entry
+    return model

@@ -148,3 +148,92 @@ def grouped_matvec(eps, expect, groups=1):
         _ffi.check(lib.dfq_grouped_matvec(_ffi.ptr(e), _ffi.ptr(x), e.shape[0], e.shape[1], int(groups), _ffi.ptr(out),
                                           _ffi.stream_arg()))
         return stage.out_like(eps, out)
+
+
+HIST_MAX_BINS = 4096          # kHistMaxBins of dfq_act_hist.hip
+HIST_METHODS = {'percentile': 0, 'mse': 1}
+
+
+def _device_f32(t, dev):
+    """float32, contiguous, on the engine's device -- the tensor itself when it already is"""
+    if not torch.is_tensor(t):
+        t = torch.tensor(t, dtype=torch.float32)
+    t = t.detach()
+    if t.device != dev or t.dtype is not torch.float32:
+        t = t.to(device=dev, dtype=torch.float32)
+    return t.contiguous()
+
+
+def act_histogram(x, range2, bins=2048, counts=None):
+    """counts[slot] += 1 for every element of `x` over the range (lo, hi) = `range2`, by dfq_act_hist_accumulate (the slot
+    rule: include/dfq_hip.h) -> int64 [bins + 3] on the engine's device: the bins, then below, above, nan.  The counts are the
+    library's uint64 (torch reduces and communicates int64; a count stays far below 2^63).
+
+    ``range2``: a float32 [2] tensor -- read on the device, nothing waits for it -- or a pair of numbers.  ``counts``: a
+    contiguous int64 [bins + 3] tensor on the engine's device to add to (a slice of a table of yours); None makes a zeroed one.
+    An `x` that is not float32, not contiguous, on another device or not 16-byte aligned is copied first."""
+    bins = int(bins)
+    if not 2 <= bins <= HIST_MAX_BINS:
+        raise ValueError('act_histogram: bins is 2 ... {}, not {}'.format(HIST_MAX_BINS, bins))
+    lib = _ffi.lib()
+    dev = _ffi.target_device()
+    with torch.no_grad():
+        if counts is None:
+            counts = torch.zeros(bins + 3, dtype=torch.int64, device=dev)
+        if (counts.dtype is not torch.int64 or counts.dim() != 1 or counts.numel() != bins + 3 or not counts.is_contiguous()
+                or counts.device != dev):
+            raise ValueError('act_histogram: counts is a contiguous int64 vector [bins + 3] on {}'.format(dev))
+        r = _device_f32(range2, dev).reshape(-1)
+        if r.numel() != 2:
+            raise ValueError('act_histogram: range2 is (lo, hi)')
+        xx = _device_f32(x, dev)
+        if xx.data_ptr() % 16:
+            xx = xx.clone()                                 # (a view into the middle of a buffer: the kernel's loads are 16-byte)
+        _ffi.check(lib.dfq_act_hist_accumulate(_ffi.ptr(xx), xx.numel(), _ffi.ptr(r), bins, _ffi.ptr(counts), _ffi.stream_arg()))
+    return counts
+
+
+def hist_clip_range(counts, range2, num_bits=8, method='mse', percentile=0.9999, candidates=None):
+    """The clipped range of one histogram ([bins + 3] counts, [2] range -> float32 [2]) or of several in ONE launch
+    ([n, bins + 3], [n, 2] -> [n, 2]) by dfq_hist_clip_range; the definitions are in include/dfq_hip.h.
+
+    ``method``: 'mse' searches ``candidates`` (default bins // 2) edges from each end for the range of least modelled
+    quantisation error at ``num_bits``; 'percentile' keeps the central ``percentile`` of the mass on either side.
+    ``num_bits``: one width in [2, 16] for all histograms, or one per histogram (a sequence or an integer tensor; a tensor on
+    the engine's device is validated by the caller, not here: reading it would wait for the device)."""
+    if method not in HIST_METHODS:
+        raise ValueError("hist_clip_range: method is 'mse' or 'percentile', not {!r}".format(method))
+    lib = _ffi.lib()
+    dev = _ffi.target_device()
+    with torch.no_grad():
+        single = counts.dim() == 1
+        c = counts.detach()
+        if c.dtype is not torch.int64:
+            raise ValueError('hist_clip_range: counts is int64 (the table act_histogram fills)')
+        c = c.to(dev).contiguous().reshape(1 if single else c.shape[0], -1)
+        n_hist, bins = int(c.shape[0]), int(c.shape[1]) - 3
+        if not 2 <= bins <= HIST_MAX_BINS:
+            raise ValueError('hist_clip_range: counts is [..., bins + 3] with 2 ... {} bins'.format(HIST_MAX_BINS))
+        r = _device_f32(range2, dev).reshape(-1, 2)
+        if r.shape[0] != n_hist:
+            raise ValueError('hist_clip_range: {} ranges for {} histograms'.format(r.shape[0], n_hist))
+        if torch.is_tensor(num_bits) and num_bits.device == dev and dev.type == 'cuda':
+            bits = num_bits.to(torch.int32).contiguous().reshape(-1)
+        else:
+            if torch.is_tensor(num_bits):
+                num_bits = num_bits.reshape(-1).tolist()
+            host = [int(b) for b in num_bits] if hasattr(num_bits, '__len__') else [int(num_bits)]
+            if len(host) == 1:
+                host = host * n_hist
+            if any(b < 2 or b > 16 for b in host):
+                raise ValueError('hist_clip_range: num_bits is 2 ... 16, not {}'.format(sorted(set(host))))
+            bits = torch.tensor(host, dtype=torch.int32).to(dev)
+        if bits.numel() != n_hist:
+            raise ValueError('hist_clip_range: {} bit widths for {} histograms'.format(bits.numel(), n_hist))
+        if candidates is None:
+            candidates = bins // 2
+        out = torch.empty((n_hist, 2), dtype=torch.float32, device=dev)
+        _ffi.check(lib.dfq_hist_clip_range(_ffi.ptr(c), _ffi.ptr(r), n_hist, bins, _ffi.ptr(bits), HIST_METHODS[method],
+                                           float(percentile), int(candidates), _ffi.ptr(out), _ffi.stream_arg()))
+        out = out.to(counts.device) if out.device != counts.device else out
+    return out[0] if single else out

@@ -978,6 +978,49 @@ int dfq_channel_sum_accumulate(const float* x, int64_t n_samples, int64_t channe
 int dfq_bias_sub_channel_delta(float* bias, const double* acc_q, const double* acc_ref, int64_t channels, double scale,
                                void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Clipped activation ranges from distilled data (extension: the reference has min / max rules only): the histogram of a
+ * quantiser's input, reduced on the device the moment a hook sees it, and the percentile / MSE-optimal range read off it.
+ * ---------------------------------------------------------------------------------------- */
+/* counts[slot(x[i])] += 1 for every i < n, in one read of x (contiguous float32, 16-byte aligned).  `range2` is a DEVICE
+ * float32[2] = (lo, hi): nothing is read on the host and nothing waits.  `counts` is a device uint64[bins + 3]: the bins,
+ * then `below` (slot bins), `above` (bins + 1) and `nan` (bins + 2); the call ADDS to it, the caller clears it.
+ * The slot of an element, in float32 with no contraction:
+ *     w = hi - lo;  degenerate := not (w is finite and w > 0)
+ *     x is NaN (either sign, quiet or signalling)  ->  nan
+ *     degenerate:  x < lo -> below;  x > hi -> above;  else bin 0
+ *     otherwise:   inv = (float)bins / w            (IEEE division)
+ *                  t   = (x - lo) * inv             (one subtraction, one multiplication)
+ *                  t < 0            -> below
+ *                  t >= (float)bins -> x <= hi ? bin bins - 1 : above
+ *                  else             -> bin (int)t   (truncation; t is NaN only when bins / w overflowed and x == lo: bin 0)
+ * So +-inf land in above / below, denormals and -0.0 are ordinary values, lo > hi and a width that overflows ((-3e38, 3e38))
+ * are degenerate, and the sum over all bins + 3 slots grows by exactly n per call.  Counts are integers added with integer
+ * atomics: the result does not depend on the order of the additions and is bit-equal from run to run.
+ * n == 0 is a no-op (x may then be null: an empty tensor has no address).  DFQ_ERR_ARG: a null pointer, bins outside [2, 4096], n < 0 or more than 2^31 - 1 pieces of 131072
+ * floats, x not 16-byte aligned (the Python layer copies such a view), range2 not 4-byte or counts not 8-byte aligned. */
+int dfq_act_hist_accumulate(const float* x, int64_t n, const float* range2, int32_t bins, unsigned long long* counts,
+                            void* stream);
+/* The clipped range of n_hist histograms in ONE launch: counts[n_hist][bins + 3] (layout above), range2[n_hist][2] the
+ * (lo, hi) they were counted over, num_bits[n_hist] (device int32), out2[n_hist][2] (device float32).
+ *     n_b     = counts[b], `below` added to bin 0 and `above` to bin bins - 1; NaN is ignored.  total = sum n_b
+ *     edge(b) = f32(lo + b (hi - lo) / bins) in float64, edge(0) = lo and edge(bins) = hi exactly
+ *     rep(b)  = f32(lo + (b + 1/2)(hi - lo) / bins), but rep(0) = lo and rep(bins - 1) = hi: the point masses of ReLU and
+ *               ReLU6 sit exactly on the extrema
+ * method 0, percentile, param = p in (0.5, 1]: k = clamp(ceil(p total), 1, total) in float64; hi' = edge(b_hi + 1) for the
+ *     first b_hi whose inclusive prefix sum is >= k, lo' = edge(b_lo) for the last b_lo whose inclusive suffix sum is >= k.
+ * method 1, MSE, candidates = C in [1, bins / 2] (param unused): err(l, h) = sum_b n_b (fq(rep(b); l, h, bits) - rep(b))^2
+ *     with fq the asymmetric float64-scale recipe of dfq_fake_quant (scale = max((h - l) / (2^bits - 1), 1e-8) in double);
+ *     difference, square and sum in float64, the sum in bin order.  k_h = argmin_{k < C} err(lo, edge(bins - k)), then
+ *     k_l = argmin_{k < C} err(edge(k), edge(bins - k_h)), the smallest k on a tie; the result is
+ *     (edge(k_l), edge(bins - k_h)).
+ * A degenerate range (above) or total == 0 gives (lo, hi) unchanged.
+ * DFQ_ERR_ARG: a null or misaligned pointer, n_hist < 0, bins outside [2, 4096], an unknown method, p outside (0.5, 1]
+ * (method 0), C outside [1, bins / 2] (method 1).  The bit widths live on the device and are NOT read here: the Python
+ * layer (prims.hist_clip_range) refuses a width outside [2, 16]; the kernel leaves the range of such a histogram unchanged. */
+int dfq_hist_clip_range(const unsigned long long* counts, const float* range2, int32_t n_hist, int32_t bins,
+                        const int32_t* num_bits, int32_t method, double param, int32_t candidates, float* out2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
