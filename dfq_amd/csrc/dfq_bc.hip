@@ -23,7 +23,7 @@
 #include <memory>
 #include <vector>
 
-#include "dfq_common.hpp"
+#include "dfq_range.hpp"
 #include "dfq_le_shared.hpp"
 
 namespace dfq {
@@ -38,6 +38,7 @@ __device__ long long g_bc_trace[kBcTraceWgs * kBcTraceWords];
 #define BC_STAMP_VAL(k, v) do { } while (0)
 #endif
 
+constexpr int kMmInFlight = 4;          // 16-byte loads a lane of the min/max pass issues per trip (range_span, dfq_range.hpp)
 constexpr int kMmChunk = kBlock * 64;   // floats per workgroup of the min/max pass: a read-only stream wants long runs (4 trips of 4 loads)
 constexpr int kQePairs = 4;            // (o, i) pairs per thread of the quant-error kernel for khkw == 1 layers
 constexpr int kExpectMax = 8192;       // floats of E[x] kept in LDS (32 KiB)
@@ -115,15 +116,6 @@ struct BcCacheSeg {          // one BN whose ReLU moment is cached
     int32_t channels, begin; // begin: first global channel index of this segment in the init launch
 };
 
-__device__ __forceinline__ int bc_find(const int32_t* __restrict__ begin, int n, int block) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (begin[mid] <= block) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 __device__ __forceinline__ float relu_mean(float w, float b);
 struct BcCacheSeg;
 __device__ __forceinline__ void bc_cache_init_block(const BcCacheSeg* __restrict__ segs, int n_segs, int total, int block, bool device_scope);
@@ -131,59 +123,15 @@ __device__ __forceinline__ void bc_cache_init_block(const BcCacheSeg* __restrict
 // per-tensor (min, max): one block of `mm_chunk` floats of one layer, merged into the layer's two slots
 __device__ __forceinline__ void bc_minmax_block(const BcLayerDev* __restrict__ layers, const int32_t* __restrict__ block_begin, int n_layers,
                                                 uint32_t* __restrict__ slots, int mm_chunk, int block, uint32_t* arrive) {
-    __shared__ float sh_mn[kBlock / kWave];
-    __shared__ float sh_mx[kBlock / kWave];
-    const int l = bc_find(block_begin, n_layers, block);
+    const int l = find_segment(block_begin, n_layers, block);
     const BcLayerDev L = layers[l];
-    const int64_t b = (int64_t)(block - block_begin[l]) * mm_chunk;
+    const int64_t b = (int64_t)(block - block_begin[l]) * mm_chunk;       // (a multiple of four floats: the chunk is as aligned as the tensor)
     const int64_t e = (b + mm_chunk < L.n) ? b + mm_chunk : L.n;
     float mn = INFINITY, mx = -INFINITY;
-    if ((((uintptr_t)L.w) & 15u) == 0) {
-        // 16-byte vectors over the aligned body of the chunk (chunk starts are multiples of 4 floats)
-        const int64_t e4 = b + ((e - b) & ~(int64_t)3);
-        // four independent 16-byte loads per trip (a read-only pass with one load in flight per lane leaves most of the
-        // memory pipeline idle), raw v_min / v_max on quieted values (a NaN of either kind is skipped, as dfq_tensor_minmax does)
-        int64_t i = b + 4 * (int64_t)threadIdx.x;
-        for (; i + 12 * kBlock < e4; i += 16 * kBlock) {
-            fvec4 v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = kReadNt ? DFQ_NT_LOAD((const fvec4*)(L.w + i + u * 4 * kBlock)) : *(const fvec4*)(L.w + i + u * 4 * kBlock);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {                  // (straight from memory: quiet_nan, dfq_common.hpp)
-                const float x0 = quiet_nan(v[u][0]), x1 = quiet_nan(v[u][1]), x2 = quiet_nan(v[u][2]), x3 = quiet_nan(v[u][3]);
-                mn = vmin_raw(vmin_raw(mn, x0), vmin_raw(x1, vmin_raw(x2, x3)));
-                mx = vmax_raw(vmax_raw(mx, x0), vmax_raw(x1, vmax_raw(x2, x3)));
-            }
-        }
-        for (; i < e4; i += 4 * kBlock) {
-            const fvec4 v = *(const fvec4*)(L.w + i);
-            const float x0 = quiet_nan(v[0]), x1 = quiet_nan(v[1]), x2 = quiet_nan(v[2]), x3 = quiet_nan(v[3]);
-            mn = vmin_raw(vmin_raw(mn, x0), vmin_raw(x1, vmin_raw(x2, x3)));
-            mx = vmax_raw(vmax_raw(mx, x0), vmax_raw(x1, vmax_raw(x2, x3)));
-        }
-        for (int64_t i = e4 + threadIdx.x; i < e; i += kBlock) {
-            const float v = quiet_nan(L.w[i]);
-            mn = fminf(mn, v);
-            mx = fmaxf(mx, v);
-        }
-    } else {
-        for (int64_t i = b + threadIdx.x; i < e; i += kBlock) {
-            const float v = quiet_nan(L.w[i]);
-            mn = fminf(mn, v);
-            mx = fmaxf(mx, v);
-        }
-    }
-    mn = wave_min(mn);
-    mx = wave_max(mx);
-    if ((threadIdx.x % kWave) == 0) { sh_mn[threadIdx.x / kWave] = mn; sh_mx[threadIdx.x / kWave] = mx; }
-    __syncthreads();
+    range_span<kMmInFlight>(L.w + b, e - b, mn, mx);
+    block_range(mn, mx);
     if (threadIdx.x == 0) {
-        float a = sh_mn[0], c = sh_mx[0];
-        for (int w = 1; w < kBlock / kWave; ++w) { a = fminf(a, sh_mn[w]); c = fmaxf(c, sh_mx[w]); }
-        if (a <= c) {
-            atomicMax(slots + 2 * l + 0, ~enc_ord(a));
-            atomicMax(slots + 2 * l + 1, enc_ord(c));
-        }
+        range_publish(mn, mx, slots + 2 * l + 0, slots + 2 * l + 1);
         // one-launch correction: the steps of THIS launch wait for their layer's blocks.  The two merges above are performed (s_waitcnt)
         // before the counter moves -- plain device-scope atomics: a RELEASE here is a write-back of the whole L2 per block, an ACQUIRE
         // in the waiters' polls an invalidation per poll, and the correction of a batch took 0.98 instead of 0.41 ms with them.
@@ -216,7 +164,7 @@ __global__ __launch_bounds__(kBlock) void bc_quant_error_kernel(const BcLayerDev
                                                                 const int32_t* __restrict__ block_begin,
                                                                 int n_layers, const uint32_t* __restrict__ slots,
                                                                 int num_bits, int symmetric) {
-    const int l = bc_find(block_begin, n_layers, blockIdx.x);
+    const int l = find_segment(block_begin, n_layers, blockIdx.x);
     const BcLayerDev L = layers[l];
     const QParams p = qparams_double((double)slot_min(slots[2 * l + 0]), (double)slot_max(slots[2 * l + 1]),
                                      num_bits, symmetric);
@@ -272,19 +220,13 @@ __global__ __launch_bounds__(kBlock) void bc_row_range_kernel(const BcRowLayerDe
     const int r = (int)blockIdx.x * (kBlock / kWave) + (int)threadIdx.x / kWave;
     if (r >= total_rows) return;                       // (wave-uniform: the reductions below stay whole-wave)
     const int lane = threadIdx.x % kWave;
-    const int l = bc_find(row_begin, n_layers, r);
+    const int l = find_segment(row_begin, n_layers, r);
     const BcRowLayerDev L = layers[l];
     const int o = r - L.row_base;
     const int64_t len = (int64_t)L.in_per_group * L.khkw;
     const float* w = L.w + (int64_t)o * len;
-    float mn = INFINITY, mx = -INFINITY;
-    for (int64_t i = lane; i < len; i += kWave) {
-        const float v = w[i];
-        mn = fminf(mn, v);
-        mx = fmaxf(mx, v);
-    }
-    mn = wave_min(mn);
-    mx = wave_max(mx);
+    float mn, mx;
+    wave_row_range(w, len, mn, mx);
     const QParams p = qparams_double((double)mn, (double)mx, num_bits, symmetric);
     if (lane == 0) { rowq[2 * (int64_t)r + 0] = p.scale; rowq[2 * (int64_t)r + 1] = p.min_value; }
     if (L.eps) {

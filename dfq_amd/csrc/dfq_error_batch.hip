@@ -7,12 +7,12 @@
 // bit for bit, what dfq_batch_quant_plan_run would store minus w ((min, max) of the tensor, or of the row for a per-row
 // configuration).
 //
-// A tensor is cut into flat pieces of kErrPiece floats, one workgroup each, as bf_stream_kernel / bt_stream_kernel cut them
-// (dfq_fold_batch.hip, dfq_table_batch.hip): a lane issues four 16-byte loads back to back whatever the row length, and the
-// row of element e is e / row_len.  The words of the ranges are cleared, then three launches, none with a wait inside:
+// A tensor is cut into flat pieces of kErrPiece floats, one workgroup each (batch_piece, dfq_batch_shared.hpp): a lane issues
+// four 16-byte loads back to back whatever the row length, and the row of element e is e / row_len.  The words of the ranges
+// are cleared, then three launches, none with a wait inside:
 //   1. be_range_kernel: the piece's (min, max) into its tensor's two words, and -- only if a configuration is per row --
 //      the (min, max) of every row the piece touches.  The four elements of a vector are folded into runs of one row; the
-//      run a vector STARTS in goes through bt_stream_kernel's segmented scan over the wave, here of a (min, max) pair, the
+//      run a vector STARTS in goes through the segmented scan over the wave (wave_head_scan), here of a (min, max) pair, the
 //      others into the piece's row table in LDS.  Rows inside the piece are stored, the first and the last row of a piece,
 //      which a neighbouring piece may hold a part of, are merged with atomicMax of the order-preserving words ~enc_ord(min),
 //      enc_ord(max) (dfq_common.hpp).  min and max do not depend on the order of the merges.
@@ -27,19 +27,19 @@
 //   3. be_fold_kernel: a thread per network, tensor and value adds the tensor's pieces in rising piece order into the
 //      caller's block.
 // No floating-point atomic anywhere: two runs are bit-identical, and network n's sums depend on nothing but its weights.
-// NaN is skipped by every min / max (v_min_f32 / v_max_f32 return the other operand); an element that is NaN has e = NaN, so a
-// tensor holding one gets NaN sums, in its own slot only.  Work is found from tables of ONE network: workgroup -> (network,
-// piece of network 0) by a division, then the piece's tensor from a table of network 0's pieces (one load).
+// NaN of either kind is skipped by every range (the rule of "Special values", include/dfq_hip.h; range_fold, dfq_range.hpp); an
+// element that is NaN has e = NaN, so a tensor holding one gets NaN sums, in its own slot only.
 #include <math.h>
 
 #include <vector>
 
 #include "dfq_batch_shared.hpp"
+#include "dfq_range.hpp"
 
 namespace dfq {
 
-constexpr int kErrInFlight = 4;                              // 16-byte loads a lane issues before it uses the first
-constexpr int kErrPiece = kBlock * 4 * kErrInFlight;         // floats of one tensor a workgroup reads
+constexpr int kErrInFlight = kPieceInFlight;                 // 16-byte loads a lane issues before it uses the first
+constexpr int kErrPiece = kBatchPiece;                       // floats of one tensor a workgroup reads
 constexpr int kErrRowsLds = 2048;                            // rows whose quantiser parameters are staged at a time
 constexpr int kErrMaxConfigs = 4;
 
@@ -65,64 +65,23 @@ struct BeArgs {
     int32_t pieces_pn, n_tensors, n_nets, n_configs, n_vals;
 };
 
-// what the three kernels share: the piece of this workgroup
-struct BePiece {
+// what the kernels share: the piece of this workgroup, its tensor, its first element
+struct BePiece : BatchPiece {
     BeTensorDev T;
-    const gfloat* w;              // its first element
-    int64_t first_row;
-    uint32_t rem0, row_len;       // of the piece's first element in its row
-    int net, lp, ti, count, n_rows, nv;
+    const gfloat* w;
 };
 
 __device__ __forceinline__ BePiece be_piece(const BeArgs& a) {
     BePiece p;
-    p.net = (int)(blockIdx.x / (unsigned)a.pieces_pn);
-    p.lp = (int)blockIdx.x - p.net * a.pieces_pn;
-    p.ti = a.piece_tensor[p.lp];
-    p.T = a.tensors[p.ti];
-    const int64_t start = (int64_t)(p.lp - p.T.piece_begin) * kErrPiece;
-    p.count = (int)(p.T.n - start < kErrPiece ? p.T.n - start : kErrPiece);
-    p.first_row = start / p.T.row_len;
-    p.rem0 = (uint32_t)(start - p.first_row * p.T.row_len);
-    p.row_len = (uint32_t)p.T.row_len;
-    p.n_rows = (int)((p.rem0 + (uint32_t)p.count - 1u) / p.row_len) + 1;
-    p.w = (const gfloat*)(const float*)((const char*)p.T.w + a.delta[p.net]) + start;
-    p.nv = p.count >> 2;
+    (BatchPiece&)p = batch_piece(a.pieces_pn, a.piece_tensor, a.tensors, p.T);
+    p.w = (const gfloat*)(const float*)((const char*)p.T.w + a.delta[p.net]) + p.start;
     return p;
-}
-
-// every load of the piece back to back, a lane past the piece's end reading the last vector again (bf_stream_kernel); a
-// tensor's last piece may end in up to three single floats, one each for the first lanes
-__device__ __forceinline__ void be_load(const BePiece& p, fvec4 (&x)[kErrInFlight], float& xt) {
-    const int t = threadIdx.x;
-    if (p.nv > 0) {
-#pragma unroll
-        for (int j = 0; j < kErrInFlight; ++j) {
-            const int v = j * kBlock + t;
-            x[j] = *(const gfvec4*)(p.w + 4 * (v < p.nv ? v : p.nv - 1));
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < kErrInFlight; ++j) x[j] = fvec4{0.0f, 0.0f, 0.0f, 0.0f};
-    }
-    const int tail = (p.nv << 2) + t;
-    xt = tail < p.count ? p.w[tail] : 0.0f;
-}
-
-// a run's (min, max) into the piece's row table; a run of nothing but NaN has kept the identities and is left out
-__device__ __forceinline__ void be_merge(uint32_t* row_mn, uint32_t* row_mx, uint32_t r, float mn, float mx) {
-    if (mn <= mx) {
-        atomicMax(&row_mn[r], ~enc_ord(mn));
-        atomicMax(&row_mx[r], enc_ord(mx));
-    }
 }
 
 // launch 1: (min, max) of the piece into its tensor's words and, with a per-row configuration, of every row it touches
 __global__ __launch_bounds__(kBlock) void be_range_kernel(BeArgs a) {
     __shared__ uint32_t row_mn[kErrPiece];             // ~enc_ord(min) of row first_row + i (a piece of rows of 1 has kErrPiece)
     __shared__ uint32_t row_mx[kErrPiece];             // enc_ord(max)
-    __shared__ float sh_mn[kBlock / kWave];
-    __shared__ float sh_mx[kBlock / kWave];
     const BePiece p = be_piece(a);
     const int t = threadIdx.x;
     const int lane = t % kWave;
@@ -131,7 +90,7 @@ __global__ __launch_bounds__(kBlock) void be_range_kernel(BeArgs a) {
     const bool by_row = a.row_words != nullptr;        // (uniform over the launch)
     fvec4 x[kErrInFlight];
     float xt;
-    be_load(p, x, xt);
+    batch_piece_load<false>(p, p.w, x, xt);
     if (by_row) {
         for (int i = t; i < p.n_rows; i += kBlock) { row_mn[i] = 0u; row_mx[i] = 0u; }
         __syncthreads();
@@ -143,70 +102,48 @@ __global__ __launch_bounds__(kBlock) void be_range_kernel(BeArgs a) {
         const int v = j * kBlock + t;
         const bool live = v < nv;
         if (!by_row) {
-            if (live) {
-#pragma unroll
-                for (int c = 0; c < 4; ++c) { mn = vmin_raw(mn, x[j][c]); mx = vmax_raw(mx, x[j][c]); }
-            }
+            if (live) range_fold4(x[j], mn, mx);
             continue;
         }
         const uint32_t e = p.rem0 + 4u * (uint32_t)v;
         const uint32_t key = e / row_len;              // the row this vector starts in
         uint32_t rem = e - key * row_len;
         uint32_t r = key;
-        float hmn = INFINITY, hmx = -INFINITY, rmn = INFINITY, rmx = -INFINITY;
+        float head[2] = {INFINITY, -INFINITY}, rmn = INFINITY, rmx = -INFINITY;
         bool first = true;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            const float xv = x[j][c];
-            if (live) {
-                mn = vmin_raw(mn, xv);
-                mx = vmax_raw(mx, xv);
-            }
-            rmn = vmin_raw(rmn, xv);
-            rmx = vmax_raw(rmx, xv);
+            if (live) range_fold(x[j][c], mn, mx);
+            range_fold(x[j][c], rmn, rmx);
             if (++rem == row_len) {                    // the row ends behind this element
                 rem = 0;
-                if (first) { hmn = rmn; hmx = rmx; first = false; }
-                else if (live) be_merge(row_mn, row_mx, r, rmn, rmx);
+                if (first) { head[0] = rmn; head[1] = rmx; first = false; }
+                else if (live) range_publish(rmn, rmx, &row_mn[r], &row_mx[r]);
                 ++r;
                 rmn = INFINITY;
                 rmx = -INFINITY;
             }
         }
-        if (first) { hmn = rmn; hmx = rmx; }
-        else if (live && rem != 0) be_merge(row_mn, row_mx, r, rmn, rmx);
-        // segmented scan of the head run over the lanes whose vectors start in row `key` (bt_stream_kernel): they are
-        // consecutive, and the first of them is the first lane whose vector starts at or behind the row's first element
-        const int wave_e0 = (int)(p.rem0 + 4u * (uint32_t)(v - lane));
-        const int ahead = (int)(key * row_len) - wave_e0;
-        const int lane_start = ahead <= 0 ? 0 : (ahead + 3) >> 2;
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const int src = lane >= d ? lane - d : lane;
-            const float on = __shfl(hmn, src);
-            const float ox = __shfl(hmx, src);
-            if (lane - d >= lane_start) { hmn = vmin_raw(hmn, on); hmx = vmax_raw(hmx, ox); }
-        }
+        if (first) { head[0] = rmn; head[1] = rmx; }
+        else if (live && rem != 0) range_publish(rmn, rmx, &row_mn[r], &row_mx[r]);
+        wave_head_scan(p, v, key, head, [](float (&h)[2], const float (&o)[2]) { range_merge(h[0], h[1], o[0], o[1]); });
         // the last lane of the segment holds its range: r is the row the NEXT lane's vector starts in
-        if (live && (lane == kWave - 1 || v + 1 >= nv || r != key)) be_merge(row_mn, row_mx, key, hmn, hmx);
+        if (live && (lane == kWave - 1 || v + 1 >= nv || r != key)) range_publish(head[0], head[1], &row_mn[key], &row_mx[key]);
     }
     const int tail = (nv << 2) + t;
     if (tail < p.count) {
-        mn = vmin_raw(mn, xt);
-        mx = vmax_raw(mx, xt);
-        if (by_row) be_merge(row_mn, row_mx, (p.rem0 + (uint32_t)tail) / row_len, vmin_raw(INFINITY, xt), vmax_raw(-INFINITY, xt));
-    }
-    wave_minmax(mn, mx);
-    if (lane == 0) { sh_mn[t / kWave] = mn; sh_mx[t / kWave] = mx; }
-    __syncthreads();                                   // (the row table is complete behind it, too)
-    if (t == 0) {
-#pragma unroll
-        for (int k = 1; k < kBlock / kWave; ++k) { mn = vmin_raw(mn, sh_mn[k]); mx = vmax_raw(mx, sh_mx[k]); }
-        if (mn <= mx) {                                // (false only for a piece of NaNs)
-            uint32_t* words = a.tensor_words + 2 * ((int64_t)p.net * a.n_tensors + p.ti);
-            atomicMax(words + 0, ~enc_ord(mn));
-            atomicMax(words + 1, enc_ord(mx));
+        range_fold(xt, mn, mx);
+        if (by_row) {
+            const uint32_t r = (p.rem0 + (uint32_t)tail) / row_len;
+            float tmn = INFINITY, tmx = -INFINITY;
+            range_fold(xt, tmn, tmx);
+            range_publish(tmn, tmx, &row_mn[r], &row_mx[r]);
         }
+    }
+    block_range(mn, mx);                               // (the row table is complete behind its barrier, too)
+    if (t == 0) {                                      // (nothing for a piece of NaNs)
+        uint32_t* words = a.tensor_words + 2 * ((int64_t)p.net * a.n_tensors + p.ti);
+        range_publish(mn, mx, words + 0, words + 1);
     }
     if (!by_row) return;
     uint32_t* rows = a.row_words + 2 * ((int64_t)p.net * a.rows_pn + p.T.row_begin + p.first_row);
@@ -284,7 +221,7 @@ __global__ __launch_bounds__(kBlock) void be_error_kernel(BeArgs a) {
     const int t = threadIdx.x;
     fvec4 x[kErrInFlight];
     float xt;
-    be_load(p, x, xt);
+    batch_piece_load<false>(p, p.w, x, xt);
     double* part = a.partial + ((int64_t)p.net * a.pieces_pn + p.lp) * a.n_vals;
     {
         double sw = 0.0;
@@ -396,7 +333,7 @@ int dfq_batch_error_plan_create(const dfq_batch_error_tensor* tensors, int32_t n
 
     std::vector<BeTensorDev> dev;
     std::vector<int32_t> piece_tensor;
-    int64_t pieces = 0, rows_pn = 0;
+    int64_t rows_pn = 0;
     for (int i = 0; i < n_tensors; ++i) {
         const dfq_batch_error_tensor& q = tensors[i];
         if (!q.data) return fail_arg("%s: tensor %d: null weight", me, i);
@@ -406,15 +343,15 @@ int dfq_batch_error_plan_create(const dfq_batch_error_tensor* tensors, int32_t n
         if ((uintptr_t)q.data % 16 != 0) return fail_arg("%s: tensor %d: the weight is not 16-byte aligned", me, i);
         if (q.out_offset < 0 || q.out_offset > stride - n_vals)
             return fail_arg("%s: tensor %d: %d sums at %lld lie outside the stride %lld", me, i, n_vals, (long long)q.out_offset, (long long)stride);
-        BeTensorDev T{q.data, q.rows * q.row_len, q.out_offset, rows_pn, (int32_t)q.row_len, (int32_t)q.rows, (int32_t)pieces, 0};
-        const int64_t k = (T.n + kErrPiece - 1) / kErrPiece;
-        T.n_pieces = (int32_t)k;
-        pieces += k;
+        BeTensorDev T{q.data, q.rows * q.row_len, q.out_offset, rows_pn, (int32_t)q.row_len, (int32_t)q.rows, 0, 0};
+        const int64_t begin = batch_add_pieces(piece_tensor, i, T.n, 0x7fffffff / n_nets / n_vals);
         rows_pn += q.rows;
-        if (pieces > 0x7fffffff / n_nets / n_vals || rows_pn > INT64_MAX / 16 / n_nets) return fail_arg("%s: too much work for one launch", me);
-        piece_tensor.insert(piece_tensor.end(), (size_t)k, (int32_t)i);
+        if (begin < 0 || rows_pn > INT64_MAX / 16 / n_nets) return fail_arg("%s: too much work for one launch", me);
+        T.piece_begin = (int32_t)begin;
+        T.n_pieces = (int32_t)((int64_t)piece_tensor.size() - begin);
         dev.push_back(T);
     }
+    const int64_t pieces = (int64_t)piece_tensor.size();
     if (stride > INT64_MAX / 8 / n_nets) return fail_arg("%s: a block of %d x %lld doubles", me, (int)n_nets, (long long)stride);
 
     dfq_batch_error_plan* p = new dfq_batch_error_plan();

@@ -6,14 +6,13 @@
 //
 // Two launches, neither with a wait inside, no atomics:
 //   1. bf_stream_kernel reads and writes every folded weight once.  A tensor is cut into flat pieces of kFoldPiece floats,
-//      one workgroup each: the row of element e is e / row_len, so depthwise rows of 9, the stem's rows of 27 and rows
-//      longer than a piece all take the same path and every lane moves 16 bytes at a time whatever the row length.  The
+//      one workgroup each (batch_piece, dfq_batch_shared.hpp): the row of element e is e / row_len, so depthwise rows of 9,
+//      the stem's rows of 27 and rows longer than a piece all take the same path and every lane moves 16 bytes at a time
+//      whatever the row length.  The
 //      piece's k = gamma / sqrtf(var + eps) -- one per row it touches, at most kFoldPiece of them -- are recomputed into LDS
 //      while the piece's loads are in flight.  gamma and var are only READ in this launch.
 //   2. bf_vec_kernel, a thread per channel of every pair and network: the bias update, the proxies, the identity BatchNorm.
 //      It is the only writer of gamma / var, and stream order puts it behind every reader.
-// Work is found from tables of ONE network: workgroup -> (network, piece of network 0) by a division, then the piece's pair
-// from a table of network 0's pieces (one load).
 #include <math.h>
 
 #include <vector>
@@ -22,8 +21,8 @@
 
 namespace dfq {
 
-constexpr int kFoldInFlight = 4;                                // 16-byte loads a lane issues before it uses the first
-constexpr int kFoldPiece = kBlock * 4 * kFoldInFlight;          // floats of one tensor a workgroup scales
+constexpr int kFoldInFlight = kPieceInFlight;                   // 16-byte loads a lane issues before it uses the first
+constexpr int kFoldPiece = kBatchPiece;                         // floats of one tensor a workgroup scales
 
 struct BfPairDev {                // a (layer, BatchNorm) pair of network 0
     float *w, *b, *gamma, *beta, *mean, *var, *fake_weight, *fake_bias;
@@ -48,34 +47,19 @@ __device__ __forceinline__ T* bf_at(T* p, int64_t d) { return (T*)((char*)p + d)
 // launch 1: w[r, :] *= gamma[r] / sqrtf(var[r] + eps)
 __global__ __launch_bounds__(kBlock) void bf_stream_kernel(BfArgs a) {
     __shared__ float k_of[kFoldPiece];                 // k of row first_row + i
-    const int net = (int)(blockIdx.x / (unsigned)a.pieces_pn);
-    const int lp = (int)blockIdx.x - net * a.pieces_pn;
-    const BfPairDev P = a.pairs[a.piece_pair[lp]];
-    const int64_t d = a.delta[net];
-    const int64_t start = (int64_t)(lp - P.piece_begin) * kFoldPiece;
-    const int count = (int)(P.n - start < kFoldPiece ? P.n - start : kFoldPiece);
-    const int64_t first_row = start / P.row_len;
-    const uint32_t rem0 = (uint32_t)(start - first_row * P.row_len);      // of the piece's first element in its row
-    const uint32_t row_len = (uint32_t)P.row_len;
-    const int n_rows = (int)((rem0 + (uint32_t)count - 1u) / row_len) + 1;
-    gfloat* w = (gfloat*)bf_at(P.w, d) + start;
+    BfPairDev P;
+    const BatchPiece p = batch_piece(a.pieces_pn, a.piece_pair, a.pairs, P);
+    const int64_t d = a.delta[p.net];
+    gfloat* w = (gfloat*)bf_at(P.w, d) + p.start;
     const int t = threadIdx.x;
-    const int nv = count >> 2;
-    // every load of the piece back to back: a load under a per-lane condition is a block of its own that ends in a wait, so a
-    // lane past the piece's end reads the last vector again (the same line) under one workgroup-uniform condition instead
+    const int nv = p.nv, n_rows = p.n_rows;
+    const uint32_t row_len = p.row_len, rem0 = p.rem0;
     fvec4 x[kFoldInFlight];
-    if (nv > 0) {
-#pragma unroll
-        for (int j = 0; j < kFoldInFlight; ++j) {
-            const int v = j * kBlock + t;
-            x[j] = DFQ_NT_LOAD((const gfvec4*)(w + 4 * (v < nv ? v : nv - 1)));
-        }
-    }
-    const int tail = (nv << 2) + t;                    // a tensor's last piece may end in up to three single floats
-    float xt = 0.0f;
-    if (tail < count) xt = w[tail];
-    const gfloat* gamma = (const gfloat*)bf_at(P.gamma, d) + first_row;
-    const gfloat* var = (const gfloat*)bf_at(P.var, d) + first_row;
+    float xt;
+    batch_piece_load<true>(p, w, x, xt);
+    const int tail = (nv << 2) + t;
+    const gfloat* gamma = (const gfloat*)bf_at(P.gamma, d) + p.first_row;
+    const gfloat* var = (const gfloat*)bf_at(P.var, d) + p.first_row;
     for (int i = t; i < n_rows; i += kBlock) {
         const float sd = sqrtf(var[i] + P.eps);        // bn_fold_vec_kernel, dfq_misc.hip
         k_of[i] = gamma[i] / sd;
@@ -96,7 +80,7 @@ __global__ __launch_bounds__(kBlock) void bf_stream_kernel(BfArgs a) {
         }
         DFQ_NT_STORE(y, (gfvec4*)(w + 4 * v));
     }
-    if (tail < count) w[tail] = xt * k_of[(rem0 + (uint32_t)tail) / row_len];
+    if (tail < p.count) w[tail] = xt * k_of[(rem0 + (uint32_t)tail) / row_len];
 }
 
 // launch 2: the per-channel part of bn_fold_vec_kernel; var becomes 1 here, what fill_kernel does behind the row scale
@@ -159,7 +143,7 @@ int dfq_batch_fold_plan_create(const dfq_batch_fold_pair* pairs, int32_t n_pairs
     std::vector<BfPairDev> dev;
     std::vector<int32_t> piece_pair, chan_pair;
     std::vector<const void*> vectors;                  // every per-channel vector seen so far: none may appear twice
-    int64_t pieces = 0, chans = 0, elements = 0;
+    int64_t chans = 0, elements = 0;
     for (int i = 0; i < n_pairs; ++i) {
         const dfq_batch_fold_pair& q = pairs[i];
         if (!q.w || !q.b || !q.gamma || !q.beta || !q.mean || !q.var || !q.fake_weight || !q.fake_bias)
@@ -178,17 +162,17 @@ int dfq_batch_fold_plan_create(const dfq_batch_fold_pair* pairs, int32_t n_pairs
         }
         vectors.insert(vectors.end(), mine, mine + 7);
         BfPairDev P{q.w, q.b, q.gamma, q.beta, q.mean, q.var, q.fake_weight, q.fake_bias,
-                    (int64_t)q.out_ch * q.row_len, (int32_t)q.row_len, q.out_ch, q.eps, (int32_t)pieces, (int32_t)chans};
-        const int64_t k = (P.n + kFoldPiece - 1) / kFoldPiece;
-        pieces += k;
+                    (int64_t)q.out_ch * q.row_len, (int32_t)q.row_len, q.out_ch, q.eps, 0, (int32_t)chans};
+        const int64_t begin = batch_add_pieces(piece_pair, i, P.n, 0x7fffffff / n_nets);
         chans += q.out_ch;
         elements += P.n;
-        if (pieces > 0x7fffffff / n_nets || chans > 0x7fffffff / n_nets) return fail_arg("%s: too much work for one launch", me);
-        piece_pair.insert(piece_pair.end(), (size_t)k, (int32_t)i);
+        if (begin < 0 || chans > 0x7fffffff / n_nets) return fail_arg("%s: too much work for one launch", me);
+        P.piece_begin = (int32_t)begin;
         chan_pair.insert(chan_pair.end(), (size_t)q.out_ch, (int32_t)i);
         dev.push_back(P);
     }
 
+    const int64_t pieces = (int64_t)piece_pair.size();
     dfq_batch_fold_plan* p = new dfq_batch_fold_plan();
     BfArgs& a = p->args;
     a.pieces_pn = (int32_t)pieces;

@@ -6,7 +6,7 @@
 // (four launches and two passes over the data per pair instead of one pass per level).
 #include <algorithm>
 
-#include "dfq_common.hpp"
+#include "dfq_range.hpp"
 
 namespace dfq {
 
@@ -24,14 +24,8 @@ __global__ __launch_bounds__(kBlock) void row_range_kernel(const float* __restri
     if (r >= rows) return;
     const int lane = threadIdx.x % kWave;
     const float* row = w + r * row_len;
-    float mn = INFINITY, mx = -INFINITY;
-    for (int64_t i = lane; i < row_len; i += kWave) {
-        const float v = quiet_nan(row[i]);            // a NaN of either kind is skipped (include/dfq_hip.h, "NaN rule")
-        mn = fminf(mn, v);
-        mx = fmaxf(mx, v);
-    }
-    mn = wave_min(mn);
-    mx = wave_max(mx);
+    float mn, mx;
+    wave_row_range(row, row_len, mn, mx);             // a NaN of either kind is skipped (include/dfq_hip.h, "NaN rule")
     if (lane == 0) out[r] = prim_range(mn, mx, signed_range);
 }
 
@@ -48,11 +42,7 @@ __global__ __launch_bounds__(kBlock) void col_range_kernel(const float* __restri
     float mn = INFINITY, mx = -INFINITY;
     for (int j = 0; j < go; ++j) {
         const float* p = w2 + (((int64_t)g * go + j) * in_per_group + ii) * khkw;
-        for (int k = 0; k < khkw; ++k) {
-            const float v = quiet_nan(p[k]);
-            mn = fminf(mn, v);
-            mx = fmaxf(mx, v);
-        }
+        for (int k = 0; k < khkw; ++k) range_fold(p[k], mn, mx);
     }
     out[c] = prim_range(mn, mx, signed_range);
 }
@@ -149,14 +139,7 @@ __global__ __launch_bounds__(kBlock) void fake_quant_rows_kernel(const float* __
         mn = mins[r];
         mx = maxs[r];
     } else {
-        mn = INFINITY; mx = -INFINITY;
-        for (int64_t i = lane; i < row_len; i += kWave) {
-            const float v = row[i];
-            mn = fminf(mn, v);
-            mx = fmaxf(mx, v);
-        }
-        mn = wave_min(mn);
-        mx = wave_max(mx);
+        wave_row_range(row, row_len, mn, mx);
     }
     if (minmax_out && lane == 0) { minmax_out[2 * r] = mn; minmax_out[2 * r + 1] = mx; }
     const QParams p = qparams_double((double)mn, (double)mx, num_bits, symmetric);
@@ -188,14 +171,7 @@ __global__ __launch_bounds__(kBlock) void zeroq_quant_rows_kernel(const float* _
         mn = mins[r];
         mx = maxs[r];
     } else {
-        mn = INFINITY; mx = -INFINITY;
-        for (int64_t i = lane; i < row_len; i += kWave) {
-            const float v = row[i];
-            mn = fminf(mn, v);
-            mx = fmaxf(mx, v);
-        }
-        mn = wave_min(mn);
-        mx = wave_max(mx);
+        wave_row_range(row, row_len, mn, mx);
     }
     if (minmax_out && lane == 0) { minmax_out[2 * r] = mn; minmax_out[2 * r + 1] = mx; }
     const float n = (float)((1ll << num_bits) - 1);

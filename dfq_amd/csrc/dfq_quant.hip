@@ -9,103 +9,17 @@
 
 #include <algorithm>
 
-#include "dfq_common.hpp"
+#include "dfq_range.hpp"
 #include "dfq_le_shared.hpp"   // spin_limit_from_env
 
 namespace dfq {
 
 constexpr int kChunk = kBlock * 16;   // elements one workgroup owns in the multi-tensor kernels
+constexpr int kSpanInFlight = 8;      // 16-byte loads a lane of the range kernels issues per trip (range_span, dfq_range.hpp)
 
 // ---------------------------------------------------------------------------------------------
 // device bodies
 // ---------------------------------------------------------------------------------------------
-// one 16-byte vector into a lane's running (min, max): NaN of either kind is skipped (quiet_nan, dfq_common.hpp)
-__device__ __forceinline__ void fold_vec(const float4& raw, float& mn, float& mx) {
-    const float x = quiet_nan(raw.x), y = quiet_nan(raw.y), z = quiet_nan(raw.z), w = quiet_nan(raw.w);
-    mn = vmin_raw(vmin_raw(mn, x), vmin_raw(y, vmin_raw(z, w)));
-    mx = vmax_raw(vmax_raw(mx, x), vmax_raw(y, vmax_raw(z, w)));
-}
-
-__device__ __forceinline__ void thread_minmax_range(const float* __restrict__ x, int64_t begin,
-                                                    int64_t end, float& mn, float& mx) {
-    const int tid = threadIdx.x;
-    const float* p = x + begin;
-    const int64_t len = end - begin;
-    if ((reinterpret_cast<uintptr_t>(p) & 15u) == 0) {
-        const int64_t n4 = len >> 2;
-        const float4* p4 = reinterpret_cast<const float4*>(p);
-        // four independent 16-byte loads per trip (a read-only pass with one load in flight per lane leaves most of
-        // the memory pipeline idle), raw v_min / v_max on values quieted once (fold_vec)
-        int64_t i = tid;
-        for (; i + 7 * kBlock < n4; i += 8 * kBlock) {              // eight 16-byte loads in flight per lane
-            float4 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                if (kReadNt) { const fvec4 t = DFQ_NT_LOAD((const fvec4*)(p4 + i + u * kBlock)); v[u].x = t[0]; v[u].y = t[1]; v[u].z = t[2]; v[u].w = t[3]; }
-                else v[u] = p4[i + u * kBlock];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) fold_vec(v[u], mn, mx);
-        }
-        for (; i + 3 * kBlock < n4; i += 4 * kBlock) {
-            float4 v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = p4[i + u * kBlock];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) fold_vec(v[u], mn, mx);
-        }
-        for (; i < n4; i += kBlock) {
-            fold_vec(p4[i], mn, mx);
-        }
-        for (int64_t i = (n4 << 2) + tid; i < len; i += kBlock) {
-            const float v = quiet_nan(p[i]);             // (nothing on the GPU, where fminf canonicalises; the host's fminf returns a NaN for a signalling operand)
-            mn = fminf(mn, v);
-            mx = fmaxf(mx, v);
-        }
-    } else {
-        for (int64_t i = tid; i < len; i += kBlock) {
-            const float v = quiet_nan(p[i]);             // (nothing on the GPU, where fminf canonicalises; the host's fminf returns a NaN for a signalling operand)
-            mn = fminf(mn, v);
-            mx = fmaxf(mx, v);
-        }
-    }
-}
-
-// block-wide min/max -> one pair of atomics on the (max slot, min slot) pair
-__device__ __forceinline__ void block_publish_minmax(float mn, float mx, uint32_t* slot_pair) {
-    __shared__ float sh_mn[kBlock / kWave];
-    __shared__ float sh_mx[kBlock / kWave];
-    mn = wave_min(mn);
-    mx = wave_max(mx);
-    const int wave = threadIdx.x / kWave;
-    if ((threadIdx.x % kWave) == 0) {
-        sh_mn[wave] = mn;
-        sh_mx[wave] = mx;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float a = sh_mn[0], b = sh_mx[0];
-#pragma unroll
-        for (int w = 1; w < kBlock / kWave; ++w) {
-            a = fminf(a, sh_mn[w]);
-            b = fmaxf(b, sh_mx[w]);
-        }
-        if (a <= b) {   // false only if the range was empty
-            atomicMax(slot_pair + 0, ~enc_ord(a));   // min slot
-            atomicMax(slot_pair + 1, enc_ord(b));    // max slot
-        }
-    }
-}
-
-__device__ __forceinline__ int find_segment(const int32_t* __restrict__ block_begin, int n_segs, int block) {
-    int lo = 0, hi = n_segs - 1;   // largest s with block_begin[s] <= block
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (block_begin[mid] <= block) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 struct SegDev {
     float* data;
     int32_t* codes;
@@ -123,9 +37,10 @@ __global__ __launch_bounds__(kBlock) void minmax_kernel(const float* __restrict_
     for (int64_t c = blockIdx.x; c * kChunk < n; c += gridDim.x) {
         const int64_t b = c * kChunk;
         const int64_t e = (b + kChunk < n) ? b + kChunk : n;
-        thread_minmax_range(x, b, e, mn, mx);
+        range_span<kSpanInFlight>(x + b, e - b, mn, mx);
     }
-    block_publish_minmax(mn, mx, slot_pair);
+    block_range(mn, mx);
+    if (threadIdx.x == 0) range_publish(mn, mx, slot_pair + 0, slot_pair + 1);
 }
 
 __global__ void slots_decode_kernel(const uint32_t* __restrict__ slots, float* __restrict__ out, int n_pairs) {
@@ -144,8 +59,9 @@ __global__ __launch_bounds__(kBlock) void seg_minmax_kernel(const SegDev* __rest
     const int64_t b = (int64_t)(blockIdx.x - block_begin[s]) * kChunk;
     const int64_t e = (b + kChunk < sg.n) ? b + kChunk : sg.n;
     float mn = INFINITY, mx = -INFINITY;
-    thread_minmax_range(sg.data, b, e, mn, mx);
-    block_publish_minmax(mn, mx, slots + 2 * s);
+    range_span<kSpanInFlight>(sg.data + b, e - b, mn, mx);
+    block_range(mn, mx);
+    if (threadIdx.x == 0) range_publish(mn, mx, slots + 2 * s + 0, slots + 2 * s + 1);
 }
 
 // x may alias y (in-place), so no __restrict__ here
@@ -232,8 +148,9 @@ __global__ __launch_bounds__(kBlock) void sample_minmax_kernel(const float* __re
     const int64_t b = (int64_t)blockIdx.x * span;
     const int64_t e = (b + span < sample_len) ? b + span : sample_len;
     float mn = INFINITY, mx = -INFINITY;
-    if (b < e) thread_minmax_range(xs, b, e, mn, mx);
-    block_publish_minmax(mn, mx, slots + 2 * smp);
+    if (b < e) range_span<kSpanInFlight>(xs + b, e - b, mn, mx);
+    block_range(mn, mx);
+    if (threadIdx.x == 0) range_publish(mn, mx, slots + 2 * smp + 0, slots + 2 * smp + 1);
 }
 
 // mean over samples of the per-sample extrema (float64 accumulation in a fixed order, rounded once); valid in every thread
@@ -336,11 +253,10 @@ constexpr size_t kQmSmem = 128;
 
 __global__ __launch_bounds__(kBlock) void quant_measure_fused_kernel(QmArgs a) {
     DFQ_DYN_SMEM(smem);
-    float* sh_mn = (float*)smem;                         // [kBlock / kWave]
-    float* sh_mx = sh_mn + kBlock / kWave;
+    float* sh_range = (float*)smem;                      // [2 * kBlock / kWave]
     double* sh_d = (double*)(smem + 32);                 // [kBlock / kWave]
     int* sh_ok = (int*)(smem + 96);
-    const int tid = threadIdx.x, lane = tid % kWave, wave = tid / kWave;
+    const int tid = threadIdx.x;
     // ---- phase A: extrema of this workgroup's spans ----
     const int items = a.n_samples * a.spans_per_sample;
     for (int it = blockIdx.x; it < items; it += gridDim.x) {
@@ -348,21 +264,10 @@ __global__ __launch_bounds__(kBlock) void quant_measure_fused_kernel(QmArgs a) {
         const int64_t b = (int64_t)(it - smp * a.spans_per_sample) * a.span;
         const int64_t e = (b + a.span < a.sample_len) ? b + a.span : a.sample_len;
         float mn = INFINITY, mx = -INFINITY;
-        if (b < e) thread_minmax_range(a.x + (int64_t)smp * a.sample_len, b, e, mn, mx);
-        mn = wave_min(mn);
-        mx = wave_max(mx);
-        if (lane == 0) { sh_mn[wave] = mn; sh_mx[wave] = mx; }
-        __syncthreads();
-        if (tid == 0) {
-            float lo = sh_mn[0], hi = sh_mx[0];
-#pragma unroll
-            for (int w = 1; w < kBlock / kWave; ++w) { lo = fminf(lo, sh_mn[w]); hi = fmaxf(hi, sh_mx[w]); }
-            if (lo <= hi) {   // false only if the range was empty
-                atomicMax(a.slots_cur + 2 * smp + 0, ~enc_ord(lo));
-                atomicMax(a.slots_cur + 2 * smp + 1, enc_ord(hi));
-            }
-        }
-        __syncthreads();                                  // sh_mn / sh_mx are rewritten by the next item
+        if (b < e) range_span<kSpanInFlight>(a.x + (int64_t)smp * a.sample_len + b, e - b, mn, mx);
+        block_range(mn, mx, sh_range);
+        if (tid == 0) range_publish(mn, mx, a.slots_cur + 2 * smp + 0, a.slots_cur + 2 * smp + 1);
+        __syncthreads();                                  // sh_range is rewritten by the next item
     }
     // ---- the whole grid has published: arrival (after this workgroup's atomics have been performed), bounded wait ----
     __builtin_amdgcn_s_waitcnt(0);

@@ -12,12 +12,14 @@
 // row, and read the row twice.  A per-tensor tensor of at most kRegElems elements is a single such row.
 // Per tensor, longer: a min/max launch folds every chunk of kChunkQ elements into its tensor's pair of order-preserving slots
 // (atomicMax of enc_ord, as dfq_quant_plan does; the slots are cleared in front of it), the quantising launch reads the pair.
-// No workgroup ever waits for another one of its launch.
+// No workgroup ever waits for another one of its launch.  NaN of either kind is skipped by every range (the rule of "Special
+// values", include/dfq_hip.h; range_fold, dfq_range.hpp).
 // Work is found from tables of ONE network: wave -> (network, wave of network 0) by a division, then the wave's tensor from a
 // table of network 0's waves (one load; a binary search over the tensors cost a chain of dependent loads per wave).
 #include <vector>
 
 #include "dfq_batch_shared.hpp"
+#include "dfq_range.hpp"
 
 namespace dfq {
 
@@ -68,20 +70,6 @@ __device__ __forceinline__ void bq_store_code(unsigned char* codes, int code_byt
     else ((guint8*)codes)[i] = (uint8_t)(int32_t)code;   // the int32 code's low byte: uint8 (asymmetric) / int8 (symmetric)
 }
 
-// (min, max) of the block in every thread
-__device__ __forceinline__ void bq_block_minmax(float& mn, float& mx) {
-    __shared__ float sh_mn[kBlock / kWave];
-    __shared__ float sh_mx[kBlock / kWave];
-    wave_minmax(mn, mx);
-    const int wave = threadIdx.x / kWave;
-    if ((threadIdx.x % kWave) == 0) { sh_mn[wave] = mn; sh_mx[wave] = mx; }
-    __syncthreads();
-    mn = sh_mn[0];
-    mx = sh_mx[0];
-#pragma unroll
-    for (int w = 1; w < kBlock / kWave; ++w) { mn = vmin_raw(mn, sh_mn[w]); mx = vmax_raw(mx, sh_mx[w]); }
-}
-
 // R sets of 64 / L rows of one tensor from first_row on (row first_row + j * 64 / L + lane / L), L lanes each, K register slots
 // per lane and row (len <= K * L)
 template <int L, int K, int R>
@@ -118,10 +106,7 @@ __device__ __forceinline__ void bq_rows(const BqRowDev& T, float* x, unsigned ch
         for (int k = 0; k < K; ++k) {
             if (k * L >= len) break;
             const int i = g + k * L;
-            if (live && i < len) {
-                mn = vmin_raw(mn, v[j][k]);
-                mx = vmax_raw(mx, v[j][k]);
-            }
+            if (live && i < len) range_fold(v[j][k], mn, mx);
         }
         if constexpr (L > 1) xor_lane_minmax<1>(mn, mx);
         if constexpr (L > 2) xor_lane_minmax<2>(mn, mx);
@@ -150,13 +135,8 @@ __device__ __forceinline__ void bq_long_row(const BqRowDev& T, float* x, unsigne
     const int lane = threadIdx.x % kWave;
     const int len = T.len;
     gfloat* xr = (gfloat*)x + (int64_t)r * len;
-    float mn = INFINITY, mx = -INFINITY;
-    for (int i = lane; i < len; i += kWave) {
-        const float v = xr[i];
-        mn = vmin_raw(mn, v);
-        mx = vmax_raw(mx, v);
-    }
-    wave_minmax(mn, mx);
+    float mn, mx;
+    wave_row_range(xr, len, mn, mx);
     if (ranges && lane == 0) { ((gfloat*)ranges)[2 * r + 0] = mn; ((gfloat*)ranges)[2 * r + 1] = mx; }
     const QParams p = qparams_double((double)mn, (double)mx, T.num_bits, T.symmetric);
     for (int i = lane; i < len; i += kWave) {
@@ -178,17 +158,12 @@ __global__ __launch_bounds__(kBlock) void bq_chunk_minmax_kernel(BqArgs a) {
 #pragma unroll
     for (int j = 0; j < kChunkPerThread; ++j) {
         const int64_t i = b + j * kBlock + threadIdx.x;
-        if (i < T.n) {
-            const float v = x[i];
-            mn = vmin_raw(mn, v);
-            mx = vmax_raw(mx, v);
-        }
+        if (i < T.n) range_fold(x[i], mn, mx);
     }
-    bq_block_minmax(mn, mx);
-    if (threadIdx.x == 0 && mn <= mx) {                // (false only for a chunk of NaNs, as in block_publish_minmax)
+    block_range(mn, mx);
+    if (threadIdx.x == 0) {                            // (nothing for a chunk of NaNs)
         uint32_t* slot = a.slots + 2 * ((int64_t)net * a.chunk_tensors + t);
-        atomicMax(slot + 0, ~enc_ord(mn));
-        atomicMax(slot + 1, enc_ord(mx));
+        range_publish(mn, mx, slot + 0, slot + 1);
     }
 }
 

@@ -6,7 +6,7 @@
 // asked, then quantises the row (the second read hits the cache) and writes the integer codes if asked.
 #include <vector>
 
-#include "dfq_common.hpp"
+#include "dfq_range.hpp"
 
 namespace dfq {
 
@@ -24,22 +24,11 @@ __global__ __launch_bounds__(kBlock) void row_seg_quant_kernel(const RowSegDev* 
     const int r = (int)blockIdx.x * (kBlock / kWave) + (int)threadIdx.x / kWave;
     if (r >= total_rows) return;                       // (wave-uniform)
     const int lane = threadIdx.x % kWave;
-    int lo = 0, hi = n_segs - 1;                       // largest s with row_begin[s] <= r
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (row_begin[mid] <= r) lo = mid; else hi = mid - 1;
-    }
-    const RowSegDev sg = segs[lo];
+    const RowSegDev sg = segs[find_segment(row_begin, n_segs, r)];
     const int64_t o = r - sg.row_begin;
     float* x = sg.data + o * sg.row_len;
-    float mn = INFINITY, mx = -INFINITY;
-    for (int64_t i = lane; i < sg.row_len; i += kWave) {
-        const float v = x[i];
-        mn = fminf(mn, v);
-        mx = fmaxf(mx, v);
-    }
-    mn = wave_min(mn);
-    mx = wave_max(mx);
+    float mn, mx;
+    wave_row_range(x, sg.row_len, mn, mx);
     if (sg.ranges && lane == 0) { sg.ranges[2 * o + 0] = mn; sg.ranges[2 * o + 1] = mx; }
     const QParams p = qparams_double((double)mn, (double)mx, sg.num_bits, sg.symmetric);
     for (int64_t i = lane; i < sg.row_len; i += kWave) {

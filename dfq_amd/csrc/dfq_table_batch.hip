@@ -5,12 +5,11 @@
 // per output row max|w| -- what dfq_row_range(signed) gives.  Both are selections, no arithmetic: the values are exact.
 //
 // The caller's float32 block [n_nets, stride] is cleared, then two launches, neither with a wait inside:
-//   1. bt_stream_kernel.  A tensor is cut into flat pieces of kTablePiece floats, one workgroup each, as bf_stream_kernel
-//      cuts them (dfq_fold_batch.hip): every lane moves 16 bytes per access whatever the row length, and depthwise rows of 9
+//   1. bt_stream_kernel.  A tensor is cut into flat pieces of kTablePiece floats, one workgroup each (batch_piece,
+//      dfq_batch_shared.hpp): every lane moves 16 bytes per access whatever the row length, and depthwise rows of 9
 //      or the stem's rows of 27 are just elements e with row e / row_len -- 455 rows of 9 to a workgroup, not a wave each.
 //      A lane folds the four elements of a vector into runs of one row.  The run its vector STARTS in goes through a
-//      segmented max-scan over the wave (rows are contiguous, so the lanes of one row are consecutive and the first of them
-//      follows from the row's first element: six shuffles, no keys exchanged); the last lane of every segment merges it into
+//      segmented max-scan over the wave (wave_head_scan); the last lane of every segment merges it into
 //      the piece's row table in LDS.  Runs that start inside a vector (one at most for rows of four elements or more) go to
 //      the LDS table directly.  The rows of the piece are then stored; only the first and the last row of a piece can
 //      continue in a neighbouring piece, and those two are merged into the block with atomicMax: |w| >= 0, so the bit
@@ -18,19 +17,19 @@
 //      merged into the tensor's two words as ~enc_ord(min), enc_ord(max), the order-preserving words of dfq_quant_batch.hip.
 //      Min and max do not depend on the order of the merges: the result is deterministic.
 //   2. bt_decode_kernel, a thread per tensor and network: the two merged words become the floats (min, max) in place.
-// NaN is skipped by every min / max (v_min_f32 / v_max_f32 return the other operand); a tensor of nothing but NaN ends as
-// (NaN, NaN), a row of nothing but NaN as 0.  Work is found from tables of ONE network: workgroup -> (network, piece of network 0) by a division, then the
-// piece's tensor from a table of network 0's pieces (one load).
+// NaN of either kind is skipped by every min / max (the rule of "Special values", include/dfq_hip.h; range_fold and
+// range_fold_abs, dfq_range.hpp); a tensor of nothing but NaN ends as (NaN, NaN), a row of nothing but NaN as 0.
 #include <math.h>
 
 #include <vector>
 
 #include "dfq_batch_shared.hpp"
+#include "dfq_range.hpp"
 
 namespace dfq {
 
-constexpr int kTableInFlight = 4;                               // 16-byte loads a lane issues before it uses the first
-constexpr int kTablePiece = kBlock * 4 * kTableInFlight;        // floats of one tensor a workgroup reads
+constexpr int kTableInFlight = kPieceInFlight;                  // 16-byte loads a lane issues before it uses the first
+constexpr int kTablePiece = kBatchPiece;                        // floats of one tensor a workgroup reads
 
 struct BtTensorDev {              // a weight of network 0
     const float* w;
@@ -53,99 +52,59 @@ struct BtArgs {
 // launch 1: (min, max) of the piece into its tensor's words, max|w| of every row the piece touches
 __global__ __launch_bounds__(kBlock) void bt_stream_kernel(BtArgs a) {
     __shared__ uint32_t row_max[kTablePiece];          // bits of max|w| of row first_row + i (a piece of rows of 1 has kTablePiece)
-    __shared__ float sh_mn[kBlock / kWave];
-    __shared__ float sh_mx[kBlock / kWave];
-    const int net = (int)(blockIdx.x / (unsigned)a.pieces_pn);
-    const int lp = (int)blockIdx.x - net * a.pieces_pn;
-    const int ti = a.piece_tensor[lp];
-    const BtTensorDev T = a.tensors[ti];
-    const int64_t start = (int64_t)(lp - T.piece_begin) * kTablePiece;
-    const int count = (int)(T.n - start < kTablePiece ? T.n - start : kTablePiece);
-    const int64_t first_row = start / T.row_len;
-    const uint32_t rem0 = (uint32_t)(start - first_row * T.row_len);      // of the piece's first element in its row
-    const uint32_t row_len = (uint32_t)T.row_len;
-    const int n_rows = (int)((rem0 + (uint32_t)count - 1u) / row_len) + 1;
-    const gfloat* w = (const gfloat*)(const float*)((const char*)T.w + a.delta[net]) + start;
+    BtTensorDev T;
+    const BatchPiece p = batch_piece(a.pieces_pn, a.piece_tensor, a.tensors, T);
+    const gfloat* w = (const gfloat*)(const float*)((const char*)T.w + a.delta[p.net]) + p.start;
     const int t = threadIdx.x;
     const int lane = t % kWave;
-    const int nv = count >> 2;
-    // every load of the piece back to back, a lane past the piece's end reading the last vector again (bf_stream_kernel)
+    const int nv = p.nv, n_rows = p.n_rows;
+    const uint32_t row_len = p.row_len;
     fvec4 x[kTableInFlight];
-    if (nv > 0) {
-#pragma unroll
-        for (int j = 0; j < kTableInFlight; ++j) {
-            const int v = j * kBlock + t;
-            x[j] = *(const gfvec4*)(w + 4 * (v < nv ? v : nv - 1));
-        }
-    }
-    const int tail = (nv << 2) + t;                    // a tensor's last piece may end in up to three single floats
-    float xt = 0.0f;
-    if (tail < count) xt = w[tail];
+    float xt;
+    batch_piece_load<false>(p, w, x, xt);
     for (int i = t; i < n_rows; i += kBlock) row_max[i] = 0u;
     __syncthreads();
     float mn = INFINITY, mx = -INFINITY;
-    if (nv > 0) {
 #pragma unroll
-        for (int j = 0; j < kTableInFlight; ++j) {
-            if (j * kBlock >= nv) break;               // (workgroup-uniform)
-            const int v = j * kBlock + t;
-            const bool live = v < nv;
-            const uint32_t e = rem0 + 4u * (uint32_t)v;
-            const uint32_t key = e / row_len;          // the row this vector starts in
-            uint32_t rem = e - key * row_len;
-            uint32_t r = key;
-            float head = 0.0f, run = 0.0f;
-            bool first = true;
+    for (int j = 0; j < kTableInFlight; ++j) {
+        if (j * kBlock >= nv) break;                   // (workgroup-uniform)
+        const int v = j * kBlock + t;
+        const bool live = v < nv;
+        const uint32_t e = p.rem0 + 4u * (uint32_t)v;
+        const uint32_t key = e / row_len;              // the row this vector starts in
+        uint32_t rem = e - key * row_len;
+        uint32_t r = key;
+        float head[1] = {0.0f}, run = 0.0f;
+        bool first = true;
 #pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float xv = x[j][c];
-                if (live) {
-                    mn = vmin_raw(mn, xv);
-                    mx = vmax_raw(mx, xv);
-                }
-                run = vmax_raw(run, fabsf(xv));
-                if (++rem == row_len) {                // the row ends behind this element
-                    rem = 0;
-                    if (first) { head = run; first = false; }
-                    else if (live) atomicMax(&row_max[r], __float_as_uint(run));
-                    ++r;
-                    run = 0.0f;
-                }
+        for (int c = 0; c < 4; ++c) {
+            if (live) range_fold(x[j][c], mn, mx);
+            range_fold_abs(x[j][c], run);
+            if (++rem == row_len) {                    // the row ends behind this element
+                rem = 0;
+                if (first) { head[0] = run; first = false; }
+                else if (live) atomicMax(&row_max[r], __float_as_uint(run));
+                ++r;
+                run = 0.0f;
             }
-            if (first) head = run;
-            else if (live && rem != 0) atomicMax(&row_max[r], __float_as_uint(run));
-            // segmented max-scan of `head` over the lanes whose vectors start in row `key`: they are consecutive, and the first
-            // of them is the first lane whose vector starts at or behind the row's first element
-            const int wave_e0 = (int)(rem0 + 4u * (uint32_t)(v - lane));
-            const int ahead = (int)(key * row_len) - wave_e0;
-            const int lane_start = ahead <= 0 ? 0 : (ahead + 3) >> 2;
-#pragma unroll
-            for (int d = 1; d < kWave; d <<= 1) {
-                const float o = __shfl(head, lane >= d ? lane - d : lane);
-                if (lane - d >= lane_start) head = vmax_raw(head, o);
-            }
-            // the last lane of the segment holds its maximum: r is the row the NEXT lane's vector starts in
-            if (live && (lane == kWave - 1 || v + 1 >= nv || r != key)) atomicMax(&row_max[key], __float_as_uint(head));
         }
+        if (first) head[0] = run;
+        else if (live && rem != 0) atomicMax(&row_max[r], __float_as_uint(run));
+        wave_head_scan(p, v, key, head, [](float (&h)[1], const float (&o)[1]) { h[0] = vmax_raw(h[0], o[0]); });
+        // the last lane of the segment holds its maximum: r is the row the NEXT lane's vector starts in
+        if (live && (lane == kWave - 1 || v + 1 >= nv || r != key)) atomicMax(&row_max[key], __float_as_uint(head[0]));
     }
-    if (tail < count) {
-        mn = vmin_raw(mn, xt);
-        mx = vmax_raw(mx, xt);
-        atomicMax(&row_max[(rem0 + (uint32_t)tail) / row_len], __float_as_uint(vmax_raw(0.0f, fabsf(xt))));
+    const int tail = (nv << 2) + t;
+    if (tail < p.count) {
+        range_fold(xt, mn, mx);
+        float run = 0.0f;
+        range_fold_abs(xt, run);
+        atomicMax(&row_max[(p.rem0 + (uint32_t)tail) / row_len], __float_as_uint(run));
     }
-    wave_minmax(mn, mx);
-    if (lane == 0) { sh_mn[t / kWave] = mn; sh_mx[t / kWave] = mx; }
-    __syncthreads();                                   // (the row table is complete behind it, too)
-    uint32_t* out = (uint32_t*)(a.out + (int64_t)net * a.stride);
-    if (t == 0) {
-#pragma unroll
-        for (int k = 1; k < kBlock / kWave; ++k) { mn = vmin_raw(mn, sh_mn[k]); mx = vmax_raw(mx, sh_mx[k]); }
-        if (mn <= mx) {                                // (false only for a piece of NaNs)
-            atomicMax(out + T.range_off + 0, ~enc_ord(mn));
-            atomicMax(out + T.range_off + 1, enc_ord(mx));
-        }
-    }
-    uint32_t* rows = out + T.row_off + first_row;
+    block_range(mn, mx);                               // (the row table is complete behind its barrier, too)
+    uint32_t* out = (uint32_t*)(a.out + (int64_t)p.net * a.stride);
+    if (t == 0) range_publish(mn, mx, out + T.range_off + 0, out + T.range_off + 1);      // (nothing for a piece of NaNs)
+    uint32_t* rows = out + T.row_off + p.first_row;
     for (int i = t; i < n_rows; i += kBlock) {
         const uint32_t bits = row_max[i];
         if (i == 0 || i == n_rows - 1) atomicMax(rows + i, bits);      // the two rows a neighbouring piece may hold a part of
@@ -193,7 +152,6 @@ int dfq_batch_table_plan_create(const dfq_batch_table_tensor* tensors, int32_t n
 
     std::vector<BtTensorDev> dev;
     std::vector<int32_t> piece_tensor;
-    int64_t pieces = 0;
     for (int i = 0; i < n_tensors; ++i) {
         const dfq_batch_table_tensor& q = tensors[i];
         if (!q.data) return fail_arg("%s: tensor %d: null weight", me, i);
@@ -206,13 +164,13 @@ int dfq_batch_table_plan_create(const dfq_batch_table_tensor* tensors, int32_t n
         if (q.row_offset < 0 || q.row_offset > stride - q.rows)
             return fail_arg("%s: tensor %d: %lld rows at %lld lie outside the stride %lld", me, i, (long long)q.rows, (long long)q.row_offset,
                             (long long)stride);
-        BtTensorDev T{q.data, q.rows * q.row_len, q.range_offset, q.row_offset, (int32_t)q.row_len, (int32_t)q.rows, (int32_t)pieces, 0};
-        const int64_t k = (T.n + kTablePiece - 1) / kTablePiece;
-        pieces += k;
-        if (pieces > 0x7fffffff / n_nets) return fail_arg("%s: too much work for one launch", me);
-        piece_tensor.insert(piece_tensor.end(), (size_t)k, (int32_t)i);
+        BtTensorDev T{q.data, q.rows * q.row_len, q.range_offset, q.row_offset, (int32_t)q.row_len, (int32_t)q.rows, 0, 0};
+        const int64_t begin = batch_add_pieces(piece_tensor, i, T.n, 0x7fffffff / n_nets);
+        if (begin < 0) return fail_arg("%s: too much work for one launch", me);
+        T.piece_begin = (int32_t)begin;
         dev.push_back(T);
     }
+    const int64_t pieces = (int64_t)piece_tensor.size();
     if (stride > INT64_MAX / 4 / n_nets) return fail_arg("%s: a block of %d x %lld floats", me, (int)n_nets, (long long)stride);
 
     dfq_batch_table_plan* p = new dfq_batch_table_plan();

@@ -293,7 +293,8 @@ int dfq_le_trace_blocks(dfq_le_plan* plan, const dfq_le_config* cfg, int32_t lau
  * Tensor primitives -- utils/quantize.py:23-76 (UniformQuantize.forward), :102-119 (QuantMeasure)
  * ---------------------------------------------------------------------------------------- */
 
-/* Special values in the reductions of this section and of dfq_quant_plan_* (the rule dfq_batch_table_plan states too): a
+/* Special values in the reductions of this section, of dfq_quant_plan_* and dfq_row_quant_plan_*, and of the batch plans
+ * dfq_batch_quant_plan, dfq_batch_error_plan and dfq_batch_table_plan (one implementation: csrc/dfq_range.hpp): a
  * NaN of any payload, quiet or signalling, is SKIPPED; a tensor, sample or segment of nothing but NaN gives (NaN, NaN);
  * infinities and denormals are ordinary values; min / max are selections, so every result is exact and only the sign of a
  * zero result is free.  The same on the 16-byte path and on the scalar path (unaligned pointers, tails).  torch's min() /
@@ -410,7 +411,8 @@ int dfq_row_quant_plan_run(dfq_row_quant_plan* plan, void* stream);
  * float32 block [n_nets, range_stride]: (min, max) per row of a per-row tensor, one pair for a per-tensor one.
  * Offsets are in elements of their block, -1 = none.  No workgroup waits for another: per-row tensors and per-tensor
  * tensors of at most dfq_batch_quant_register_elements() elements take one launch, longer per-tensor ones a min/max
- * launch in front of it (folding every chunk into one pair of slots per tensor and network, cleared first).  Every
+ * launch in front of it (folding every chunk into one pair of slots per tensor and network, cleared first).  NaN in a
+ * range: the rule of Special values above.  Every
  * tensor of network 0 must lie inside network 0's slot: nothing here can check that.  create: DFQ_ERR_ARG (and dfq_last_error) for empty / null arguments, bit widths outside
  * [2, 16] (per row) or [1, 30] (per tensor), a symmetric per-tensor tensor of 1 bit (qmax = 0), 1-byte codes of more than 8 bits, offsets that overflow their stride.
  * Synchronises (create only); run is asynchronous on `stream`. */
@@ -527,8 +529,8 @@ int64_t dfq_batch_fold_plan_elements(const dfq_batch_fold_plan* plan);
  * per tensor (min, max) at `range_offset` -- the pair dfq_quant_plan_measure gives, the `mi, ma` of convert_ncnn.py:186-187
  * -- and per output row max|w| at `row_offset` (`rows` floats) -- what dfq_row_range(signed) gives: the per-channel form of
  * the same scale.  Both come from the same read; they are selections, so every value is exact (the sign of a zero is +
- * for a row's maximum and either for a tensor's bound), infinities included.  NaN is skipped; a tensor of nothing but NaN
- * gives (NaN, NaN), a row of nothing but NaN gives 0.  A run clears the WHOLE block, then two launches: one pass over the
+ * for a row's maximum and either for a tensor's bound), infinities included.  NaN is skipped (the rule of Special values
+ * above); a tensor of nothing but NaN gives (NaN, NaN), a row of nothing but NaN gives 0.  A run clears the WHOLE block, then two launches: one pass over the
  * weights (flat pieces of a tensor, 16-byte loads, any row length; partial results are merged with atomicMax of
  * order-preserving words, which is deterministic for min / max), then a thread per tensor and network that turns the merged
  * words into floats; no workgroup waits for another.  Offsets are in floats from a network's part of the block; the slots of
@@ -563,7 +565,7 @@ int32_t dfq_batch_table_plan_launches(const dfq_batch_table_plan* plan);
  * constant tensor or row takes the max(scale, 1e-8) branch of the recipe.  Every sum is a float64 accumulation of float32
  * terms (e^2 and w^2 formed in float64, exactly) in an order of the plan's own that is fixed: two runs are bit-identical,
  * network n's values do not depend on n_nets or on n's place in the batch, no floating-point atomic is used.  NaN is
- * skipped by the ranges (the rule stated above); a tensor holding NaN gets NaN sums, nothing else does.  Nothing else in
+ * skipped by the ranges (the rule of Special values above); a tensor holding NaN gets NaN sums, nothing else does.  Nothing else in
  * the block is touched.  A clear of the plan's own range words, then three launches (ranges, errors, a fold of the
  * pieces' sums in rising order); no workgroup waits for another.  Offsets are in doubles from a network's part of the
  * block; the slots of different tensors must not overlap (not checked).  create: DFQ_ERR_ARG (and dfq_last_error) for null

@@ -5,7 +5,7 @@ The contract is equality, not closeness.  The plan selects values (a tensor's mi
 nothing, so ``ranges(n)`` / ``row_absmax(n)`` are compared with ``==`` against ``ncnn_table.weight_ranges`` /
 ``prims.row_range(w, signed=True)`` and numpy (which leaves the sign of a zero free and nothing else), and the tables are
 compared string for string with ``ncnn_table.calibration_table`` on each network alone, on the CPU emulation and on the
-MI355X alike.  A tensor holding NaN is outside that contract: it must not fault and must not reach any other tensor."""
+MI355X alike.  A tensor holding NaN must not fault and must not reach any other tensor."""
 import copy
 import ctypes
 import json
