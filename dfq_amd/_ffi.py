@@ -88,6 +88,15 @@ class DfqBatchErrorConfig(Structure):
     _fields_ = [('num_bits', c_int32), ('symmetric', c_int32), ('per_row', c_int32), ('pad', c_int32)]
 
 
+class DfqBatchClipTensor(Structure):
+    _fields_ = [('data', c_void_p), ('rows', c_int64), ('row_len', c_int64), ('out_offset', c_int64)]
+
+
+class DfqBatchClipConfig(Structure):
+    _fields_ = [('num_bits', c_int32), ('symmetric', c_int32), ('per_row', c_int32), ('candidates', c_int32),
+                ('alpha_min', c_double), ('apply', c_int32), ('pad', c_int32)]
+
+
 class DfqBatchActResult(Structure):
     _fields_ = [('step_begin', c_int32), ('step_count', c_int32)]
 
@@ -223,6 +232,11 @@ SIGNATURES = {
     'dfq_batch_error_plan_run': (c_int32, [c_void_p, c_void_p]),
     'dfq_batch_error_plan_destroy': (None, [c_void_p]),
     'dfq_batch_error_plan_launches': (c_int32, [c_void_p]),
+    'dfq_batch_clip_plan_create': (c_int32, [POINTER(DfqBatchClipTensor), c_int32, POINTER(DfqBatchClipConfig), POINTER(c_void_p),
+                                             c_int32, c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_void_p)]),
+    'dfq_batch_clip_plan_run': (c_int32, [c_void_p, c_void_p]),
+    'dfq_batch_clip_plan_destroy': (None, [c_void_p]),
+    'dfq_batch_clip_plan_launches': (c_int32, [c_void_p]),
     'dfq_batch_act_plan_create': (c_int32, [POINTER(DfqBatchActResult), c_int32, POINTER(DfqBatchActStep), c_int32,
                                             POINTER(DfqBatchActSource), c_int32, POINTER(c_void_p), c_int32, c_float, c_float,
                                             c_void_p, c_int64, POINTER(c_void_p)]),

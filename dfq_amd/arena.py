@@ -40,6 +40,11 @@ leave per weight the float64 sums of w^2 and of e, |e|, e^2 for one to four quan
 for bit what ``quant_plan`` would store minus w; ``quantize_error`` turns them into the reference's 'sum' and 'mean', the mean
 squared error and the SQNR (tests/test_batch_error.py).  It changes nothing, so it can stand anywhere in the sequence -- in
 front of ``le_plan`` and behind it shows what equalisation bought.
+``clip_plan`` acts on that signal: per tensor or per output row it searches the one of K ranges, shrunk from the unit's
+(min, max), under which the quantiser has the least sum e^2, and clamps the weights to it -- ``clip_weight`` (dfq.py:167-170)
+with a searched bound, standing where ``absorb_plan(range_clip=...)`` clips: fold_plan -> le_plan -> absorb_plan -> clip_plan
+-> bc_plan -> quant_plan -> act_range_plan.  A unit's own (min, max) is then the chosen range, so the plans behind it are
+unchanged (tests/test_batch_clip.py).
 """
 from __future__ import annotations
 
@@ -584,6 +589,33 @@ class NetworkBatch:
             out.append(res)
         return out
 
+    def clip_plan(self, bit_weight=8, per_channel=False, signed=False, candidates=32, alpha_min=0.5, apply=True, keep_errors=False):
+        """One plan (BatchClipPlan) for the MSE-optimal clipping of every ``targ_type`` weight of every network: per tensor,
+        or per output row with ``per_channel``, the one of ``candidates`` ranges -- shrunk from the unit's (min, max) toward
+        zero by factors from 1 down to ``alpha_min`` -- under which the ``bit_weight``-bit quantiser (``signed``: the symmetric
+        recipe) has the least sum of squared errors; with ``apply`` the weights are clamped to it in place, the reference's
+        ``clip_weight`` (dfq.py:167-170) with a searched bound.  The definition is the comment of dfq_batch_clip_plan_create
+        (include/dfq_hip.h).  A unit's own (min, max) is then the chosen range, so ``bc_plan``, ``quant_plan``,
+        ``table_plan`` and ``error_plan`` see it unchanged: the plan stands where ``absorb_plan(range_clip=...)`` clips,
+        behind equalisation and absorption, in front of bias correction.  ``keep_errors``: every candidate's sum e^2 stays
+        readable (``errors(n)``).  ValueError for a bit width that is not an int in [2, 16], ``candidates`` not an int in
+        [1, 64], an ``alpha_min`` that is not a number in (0, 1]; RuntimeError for a weight of network 0 that has left its
+        slot."""
+        self._ready('clip_plan')
+        return BatchClipPlan(self, bit_weight, per_channel, signed, candidates, alpha_min, apply, keep_errors)
+
+    def clip_weight_mse(self, bit_weight=8, per_channel=False, signed=False, candidates=32, alpha_min=0.5):
+        """clip_plan(apply=True, keep_errors=True) + run + synchronise + close: one
+        ``OrderedDict[key -> {'range', 'chosen', 'err_minmax', 'err'}]`` per network -- the chosen (l, h), k*, and sum e^2 under
+        the min/max range and under the chosen one (numpy values on the host)."""
+        plan = self.clip_plan(bit_weight, per_channel, signed, candidates, alpha_min, True, True)
+        try:
+            plan.run()
+            _ffi.synchronize()
+            return [plan.report(n) for n in range(len(self.nets))]
+        finally:
+            plan.close()
+
     def _format_tables(self, names, per_channel, views, block, act_of):
         """the host side of ``calibration_tables``: the strings, by the recipe the single-network function uses"""
         tables = []
@@ -881,6 +913,54 @@ class BatchErrorPlan(_BatchPlan):
             out[key] = {'numel': numel, 'sum_sq_w': float(row[off]), 'sum': sums[:, 0].copy(), 'sum_abs': sums[:, 1].copy(),
                         'sum_sq': sums[:, 2].copy()}
         return out
+
+
+class BatchClipPlan(_BatchPlan):
+    """MSE-optimal weight clipping of every network of a NetworkBatch (dfq_batch_clip_plan, include/dfq_hip.h, which holds
+    the definition): network 0's table of ``targ_type`` weights plus the batch's base addresses.  ``run()`` enqueues on the
+    current stream -- one launch for the units searched in registers and the long rows, three more (four with ``apply``) for
+    per-tensor tensors cut into flat pieces; with ``apply`` the weights are clamped in place, and only where the clamp
+    changes them.  The results lie in blocks the plan owns, torch tensors that outlive ``close()``: ``range_block`` float32
+    [n_nets, units, 2], ``chosen_block`` int32 [n_nets, units] and, with ``keep_errors``, ``error_block`` float64
+    [n_nets, units, candidates]; a unit is a tensor, or an output row with ``per_channel``.  Two runs of a plan without
+    ``apply`` give bit-equal blocks, and a network's part does not depend on the others."""
+    _c = 'dfq_batch_clip_plan'
+
+    def __init__(self, batch, bit_weight, per_channel, signed, candidates, alpha_min, apply, keep_errors):
+        cfg = _dfq._clip_config('clip_plan', bit_weight, per_channel, signed, candidates, alpha_min, apply)
+        super().__init__(batch)
+        g0 = batch.nets[0][0]
+        tt = tuple(batch.targ_type)
+        layers = [(key, layer.weight) for key, layer in g0.items() if type(layer) in tt]
+        if not layers:
+            raise ValueError('clip_plan: the batch has no {} layer'.format(tt))
+        self.bit_weight, self.per_channel, self.signed = int(cfg.num_bits), bool(cfg.per_row), bool(cfg.symmetric)
+        self.candidates, self.alpha_min, self.apply = int(cfg.candidates), float(cfg.alpha_min), bool(cfg.apply)
+        self.keys = [key for key, _ in layers]
+        self.n_nets, self.n_tensors = len(batch.nets), len(layers)
+        self.elements = sum(w.numel() for _, w in layers)               # weights per network
+        lay = self._lay = _dfq._ClipLayout([(key, batch._in_slot(key, 'weight', w), int(w.shape[0]), w.numel() // int(w.shape[0]))
+                                            for key, w in layers], self.n_nets, cfg, keep_errors, batch.stage.device)
+        self.range_block, self.chosen_block, self.error_block = lay.range_block, lay.chosen_block, lay.error_block
+        self._create((lay.table, len(layers), ctypes.byref(cfg)), *lay.block_args())
+
+    def ranges(self, n):
+        """{graph key: float32 [2] (or [O, 2] per channel) view, the chosen (l, h) of network n's weight}"""
+        return self._lay.ranges(n)
+
+    def chosen(self, n):
+        """{graph key: int32 0-dim (or [O]) view, k* of network n's weight: 0 is the unit's own (min, max)}"""
+        return self._lay.chosen(n)
+
+    def errors(self, n):
+        """{graph key: float64 [K] (or [O, K]) view, sum e^2 under every candidate}; RuntimeError without ``keep_errors``"""
+        return self._lay.errors(n)
+
+    def report(self, n):
+        """``OrderedDict[key -> {'range', 'chosen', 'err_minmax', 'err'}]`` of network n (``keep_errors`` plans)"""
+        if self.error_block is None:
+            raise RuntimeError('clip_plan: the errors were not kept (keep_errors=True)')
+        return self._lay.report(n)
 
 
 class BatchAbsorbPlan(_BatchPlan):

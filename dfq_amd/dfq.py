@@ -1146,6 +1146,116 @@ def clip_weight(graph, range_clip=[-15, 15], targ_type=[nn.Conv2d, nn.Linear]):
 
 
 # ------------------------------------------------------------------------------------------------
+# extension: clip_weight with a searched bound (dfq_batch_clip_plan, include/dfq_hip.h)
+# ------------------------------------------------------------------------------------------------
+def _clip_config(who, bits, per_channel, signed, candidates, alpha_min, apply):
+    """the arguments of the range search as a DfqBatchClipConfig, or ValueError('<who>: ...')"""
+    import numbers
+    ints = (int, numbers.Integral)
+    if isinstance(bits, bool) or not isinstance(bits, ints) or not 2 <= bits <= 16:
+        raise ValueError('{}: the bit width must be an int in [2, 16], got {!r}'.format(who, bits))
+    if isinstance(candidates, bool) or not isinstance(candidates, ints) or not 1 <= candidates <= 64:
+        raise ValueError('{}: candidates must be an int in [1, 64], got {!r}'.format(who, candidates))
+    if isinstance(alpha_min, bool) or not isinstance(alpha_min, numbers.Real) or not 0.0 < float(alpha_min) <= 1.0:
+        raise ValueError('{}: alpha_min must be a number in (0, 1], got {!r}'.format(who, alpha_min))
+    return _ffi.DfqBatchClipConfig(int(bits), int(bool(signed)), int(bool(per_channel)), int(candidates), float(alpha_min),
+                                   int(bool(apply)), 0)
+
+
+class _ClipLayout:
+    """The tensor table and the output blocks of one dfq_batch_clip_plan.  ``layers``: [(graph key, address of the weight in
+    network 0, rows, row_len)].  A unit is a tensor, or an output row with ``per_row``; the blocks are torch tensors
+    ``range_block`` float32 [n_nets, units, 2], ``chosen_block`` int32 [n_nets, units] and, with ``keep_errors``,
+    ``error_block`` float64 [n_nets, units, K]."""
+
+    def __init__(self, layers, n_nets, cfg, keep_errors, device):
+        self.per_row, self.candidates = bool(cfg.per_row), int(cfg.candidates)
+        entries, self.views, stride = [], [], 0            # (graph key, first unit, units)
+        for key, address, rows, row_len in layers:
+            units = rows if self.per_row else 1
+            entries.append(_ffi.DfqBatchClipTensor(address, rows, row_len, stride))
+            self.views.append((key, stride, units))
+            stride += units
+        self.stride, self.n_tensors = stride, len(entries)
+        self.table = (_ffi.DfqBatchClipTensor * len(entries))(*entries)
+        self.range_block = torch.zeros((n_nets, stride, 2), dtype=torch.float32, device=device)
+        self.chosen_block = torch.zeros((n_nets, stride), dtype=torch.int32, device=device)
+        self.error_block = torch.zeros((n_nets, stride, self.candidates), dtype=torch.float64, device=device) if keep_errors else None
+
+    def block_args(self):
+        """(ranges, chosen, errors, stride) as dfq_batch_clip_plan_create takes them"""
+        return (self.range_block.data_ptr(), self.chosen_block.data_ptr(),
+                None if self.error_block is None else self.error_block.data_ptr(), self.stride)
+
+    def _views_of(self, row, tail):
+        if self.per_row:
+            return OrderedDict((key, row[off:off + units]) for (key, off, units) in self.views)
+        return OrderedDict((key, row[off:off + 1].view(tail)) for (key, off, _) in self.views)
+
+    def ranges(self, n):
+        return self._views_of(self.range_block[n], (2,))
+
+    def chosen(self, n):
+        return self._views_of(self.chosen_block[n], ())
+
+    def errors(self, n):
+        if self.error_block is None:
+            raise RuntimeError('clip_plan: the errors were not kept (keep_errors=True)')
+        return self._views_of(self.error_block[n], (self.candidates,))
+
+    def report(self, n):
+        """``OrderedDict[key -> {'range', 'chosen', 'err_minmax', 'err'}]`` of network n as numpy values on the host: the chosen
+        (l, h), k*, and sum e^2 of the min/max range (candidate 0) and of the chosen one; three device-to-host copies"""
+        rng, cho, err = self.range_block[n].cpu().numpy(), self.chosen_block[n].cpu().numpy(), self.error_block[n].cpu().numpy()
+        out = OrderedDict()
+        for key, off, units in self.views:
+            k = cho[off:off + units]
+            e = err[off:off + units]
+            best = e[range(units), k]
+            if self.per_row:
+                out[key] = {'range': rng[off:off + units].copy(), 'chosen': k.copy(), 'err_minmax': e[:, 0].copy(), 'err': best}
+            else:
+                out[key] = {'range': rng[off].copy(), 'chosen': int(k[0]), 'err_minmax': float(e[0, 0]), 'err': float(best[0])}
+        return out
+
+
+def clip_weight_mse(graph, bits_weight=8, per_channel=False, signed=False, candidates=32, alpha_min=0.5,
+                    targ_type=[nn.Conv2d, nn.Linear]):
+    """``clip_weight`` with a searched bound (extension): every ``targ_type`` weight -- every output row of it with
+    ``per_channel`` -- is clamped in place to the one of ``candidates`` ranges, shrunk from its (min, max) by factors from 1
+    down to ``alpha_min``, under which the ``bits_weight``-bit quantiser (``signed``: the symmetric recipe) has the least sum
+    of squared errors.  The definition is the comment of dfq_batch_clip_plan_create (include/dfq_hip.h); the single-network
+    form of ``NetworkBatch.clip_weight_mse``, the same plan over a batch of one.  Afterwards a weight's own (min, max) is the
+    chosen range, which is what ``bias_correction``, ``quantize_targ_layer`` and the ncnn table take: call it where
+    ``clip_weight`` stands, behind equalisation and absorption, in front of bias correction.  Returns
+    ``OrderedDict[key -> {'range', 'chosen', 'err_minmax', 'err'}]``.  ValueError for a bit width that is not an int in
+    [2, 16], ``candidates`` not an int in [1, 64], an ``alpha_min`` that is not a number in (0, 1]."""
+    cfg = _clip_config('clip_weight_mse', bits_weight, per_channel, signed, candidates, alpha_min, True)
+    lib = _ffi.lib()
+    layers = [(key, graph[key].weight) for key in graph if type(graph[key]) in targ_type]
+    if not layers:
+        raise ValueError('clip_weight_mse: the graph has no {} layer'.format(tuple(targ_type)))
+    with torch.no_grad():
+        stage = _ffi.entry_stage()
+        stage.prefetch([w for _, w in layers])
+        bufs = [stage.bind(w) for _, w in layers]
+        lay = _ClipLayout([(key, buf.data_ptr(), int(w.shape[0]), w.numel() // int(w.shape[0])) for (key, w), buf in zip(layers, bufs)],
+                          1, cfg, True, stage.device)
+        bases = (ctypes.c_void_p * 1)(bufs[0].data_ptr())
+        plan = ctypes.c_void_p()
+        _ffi.check(lib.dfq_batch_clip_plan_create(lay.table, lay.n_tensors, ctypes.byref(cfg), bases, 1, *lay.block_args(),
+                                                  ctypes.byref(plan)))
+        try:
+            _ffi.check(lib.dfq_batch_clip_plan_run(plan, _ffi.stream_arg()))
+            _ffi.synchronize()
+            report = lay.report(0)
+        finally:
+            lib.dfq_batch_clip_plan_destroy(plan)
+        stage.writeback()
+    return report
+
+
+# ------------------------------------------------------------------------------------------------
 # dfq.py:173-293
 # ------------------------------------------------------------------------------------------------
 class BCPlan:

@@ -26,7 +26,7 @@ import torch.nn as nn
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from dfq_amd import ncnn_table, synthetic                                              # noqa: E402
-from dfq_amd.dfq import bias_absorption, bias_correction, cross_layer_equalization    # noqa: E402
+from dfq_amd.dfq import bias_absorption, bias_correction, clip_weight_mse, cross_layer_equalization    # noqa: E402
 from dfq_amd.improve_dfq import _swap_modules, set_update_stat, update_quant_range      # noqa: E402
 from dfq_amd.utils.quantize import QuantMeasure                                        # noqa: E402
 from dfq_amd.zeroq import getDistilData                                                # noqa: E402
@@ -65,6 +65,9 @@ def main(argv=None):
     ap.add_argument('--bits-weight', type=int, default=8)
     ap.add_argument('--bits-bias', type=int, default=16)
     ap.add_argument('--absorption', action='store_true')
+    ap.add_argument('--clip_weight_mse', '--clip-weight-mse', action='store_true',
+                    help='clamp every weight (every output row with --per-channel) to its MSE-optimal range for --bits-weight, where '
+                         'the reference has clip_weight (extension, off by default)')
     ap.add_argument('--max-sweeps', type=int, default=None)
     ap.add_argument('--distill-range', action='store_true', help='activation ranges from ZeroQ-distilled batches (config 5)')
     ap.add_argument('--dis-batch-size', type=int, default=8)
@@ -97,6 +100,11 @@ def main(argv=None):
     sweeps = engine.last_equalization['sweeps']
     if args.absorption:
         bias_absorption(graph, res, bottoms, 3)                                                     # :156
+    if args.clip_weight_mse:                                                                        # where :163-164 has clip_weight
+        report = clip_weight_mse(graph, args.bits_weight, per_channel=args.per_channel, signed=args.signed, targ_type=targ_layer)
+        print('clip_weight_mse: {} of {} ranges narrowed'.format(sum(int((r['chosen'] != 0).sum()) if args.per_channel else int(r['chosen'] != 0)
+                                                                     for r in report.values()),
+                                                                 sum(len(r['chosen']) if args.per_channel else 1 for r in report.values())))
     if args.per_channel:
         bias_correction(graph, bottoms, targ_layer, bits_weight=args.bits_weight, signed=args.signed, per_channel=True)
     else:

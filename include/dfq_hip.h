@@ -294,7 +294,7 @@ int dfq_le_trace_blocks(dfq_le_plan* plan, const dfq_le_config* cfg, int32_t lau
  * ---------------------------------------------------------------------------------------- */
 
 /* Special values in the reductions of this section, of dfq_quant_plan_* and dfq_row_quant_plan_*, and of the batch plans
- * dfq_batch_quant_plan, dfq_batch_error_plan and dfq_batch_table_plan (one implementation: csrc/dfq_range.hpp): a
+ * dfq_batch_quant_plan, dfq_batch_error_plan, dfq_batch_clip_plan and dfq_batch_table_plan (one implementation: csrc/dfq_range.hpp): a
  * NaN of any payload, quiet or signalling, is SKIPPED; a tensor, sample or segment of nothing but NaN gives (NaN, NaN);
  * infinities and denormals are ordinary values; min / max are selections, so every result is exact and only the sign of a
  * zero result is free.  The same on the 16-byte path and on the scalar path (unaligned pointers, tails).  torch's min() /
@@ -594,6 +594,67 @@ int dfq_batch_error_plan_run(dfq_batch_error_plan* plan, void* stream);
 void dfq_batch_error_plan_destroy(dfq_batch_error_plan* plan);
 /* kernel launches per run (3); the clear of the range words in front of them is a memset */
 int32_t dfq_batch_error_plan_launches(const dfq_batch_error_plan* plan);
+
+/* MSE-optimal weight clipping of a whole batch of networks of one architecture (extension; the reference's clip_weight,
+ * dfq.py:167-170, with a searched bound per unit in place of one constant for the network).  `tensors` lists the weights of
+ * the FIRST of `n_nets` networks; network n's copy of a tensor lies bases[n] - bases[0] bytes further.
+ * DEFINITION.  A UNIT is a tensor, or an output row with `per_row`.  It has (mn, mx) by the rule of Special values above: NaN
+ * skipped, nothing but NaN gives (NaN, NaN).  With K = `candidates` in [1, 64] and `alpha_min` in (0, 1]:
+ *   shrink factor   in float64, a_k = 1 for K = 1, else 1 - k (1 - alpha_min) / (K - 1), k = 0 .. K - 1
+ *   fixed point     z = min(max(0, mn), mx): the ends shrink toward zero, or toward the end nearest zero of a one-signed
+ *                   unit, so a range is never inverted
+ *   candidate ends  l_k = (float)(z + a_k (mn - z)), h_k = (float)(z + a_k (mx - z)) in float64; candidate 0 is (mn, mx)
+ *   error           err_k = sum_i e_i^2, e_i = fake_quant(c_i; qparams(l_k, h_k, num_bits, symmetric)) - w_i in float32 with
+ *                   c_i = w_i clamped to (l_k, h_k) as `apply` clamps it, the recipe of dfq_fake_quant in range_mode 0: bit
+ *                   for bit what dfq_batch_quant_plan_run stores for the clamped unit, whose range is then (l_k, h_k), minus
+ *                   the weight as it is -- so err_k* is the error of what `apply` and the quantiser leave, and it is never
+ *                   above err_0, that of min/max quantisation.  Under the asymmetric recipe the quantiser saturates at
+ *                   (l_k, h_k) itself and the clamp inside e_i changes no bit (unless the scale sits at its floor of 1e-8);
+ *                   under the symmetric one the grid spans +-max(|l_k|, |h_k|) and only the clamp cuts at the shorter end.
+ *                   The square and the sum are float64; the order of the sum depends on
+ *                   the tensor's shape alone and no floating-point atomic is used: two runs are bit-identical, and network
+ *                   n's values do not depend on n_nets or on n's place in the batch
+ *   choice          k* = argmin err_k, the smallest k on a tie: the comparison is err < best starting from candidate 0, so a
+ *                   unit whose errors are NaN or all infinite (a NaN or an infinity among its weights, nothing but NaN)
+ *                   keeps k* = 0
+ *   apply           w <- w < l ? l : (w > h ? h : w) with (l, h) of k*; NaN and -0.0 pass through; where k* = 0 nothing is
+ *                   stored, elsewhere only what the clamp changed.  The unit's own (min, max) is then (l, h), which every
+ *                   quantiser of this library takes from the weights -- none of them has to know about the search.
+ * Outputs per unit, in blocks of the caller [n_nets][stride] units, a tensor's first unit at `out_offset`, its rows behind
+ * it: `ranges` float32 [.., 2] = (l, h) of k*; `chosen` int32 = k*; `errors` float64 [.., K] = every err_k (null: not
+ * written).  Nothing else in the blocks is touched.  Units of at most dfq_batch_quant_register_elements() elements stay in
+ * registers from the min/max through all candidates to the clamp (one launch, one read, at most one write); longer rows get
+ * a looping wave; longer per-tensor tensors three launches over flat pieces (ranges, errors per piece, fold and choice) and
+ * a fourth with `apply`.  No workgroup waits for another.
+ * create: DFQ_ERR_ARG (and dfq_last_error) for null or empty tables, a null configuration, num_bits outside [2, 16],
+ * candidates outside [1, 64], alpha_min not in (0, 1] (NaN included), a weight that is null or not 16-byte aligned, rows <= 0
+ * or row_len <= 0, a null `ranges` or `chosen` block, stride <= 0, an offset outside the stride, null bases, networks that
+ * are not 16-byte aligned to network 0.  Every tensor of network 0 must lie inside network 0's slot: nothing here can check
+ * that.  Synchronises (create only); run is asynchronous on `stream`. */
+typedef struct dfq_batch_clip_plan dfq_batch_clip_plan;
+typedef struct dfq_batch_clip_tensor { /* addresses in network 0 */
+    float* data;            /* the layer's weight [rows, row_len], clamped in place with `apply`                     */
+    int64_t rows;
+    int64_t row_len;
+    int64_t out_offset;     /* units into a network's part of the blocks: 1 unit, or `rows` with per_row              */
+} dfq_batch_clip_tensor;
+typedef struct dfq_batch_clip_config {
+    int32_t num_bits;
+    int32_t symmetric;      /* the signed recipe                                                                     */
+    int32_t per_row;        /* a unit is an output row instead of a tensor                                           */
+    int32_t candidates;     /* K                                                                                     */
+    double alpha_min;
+    int32_t apply;          /* clamp the weights to the chosen ranges                                                */
+    int32_t pad;
+} dfq_batch_clip_config;
+
+int dfq_batch_clip_plan_create(const dfq_batch_clip_tensor* tensors, int32_t n_tensors, const dfq_batch_clip_config* config,
+                               const void* const* bases, int32_t n_nets, float* ranges, int32_t* chosen, double* errors, int64_t stride,
+                               dfq_batch_clip_plan** out_plan);
+int dfq_batch_clip_plan_run(dfq_batch_clip_plan* plan, void* stream);
+void dfq_batch_clip_plan_destroy(dfq_batch_clip_plan* plan);
+/* kernel launches per run: 1 for the units in registers and the long rows, 3 (4 with apply) for the flat pieces */
+int32_t dfq_batch_clip_plan_launches(const dfq_batch_clip_plan* plan);
 
 /* Analytic activation ranges of a whole batch of networks of one architecture (extension; set_quant_minmax,
  * utils/layer_transform.py:347-609, main_cls.py:188, for every network of a batch at once).  The caller walks the graph of
