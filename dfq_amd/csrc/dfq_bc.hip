@@ -476,20 +476,24 @@ __device__ __forceinline__ void bc_step_body(const BcStepDev& st, int blk, const
         return bc_row_qparams(qp, sh_q[2 * li + 0], sh_q[2 * li + 1]);
     };
     // Everything of the matvec that does not depend on the expectation is settled here, before the wait: where in sh_E each
-    // slot's factor will lie (a byte offset < 64 Ki, two per register) and which slots take part at all (a slot outside the
-    // row or the layer holds eps = 0: its product is a zero of either sign, and adding one to a sum that started at +0.0
-    // changes no bit -- the row it would poison with 0 x inf is a row that is discarded, or one the clamped element belongs to).
+    // slot's factor will lie (a byte offset < 64 Ki, two per register) and which slots take part at all.  A slot outside the
+    // row or the layer, and a slot nobody owns, holds eps = 0 AND takes its factor from the word behind the expectation
+    // (sh_E[kExp], kept at 0.0f): its product is 0 x 0 = +0.0 whatever the expectation holds, and adding that to a sum that
+    // started at +0.0 changes no bit.  (Until the adversarial tests such a slot read a real element of the expectation: 0 x inf
+    // is NaN, not zero, and one infinite beta~ left NaN in every row where the general body -- which selects -- leaves inf.)
     // Until round 5 the index arithmetic, the predicate and the LDS read of every slot sat between the arrival of the
     // expectation and the row's sum, one slot after the other, and the compiler had sunk the quantiser there too: a third
     // of a MobileNetV2's dependent chain (profiles/r05_bc_chain.txt).
     const int num_group = st.expect_len / in;
     const int step_o = st.out_ch / num_group;
+    constexpr uint32_t kZeroOff = (uint32_t)kExp * 4u;               // byte offset of the zero word (<= 32 Ki: fits the 16 bits)
+    static_assert(kExp * 4 < (1 << 16), "the zero word must be addressable by a 16-bit offset");
+    if ((kOneGroup || DFQ_BC_BATCH_HOIST) && tid == 0) sh_E[kExp] = 0.0f;   // (every merge ends with a barrier: visible to the row sums)
     uint32_t eo[kBcRegs / 2];
 #pragma unroll
     for (int u = 0; u < kBcRegs / 2; ++u) eo[u] = 0u;
     {
         int rg = 0, c = 0;
-        uint32_t off0 = 0u;
 #pragma unroll
         for (int u = 0; u < kBcRegs; ++u) {
             if (u < n_slots) {
@@ -500,8 +504,7 @@ __device__ __forceinline__ void bc_step_body(const BcStepDev& st, int blk, const
                 const bool ok = r_local < rw && row_u < st.out_ch && col_u < in;
                 if (kOneGroup || DFQ_BC_BATCH_HOIST) {
                     const int g = (num_group == 1) ? 0 : bc_small_div(min(row_u, st.out_ch - 1), step_o);
-                    const uint32_t off = (uint32_t)(g * in + min(col_u, in - 1)) * 4u;
-                    if (u == 0) off0 = off;
+                    const uint32_t off = ok ? (uint32_t)(g * in + col_u) * 4u : kZeroOff;
                     eo[u >> 1] |= off << (16 * (u & 1));
                 }
                 const QParams uq = slot_qp(row_u);
@@ -525,8 +528,8 @@ __device__ __forceinline__ void bc_step_body(const BcStepDev& st, int blk, const
                 asm volatile("" : "+v"(ev[u]));
                 if (++c == chunks) { c = 0; ++rg; }
             } else if (kOneGroup) {
-                ev[u] = 0.0f;                                    // a slot nobody owns: factor = this lane's first one
-                eo[u >> 1] |= off0 << (16 * (u & 1));
+                ev[u] = 0.0f;                                    // a slot nobody owns: 0 x the zero word
+                eo[u >> 1] |= kZeroOff << (16 * (u & 1));
             }
         }
     }
@@ -822,7 +825,8 @@ __device__ __forceinline__ void bc_step_body(const BcStepDev& st, int blk, const
             // "matvec" of dfq.py:281-287 is one product, accumulated in float64 and rounded once like a step's row
             const BcFoldDev F = folds[st.fold];
             const float e = F.src_relu ? moment : nb;
-            const float fcorr = (float)((double)f_eps * (double)e);
+            // (the sum starts at +0.0 like a row's: a product of -0.0 -- eps exactly 0, E negative -- is +0.0 in the step's own sum)
+            const float fcorr = (float)(0.0 + (double)f_eps * (double)e);
             const float fneg = -fcorr;
             F.corr[o] = fcorr;
             F.bias[o] = f_bias + fneg;
@@ -856,7 +860,7 @@ __device__ __forceinline__ void bc_load_step(const BcStepDev* __restrict__ entry
 template <int kExp>
 __global__ __launch_bounds__(kBlock) void bc_step_kernel(BcStepDev st_inline, const BcStepDev* __restrict__ table,
                                                          const BcSourceDev* __restrict__ sources, const BcFoldDev* __restrict__ folds, int symmetric) {
-    __shared__ float sh_E[kExp];
+    __shared__ float sh_E[kExp + 1];       // (+ the zero word of bc_step_body)
     __shared__ float sh_corr[kBlock];
     __shared__ int sh_flag;
     union { BcStepDev st; uint32_t u[kStepWords]; } desc;
@@ -871,7 +875,7 @@ template <int kExp>
 __global__ __launch_bounds__(kBlock) void bc_step_kernel_rows(BcStepDev st_inline, const BcStepDev* __restrict__ table,
                                                               const BcSourceDev* __restrict__ sources, const BcFoldDev* __restrict__ folds, int symmetric,
                                                               int num_bits, const float* __restrict__ rowq) {
-    __shared__ float sh_E[kExp];
+    __shared__ float sh_E[kExp + 1];       // (+ the zero word of bc_step_body)
     __shared__ float sh_corr[kBlock];
     __shared__ float sh_q[2 * kBlock];
     __shared__ int sh_flag;
@@ -950,7 +954,7 @@ __global__ __launch_bounds__(kBlock) void bc_chain_kernel(const BcStepDev* __res
                                                           uint32_t* counters, uint32_t* err, unsigned long long* tags, uint32_t epoch,
                                                           int symmetric, int spin_limit, int mm_off, uint32_t* slots_clear, int n_slots_clear,
                                                           BcFusedMm fm) {
-    __shared__ float sh_E[kExp];
+    __shared__ float sh_E[kExp + 1];       // (+ the zero word of bc_step_body)
     __shared__ float sh_corr[kBlock];
     __shared__ int sh_flag;
     bc_chain_block<kExp, kOneGroup, false>(table, refs, sources, folds, counters, err, tags, epoch, symmetric, spin_limit, mm_off,
@@ -965,7 +969,7 @@ __global__ __launch_bounds__(kBlock) void bc_chain_kernel_rows(const BcStepDev* 
                                                                uint32_t* counters, uint32_t* err, unsigned long long* tags, uint32_t epoch,
                                                                int symmetric, int spin_limit, int mm_off, uint32_t* slots_clear, int n_slots_clear,
                                                                BcFusedMm fm, int num_bits, const float* __restrict__ rowq) {
-    __shared__ float sh_E[kExp];
+    __shared__ float sh_E[kExp + 1];       // (+ the zero word of bc_step_body)
     __shared__ float sh_corr[kBlock];
     __shared__ float sh_q[2 * kBlock];
     __shared__ int sh_flag;
