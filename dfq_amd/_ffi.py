@@ -62,6 +62,12 @@ class DfqBatchQuantTensor(Structure):
                 ('per_row', c_int32), ('pad', c_int32), ('code_offset', c_int64), ('range_offset', c_int64)]
 
 
+class DfqBatchSquantTensor(Structure):
+    _fields_ = [('data', c_void_p), ('rows', c_int64), ('row_len', c_int64), ('num_bits', c_int32), ('symmetric', c_int32),
+                ('per_row', c_int32), ('pad', c_int32), ('code_offset', c_int64), ('range_offset', c_int64),
+                ('kernel_len', c_int64), ('stats_offset', c_int64)]
+
+
 class DfqBatchAbsorbRelation(Structure):
     _fields_ = [('w2', c_void_p), ('b1', c_void_p), ('b2', c_void_p), ('bn_weight', c_void_p), ('bn_bias', c_void_p),
                 ('o2', c_int32), ('in_per_group', c_int32), ('khkw', c_int32), ('o1', c_int32), ('shift_offset', c_int64)]
@@ -210,6 +216,14 @@ SIGNATURES = {
     'dfq_batch_quant_plan_run': (c_int32, [c_void_p, c_void_p]),
     'dfq_batch_quant_plan_launches': (c_int32, [c_void_p]),
     'dfq_batch_quant_register_elements': (c_int64, []),
+    'dfq_squant_rows': (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_void_p,
+                                  c_void_p, c_void_p]),
+    'dfq_squant_max_row_len': (c_int64, []),
+    'dfq_batch_squant_plan_create': (c_int32, [POINTER(DfqBatchSquantTensor), c_int32, POINTER(c_void_p), c_int32, c_void_p, c_int32,
+                                               c_int64, c_void_p, c_int64, c_void_p, c_int64, POINTER(c_void_p)]),
+    'dfq_batch_squant_plan_run': (c_int32, [c_void_p, c_void_p]),
+    'dfq_batch_squant_plan_destroy': (None, [c_void_p]),
+    'dfq_batch_squant_plan_launches': (c_int32, [c_void_p]),
     'dfq_batch_absorb_plan_create': (c_int32, [POINTER(DfqBatchAbsorbRelation), c_int32, POINTER(DfqBatchAbsorbClip), c_int32,
                                                POINTER(c_void_p), c_int32, c_float, c_float, c_float, c_void_p, c_int64,
                                                POINTER(c_void_p)]),

@@ -426,6 +426,44 @@ class NetworkBatch:
         finally:
             plan.close()
 
+    def squant_plan(self, bit_weight=8, per_channel=False, signed=False, codes=None):
+        """One adaptive-rounding plan over the weights of the whole batch (BatchSquantPlan; SQuant, "Adaptive rounding" in
+        include/dfq_hip.h): the ranges and the quantisation grid are ``quant_plan``'s (per tensor, or per output row with
+        ``per_channel``; ``signed``: the symmetric recipe), but of the roundings to nearest the few that cost least are flipped
+        so that the rounding errors of every kH x kW kernel and of every output row sum to at most half a quantum -- what
+        ``quantize_targ_layer(..., rounding='squant')`` does to each network, bit for bit.  Weights only; ``bit_weight`` is an
+        integer in [2, 16] in both range modes.  ``codes``: None, 'int32' or 'int8' as in ``quant_plan``.  The plan exposes
+        ``codes(n)``, ``ranges(n)`` and ``stats(n)``.  ValueError for a layer whose rows are longer than
+        dfq_squant_max_row_len()."""
+        self._ready('squant_plan')
+        return BatchSquantPlan(self, bit_weight, per_channel, signed, codes)
+
+    def quantize_squant(self, bit_weight=8, bits_bias=16, per_channel=False, signed=False, codes='int32'):
+        """squant_plan for the weights, the nearest rounding of ``quantize`` for the biases (unless ``bits_bias >= 32``), run
+        + synchronise: returns (codes, ranges) like ``quantize`` -- the biases' ranges under key + '.bias' -- and every bias
+        bit for bit what ``quantize`` stores."""
+        self._ready('quantize_squant')
+        g0 = self.nets[0][0]
+        tt = tuple(self.targ_type)
+        plans = [BatchSquantPlan(self, bit_weight, per_channel, signed, codes)]
+        try:
+            if bits_bias < 32 and any(type(l) in tt and l.bias is not None for l in g0.values()):
+                plans.append(BatchQuantPlan(self, bit_weight, bits_bias, per_channel, signed, None, _biases_only=True))
+            for plan in plans:
+                plan.run()
+            _ffi.synchronize()
+            n = len(self.nets)
+            ranges = []
+            for i in range(n):
+                r = {}
+                for plan in plans:
+                    r.update({k: v.clone() for k, v in plan.ranges(i).items()})
+                ranges.append(r)
+            return [{k: v.clone() for k, v in plans[0].codes(i).items()} for i in range(n)], ranges
+        finally:
+            for plan in plans:
+                plan.close()
+
     def absorb_plan(self, N=3, range_clip=None, absorb=True):
         """One plan (BatchAbsorbPlan) for ``bias_absorption(graph, relations, bottoms, N)`` followed, if ``range_clip`` is
         given, by ``clip_weight(graph, range_clip, targ_type)`` on every network of the batch, bit for bit.  ``absorb=False``
@@ -718,7 +756,7 @@ class BatchQuantPlan(_BatchPlan):
     place, the codes and ranges written to blocks [n_nets, stride] the plan owns and hands out as views."""
     _c = 'dfq_batch_quant_plan'
 
-    def __init__(self, batch, bit_weight, bits_bias, per_channel, signed, codes):
+    def __init__(self, batch, bit_weight, bits_bias, per_channel, signed, codes, _biases_only=False):
         bit_weight = _check_bits(bit_weight, per_channel, 'bit_weight')
         with_bias = bits_bias < 32                   # layer_transform.py: `bits_bias < 32` decides whether biases are quantised
         if with_bias:
@@ -742,15 +780,16 @@ class BatchQuantPlan(_BatchPlan):
             w = layer.weight
             rows = int(w.shape[0])
             c_off = -1
-            if codes is not None:
-                c_off = code_stride
-                self._code_views.append((key, c_off, w.numel(), tuple(w.shape)))
-                code_stride += -(-w.numel() // 64) * 64
-            n_rng = 2 * rows if per_channel else 2
-            self._range_views.append((key, range_stride, (rows, 2) if per_channel else (2,)))
-            entries.append(_ffi.DfqBatchQuantTensor(in_slot(key, 'weight', w), rows, w.numel() // rows, bit_weight, int(self.signed),
-                                                    int(self.per_channel), 0, c_off, range_stride))
-            range_stride += n_rng
+            if not _biases_only:                     # (quantize_squant: the weights are another plan's)
+                if codes is not None:
+                    c_off = code_stride
+                    self._code_views.append((key, c_off, w.numel(), tuple(w.shape)))
+                    code_stride += -(-w.numel() // 64) * 64
+                n_rng = 2 * rows if per_channel else 2
+                self._range_views.append((key, range_stride, (rows, 2) if per_channel else (2,)))
+                entries.append(_ffi.DfqBatchQuantTensor(in_slot(key, 'weight', w), rows, w.numel() // rows, bit_weight, int(self.signed),
+                                                        int(self.per_channel), 0, c_off, range_stride))
+                range_stride += n_rng
             b = layer.bias
             if b is not None and with_bias:
                 self._range_views.append((key + '.bias', range_stride, (2,)))
@@ -778,6 +817,87 @@ class BatchQuantPlan(_BatchPlan):
         """{graph key: float32 [O, 2] (per channel) or [2]} of network n's weights, {key + '.bias': [2]} of its biases"""
         row = self.range_block[n]
         return {key: row[off:off + 2 * (shape[0] if len(shape) == 2 else 1)].view(shape) for (key, off, shape) in self._range_views}
+
+
+class BatchSquantPlan(_BatchPlan):
+    """Adaptive rounding (SQuant; "Adaptive rounding" in include/dfq_hip.h) of the weights of every network of a NetworkBatch
+    (dfq_batch_squant_plan): network 0's tensor table plus the batch's base addresses.  Weights only; ``run()`` enqueues on the
+    current stream and quantises them in place.  The codes, ranges and per-row stats are written to blocks [n_nets, stride] the
+    plan owns and hands out as views."""
+    _c = 'dfq_batch_squant_plan'
+
+    def __init__(self, batch, bit_weight, per_channel, signed, codes):
+        bit_weight = _check_bits(bit_weight, True, 'bit_weight')        # [2, 16] in both range modes
+        if codes not in (None, 'int32', 'int8'):
+            raise ValueError("squant_plan: codes must be None, 'int32' or 'int8', got {!r}".format(codes))
+        if codes == 'int8' and bit_weight > 8:
+            raise ValueError('squant_plan: 1-byte codes need bit_weight <= 8, got {}'.format(bit_weight))
+        super().__init__(batch)
+        self.per_channel, self.signed = bool(per_channel), bool(signed)
+        n_nets = len(batch.nets)
+        dev = batch.stage.device
+        g0 = batch.nets[0][0]
+        tt = tuple(batch.targ_type)
+        longest = int(_ffi.lib().dfq_squant_max_row_len())
+        entries, self._code_views, self._range_views, self._stats_views = [], [], [], []
+        code_stride = range_stride = stats_stride = 0
+        for key, layer in g0.items():
+            if type(layer) not in tt:
+                continue
+            w = layer.weight
+            rows = int(w.shape[0])
+            row_len = w.numel() // rows
+            if row_len > longest:
+                raise ValueError('squant_plan: {}: rows of {} weights, the longest row is {}'.format(key, row_len, longest))
+            c_off = -1
+            if codes is not None:
+                c_off = code_stride
+                self._code_views.append((key, c_off, w.numel(), tuple(w.shape)))
+                code_stride += -(-w.numel() // 64) * 64
+            self._range_views.append((key, range_stride, (rows, 2) if per_channel else (2,)))
+            self._stats_views.append((key, stats_stride, rows))
+            entries.append(_ffi.DfqBatchSquantTensor(batch._in_slot(key, 'weight', w), rows, row_len, bit_weight, int(self.signed),
+                                                     int(self.per_channel), 0, c_off, range_stride, _kernel_len(w), stats_stride))
+            range_stride += 2 * rows if per_channel else 2
+            stats_stride += 2 * rows
+        if not entries:
+            raise ValueError('squant_plan: the batch has no {} layer'.format(tt))
+        dtype = {None: torch.int32, 'int32': torch.int32, 'int8': torch.int8 if self.signed else torch.uint8}[codes]
+        self.code_dtype = None if codes is None else dtype
+        self.code_block = torch.empty((n_nets, code_stride), dtype=dtype, device=dev) if codes is not None else None
+        self.range_block = torch.empty((n_nets, range_stride), dtype=torch.float32, device=dev)
+        self.stats_block = torch.empty((n_nets, stats_stride), dtype=torch.int64, device=dev)
+        self.n_nets, self.n_tensors = n_nets, len(entries)
+        arr = (_ffi.DfqBatchSquantTensor * len(entries))(*entries)
+        self._create((arr, len(entries)), None if self.code_block is None else self.code_block.data_ptr(),
+                     1 if codes == 'int8' else 4, code_stride, self.range_block.data_ptr(), range_stride,
+                     self.stats_block.data_ptr(), stats_stride)
+
+    def codes(self, n):
+        """{graph key: integer codes of network n's weight, shaped like it} -- views of the code block"""
+        if self.code_block is None:
+            return {}
+        row = self.code_block[n]
+        return {key: row[off:off + numel].view(shape) for (key, off, numel, shape) in self._code_views}
+
+    def ranges(self, n):
+        """{graph key: float32 [O, 2] (per channel) or [2]} of network n's weights"""
+        row = self.range_block[n]
+        return {key: row[off:off + 2 * (shape[0] if len(shape) == 2 else 1)].view(shape) for (key, off, shape) in self._range_views}
+
+    def stats(self, n):
+        """{graph key: int64 [O, 2]}: per output row (the sum of P = round(p * 2^30) it is left with, at most 2^29 in size;
+        the number of codes that differ from nearest rounding)"""
+        row = self.stats_block[n]
+        return {key: row[off:off + 2 * rows].view(rows, 2) for (key, off, rows) in self._stats_views}
+
+
+def _kernel_len(w):
+    """kH * kW of a convolution's weight, 1 for a Linear one"""
+    k = 1
+    for d in w.shape[2:]:
+        k *= int(d)
+    return k
 
 
 class BatchFoldPlan(_BatchPlan):

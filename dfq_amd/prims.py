@@ -122,6 +122,32 @@ def fake_quant_rows(x, num_bits=8, min_values=None, max_values=None, symmetric=F
         return res
 
 
+def squant_rows(x, kernel_len=1, num_bits=8, min_values=None, max_values=None, symmetric=False, return_codes=False,
+                return_stats=False):
+    """Adaptive rounding (SQuant; dfq_squant_rows, "Adaptive rounding" in include/dfq_hip.h) of the rows of `x` (first
+    dimension): the grid of fake_quant_rows -- each row's own (min, max), or the given ones -- but the roundings that cost least
+    are flipped until the rounding errors of every run of `kernel_len` elements and of every row sum to at most half a quantum.
+    Returns the quantised tensor, then the int32 codes (``return_codes``), then int64 [rows, 2] = (the row's remaining error
+    sum in units of 2^-30 quanta, the number of flipped codes) (``return_stats``)."""
+    lib = _ffi.lib()
+    with torch.no_grad():
+        stage = _ffi.Stage()
+        xx = stage.bind(x)
+        rows, row_len = xx.shape[0], xx[0].numel()
+        y = stage.new(xx.shape)
+        codes = stage.new(xx.shape, dtype=torch.int32) if return_codes else None
+        stats = stage.new((rows, 2), dtype=torch.int64) if return_stats else None
+        _ffi.check(lib.dfq_squant_rows(_ffi.ptr(xx), _ffi.ptr(y), rows, row_len, int(kernel_len), _ffi.ptr(stage.bind(min_values)),
+                                       _ffi.ptr(stage.bind(max_values)), int(num_bits), int(bool(symmetric)), _ffi.ptr(codes),
+                                       _ffi.ptr(stats), _ffi.stream_arg()))
+        res = [stage.out_like(x, y)]
+        if return_codes:
+            res.append(stage.out_like(x, codes))
+        if return_stats:
+            res.append(stage.out_like(x, stats))
+        return res[0] if len(res) == 1 else tuple(res)
+
+
 def zeroq_quant_rows(x, num_bits=8, min_values=None, max_values=None, return_codes=False):
     """ZeroQ's per-output-channel asymmetric quantiser (quant_utils.py:85-135 via quant_modules.py:161-171)."""
     lib = _ffi.lib()

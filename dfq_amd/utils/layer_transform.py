@@ -113,7 +113,8 @@ def merge_batchnorm(model, graph, bottoms, targ_type=[QConv2d]):
     return model
 
 
-def quantize_targ_layer(graph, bit_weight=8, bits_bias=16, targ_type=None, return_codes=False, per_channel=False, signed=False):
+def quantize_targ_layer(graph, bit_weight=8, bits_bias=16, targ_type=None, return_codes=False, per_channel=False, signed=False,
+                        rounding='nearest'):
     """Per-tensor asymmetric fake-quant of every targ layer's weight (and bias unless 32 bit).
 
     Two launches for the whole network: one multi-tensor min/max, one multi-tensor quantise.
@@ -122,11 +123,19 @@ def quantize_targ_layer(graph, bit_weight=8, bits_bias=16, targ_type=None, retur
     ``per_channel`` (extension): every weight row (output channel) is quantised with its own (min, max); biases stay per
     tensor.  ONE launch for the whole network (dfq_row_quant_plan).  With ``return_codes`` the result is
     ``(graph, codes, ranges)``: ranges[key] = float32 [O, 2], the (min, max) each row was quantised with.
+    ``rounding`` (extension): 'nearest', or 'squant' -- the same ranges and grid, but the weights' roundings are flipped where
+    that costs least until the rounding errors of every kH x kW kernel and of every output row sum to at most half a quantum
+    (dfq_squant_rows, "Adaptive rounding" in include/dfq_hip.h; bit_weight an integer in [2, 16]).  The biases are rounded to
+    nearest as before.  Anything else: ValueError.
     """
+    if rounding not in ('nearest', 'squant'):
+        raise ValueError("quantize_targ_layer: rounding must be 'nearest' or 'squant', got {!r}".format(rounding))
     print("Quantizing Layer parameters")
     if bits_bias == 32:
         print("Skipping bias quantization (32 bits)")
     assert targ_type != None, "targ_type cannot be None!"
+    if rounding == 'squant':
+        return _quantize_targ_layer_squant(graph, bit_weight, bits_bias, targ_type, return_codes, per_channel, signed)
     if per_channel:
         return _quantize_targ_layer_rows(graph, bit_weight, bits_bias, targ_type, return_codes, signed)
     lib = _ffi.lib()
@@ -205,6 +214,73 @@ def _quantize_targ_layer_rows(graph, bit_weight, bits_bias, targ_type, return_co
     if return_codes:
         return graph, codes, ranges
     return graph
+
+
+def _quantize_targ_layer_squant(graph, bit_weight, bits_bias, targ_type, return_codes, per_channel, signed):
+    """quantize_targ_layer(rounding='squant'): every weight through dfq_squant_rows -- with its rows' own ranges per channel,
+    with the tensor's (min, max) for every row otherwise -- then the biases through the plan of the nearest path."""
+    if isinstance(bit_weight, bool) or not isinstance(bit_weight, int) or not 2 <= bit_weight <= 16:
+        raise ValueError("rounding='squant' needs bit_weight in [2, 16], got {!r}".format(bit_weight))
+    lib = _ffi.lib()
+    with torch.no_grad():
+        stage = _ffi.entry_stage()
+        codes, ranges, biases = {}, {}, {}
+        stage.prefetch([t for layer in graph.values() if type(layer) in targ_type for t in (layer.weight, layer.bias)])
+        for key in graph:
+            layer = graph[key]
+            if type(layer) not in targ_type:
+                continue
+            w = stage.bind(layer.weight)
+            rows = int(w.shape[0])
+            klen = 1
+            for d in w.shape[2:]:
+                klen *= int(d)
+            mins = maxs = None
+            if not per_channel:
+                mm, words = stage.new((2,)), stage.new((2,), dtype=torch.int32)
+                _ffi.check(lib.dfq_tensor_minmax(_ffi.ptr(w), w.numel(), _ffi.ptr(mm), _ffi.ptr(words), _ffi.stream_arg()))
+                mins, maxs = mm[0].repeat(rows), mm[1].repeat(rows)
+            c = stage.new(w.shape, dtype=torch.int32) if return_codes else None
+            if return_codes and per_channel:      # the rows' ranges, by the quantisers' rule (only the ranges are kept)
+                ranges[key], unused = stage.new((rows, 2)), stage.new(w.shape)
+                _ffi.check(lib.dfq_fake_quant_rows(_ffi.ptr(w), _ffi.ptr(unused), rows, w.numel() // rows, None, None,
+                                                   int(bit_weight), int(bool(signed)), None, _ffi.ptr(ranges[key]), _ffi.stream_arg()))
+            _ffi.check(lib.dfq_squant_rows(_ffi.ptr(w), _ffi.ptr(w), rows, w.numel() // rows, klen, _ffi.ptr(mins), _ffi.ptr(maxs),
+                                           int(bit_weight), int(bool(signed)), _ffi.ptr(c), None, _ffi.stream_arg()))
+            if return_codes:
+                codes[key] = c
+            if layer.bias is not None and bits_bias < 32:
+                biases[key] = layer
+        if biases:                                # the nearest path, on a graph of nothing but the biases
+            _quantize_biases(biases, bits_bias, per_channel, stage)
+        _ffi.synchronize()
+        stage.writeback()
+    if return_codes:
+        return (graph, codes, ranges) if per_channel else (graph, codes)
+    return graph
+
+
+def _quantize_biases(layers, bits_bias, per_channel, stage):
+    """the biases of {key: layer} as quantize_targ_layer's nearest path quantises them: per tensor, asymmetric -- through
+    dfq_quant_plan, or through dfq_row_quant_plan (a segment of one row) where the weights go per channel"""
+    lib = _ffi.lib()
+    if per_channel and (isinstance(bits_bias, bool) or not isinstance(bits_bias, int) or not 2 <= bits_bias <= 16):
+        raise ValueError('per-channel quantisation needs bit widths in [2, 16], got {!r}'.format(bits_bias))
+    bound = [stage.bind(layer.bias) for layer in layers.values()]
+    plan = ctypes.c_void_p()
+    if per_channel:
+        arr = (_ffi.DfqRowSegment * len(bound))(*[_ffi.DfqRowSegment(b.data_ptr(), 1, b.numel(), int(bits_bias), 0, None, None)
+                                                  for b in bound])
+        create, run, destroy = lib.dfq_row_quant_plan_create, lib.dfq_row_quant_plan_run, lib.dfq_row_quant_plan_destroy
+    else:
+        arr = (_ffi.DfqSegment * len(bound))(*[_ffi.DfqSegment(b.data_ptr(), b.numel(), int(bits_bias), 0, None) for b in bound])
+        create, run, destroy = lib.dfq_quant_plan_create, lib.dfq_quant_plan_run, lib.dfq_quant_plan_destroy
+    _ffi.check(create(arr, len(bound), ctypes.byref(plan)))
+    try:
+        _ffi.check(run(plan, _ffi.stream_arg()))
+        _ffi.synchronize()
+    finally:
+        destroy(plan)
 
 
 def find_prev_bn(bn_module, relu_attached, graph, bottoms, bot):

@@ -439,6 +439,70 @@ int32_t dfq_batch_quant_plan_launches(const dfq_batch_quant_plan* plan);
 /* longest row (or per-tensor tensor) kept in registers between its min/max and its quantisation; longer ones are read twice */
 int64_t dfq_batch_quant_register_elements(void);
 
+/* Adaptive rounding (extension; SQuant, ICLR 2022 -- nothing of it is in the reference): round to nearest, then flip the few
+ * roundings that cost least, so that the rounding errors of every kernel and of every output row sum to at most half a quantum
+ * (nearest rounding leaves a row sum of about sqrt(n / 12) quanta, which is what bias correction then has to repair).
+ * DEFINITION.  A tensor is [rows, row_len] with row_len = G * K; K = `kernel_len` (kH * kW; 1 for Linear and 1x1 convolutions)
+ * and G kernels per row.  The range is the quantisers': the row's own (min, max) or a given pair, NaN skipped (Special values
+ * above); QParams by the float64 recipe of dfq_fake_quant (range_mode 0), asymmetric or symmetric, num_bits in [2, 16].  The
+ * flip stages work per kernel and per row whichever range is used.  Per element, in the float32 operations of the quantiser:
+ *   t  = clamp((w + neg_min) / scale, qmin, qmax);  c0 = rintf(t);  p = c0 - t (exact);  P = llrint((double)p * 2^30),
+ *   an integer in [-2^29, 2^29].  ONE = 2^30, HALF = 2^29.  All sums of P are integer sums: a result depends on no order.
+ *   stage K (K > 1), per kernel: e = sum P; n = (|e| + HALF) >> 30; s = sign(e); of the elements with s P > 0, ordered by s P
+ *            descending, then by index ascending, the first n are flipped: c = c0 - s, P <- P - s ONE.  There are always n
+ *            of them, and afterwards |sum P| <= HALF.
+ *   stage C, per row: e_j = kernel j's sum after stage K (K = 1: a kernel is one element); E = sum e_j; N = (|E| + HALF) >> 30;
+ *            S = sign(E); of the kernels with S e_j > 0, ordered by S e_j descending, then by j ascending, each of the first N
+ *            moves one element: c <- c - S, P <- P - S ONE, the element with the largest S P > 0 AFTER stage K, the lowest
+ *            index on a tie (an element flipped in stage K may be flipped back).  Such an element always exists.
+ *   afterwards |sum_row P| <= HALF, |sum_kernel P| <= ONE, |c - c0| <= 1, qmin <= c <= qmax (an element with p = 0 -- the
+ *            row's extremes, every clamped element -- is never a candidate).  Stored: c * scale + min_value, the two float32
+ *            roundings of the quantiser.
+ *   fallback: a row with an element whose t is NaN, or whose QParams hold a non-finite value, gets no flips and is stored bit
+ *            for bit as dfq_fake_quant_rows / dfq_batch_quant_plan_run store it; its stats are (0, 0).  The code of a NaN is 0.
+ * dfq_squant_rows: one tensor.  mins / maxs: device [rows], or both NULL for each row's own range (as dfq_fake_quant_rows).
+ * codes: device int32 [rows, row_len] or NULL.  stats: device int64 [rows, 2] or NULL = (sum_row P after stage C, number of
+ * elements whose code differs from c0).  x == y is allowed.  One launch; rows of up to 256 elements share a wave (4 to 64
+ * lanes each), longer ones get a wave, rows above 1536 a workgroup.  DFQ_ERR_ARG (and dfq_last_error) for null or empty
+ * arguments, only one of mins / maxs, num_bits outside [2, 16], row_len % kernel_len != 0, row_len above
+ * dfq_squant_max_row_len(). */
+int dfq_squant_rows(const float* x, float* y, int64_t rows, int64_t row_len, int64_t kernel_len, const float* mins, const float* maxs,
+                    int32_t num_bits, int32_t symmetric, int32_t* codes, int64_t* stats, void* stream);
+/* longest row the adaptive rounding takes (16384) */
+int64_t dfq_squant_max_row_len(void);
+
+/* The same for the weights of a whole batch of networks of one architecture, in the shape of dfq_batch_quant_plan: the table
+ * describes the FIRST of `n_nets` networks, network n's copy of a tensor lies bases[n] - bases[0] bytes further.  per_row: each
+ * row its own range; else the tensor's (min, max), found by a launch in front (cleared range words, as dfq_batch_quant_plan).
+ * Codes go to a caller-owned block [n_nets, code_stride] of `code_bytes`-wide elements (4 = int32; 1 = uint8 / int8, at most 8
+ * bits), ranges to a float32 block [n_nets, range_stride] (a pair per row, or one per tensor), stats to an int64 block
+ * [n_nets, stats_stride] (a pair per row).  Offsets are in elements of their block, -1 = none.  create: DFQ_ERR_ARG (and
+ * dfq_last_error) for null or empty arguments, num_bits outside [2, 16], row_len % kernel_len != 0, row_len above
+ * dfq_squant_max_row_len(), 1-byte codes of more than 8 bits, offsets past their stride.  Synchronises (create only); run is
+ * asynchronous on `stream`. */
+typedef struct dfq_batch_squant_plan dfq_batch_squant_plan;
+typedef struct dfq_batch_squant_tensor {
+    float* data;            /* device, inside network 0's slot; [rows, row_len], quantised in place      */
+    int64_t rows;
+    int64_t row_len;
+    int32_t num_bits;
+    int32_t symmetric;
+    int32_t per_row;
+    int32_t pad;
+    int64_t code_offset;
+    int64_t range_offset;
+    int64_t kernel_len;     /* K; row_len is a multiple of it                                            */
+    int64_t stats_offset;   /* int64 elements into a network's stats block, or -1                        */
+} dfq_batch_squant_tensor;
+
+int dfq_batch_squant_plan_create(const dfq_batch_squant_tensor* tensors, int32_t n_tensors, const void* const* bases, int32_t n_nets,
+                                 void* codes, int32_t code_bytes, int64_t code_stride, float* ranges, int64_t range_stride,
+                                 int64_t* stats, int64_t stats_stride, dfq_batch_squant_plan** out_plan);
+int dfq_batch_squant_plan_run(dfq_batch_squant_plan* plan, void* stream);
+void dfq_batch_squant_plan_destroy(dfq_batch_squant_plan* plan);
+/* kernel launches per run (1 to 3: per-tensor ranges, rows of a wave or less, rows of a workgroup) */
+int32_t dfq_batch_squant_plan_launches(const dfq_batch_squant_plan* plan);
+
 /* Bias absorption and weight clipping of a whole batch of networks of one architecture (extension; bias_absorption,
  * dfq.py:121-164, followed by clip_weight, dfq.py:167-170, for every network of a batch at once).  The tables describe the
  * FIRST of `n_nets` networks; network n's copy of a tensor lies bases[n] - bases[0] bytes further.  `relations` lists, in
