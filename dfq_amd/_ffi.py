@@ -103,6 +103,16 @@ class DfqBatchClipConfig(Structure):
                 ('alpha_min', c_double), ('apply', c_int32), ('pad', c_int32)]
 
 
+class DfqBatchMixedTensor(Structure):
+    _fields_ = [('data', c_void_p), ('rows', c_int64), ('row_len', c_int64), ('sensitivity', c_double), ('fixed_bits', c_int32),
+                ('pad', c_int32), ('code_offset', c_int64), ('range_offset', c_int64)]
+
+
+class DfqBatchMixedConfig(Structure):
+    _fields_ = [('widths', c_int32 * 8), ('n_widths', c_int32), ('symmetric', c_int32), ('per_row', c_int32), ('apply', c_int32),
+                ('code_bytes', c_int32), ('pad', c_int32), ('budget_bits', c_int64)]
+
+
 class DfqBatchActResult(Structure):
     _fields_ = [('step_begin', c_int32), ('step_count', c_int32)]
 
@@ -251,6 +261,12 @@ SIGNATURES = {
     'dfq_batch_clip_plan_run': (c_int32, [c_void_p, c_void_p]),
     'dfq_batch_clip_plan_destroy': (None, [c_void_p]),
     'dfq_batch_clip_plan_launches': (c_int32, [c_void_p]),
+    'dfq_batch_mixed_plan_create': (c_int32, [POINTER(DfqBatchMixedTensor), c_int32, POINTER(DfqBatchMixedConfig), POINTER(c_void_p),
+                                              c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                                              POINTER(c_void_p)]),
+    'dfq_batch_mixed_plan_run': (c_int32, [c_void_p, c_void_p]),
+    'dfq_batch_mixed_plan_destroy': (None, [c_void_p]),
+    'dfq_batch_mixed_plan_launches': (c_int32, [c_void_p]),
     'dfq_batch_act_plan_create': (c_int32, [POINTER(DfqBatchActResult), c_int32, POINTER(DfqBatchActStep), c_int32,
                                             POINTER(DfqBatchActSource), c_int32, POINTER(c_void_p), c_int32, c_float, c_float,
                                             c_void_p, c_int64, POINTER(c_void_p)]),

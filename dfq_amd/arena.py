@@ -464,6 +464,50 @@ class NetworkBatch:
             for plan in plans:
                 plan.close()
 
+    def mixed_plan(self, widths=(2, 3, 4, 6, 8), avg_bits=None, budget_bits=None, per_channel=False, signed=False, sensitivity=None,
+                   pin=None, codes=None, apply=True):
+        """One mixed-precision plan over the weights of the whole batch (BatchMixedPlan): every ``targ_type`` weight of every
+        network gets a width of its own out of ``widths`` (rising ints in [2, 16], two to eight of them) so that the network
+        takes at most ``budget_bits`` bits -- or, with ``avg_bits``, floor(avg_bits * number of weights), computed exactly;
+        exactly one of the two is given, and the budget is the same for every network -- and the sum over the layers of
+        ``sensitivity[key]`` (default 1) times the layer's sum of squared quantisation errors is least: the greedy walk the
+        comment of dfq_batch_mixed_plan_create (include/dfq_hip.h) defines, run on the device per network.  ``pin[key]`` fixes
+        a layer's width (one of ``widths``).  With ``apply`` every weight is then quantised in place at its width, bit for bit
+        as ``quant_plan(bit_weight=that width, per_channel=, signed=)`` would; ``apply=False`` only allocates.  ``codes``:
+        None, 'int32' or 'int8' (widths <= 8) as in ``quant_plan``.  The plan exposes ``bits(n)``, ``errors(n)``, ``used(n)``,
+        ``cost(n)``, ``ranges(n)`` and ``codes(n)``.  Weights only.  ValueError for what create would refuse; RuntimeError
+        for a weight of network 0 that has left its slot."""
+        self._ready('mixed_plan')
+        return BatchMixedPlan(self, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, codes, apply)
+
+    def quantize_mixed(self, widths=(2, 3, 4, 6, 8), avg_bits=None, budget_bits=None, per_channel=False, signed=False, sensitivity=None,
+                       pin=None, codes='int32', bits_bias=16):
+        """mixed_plan for the weights, the nearest rounding of ``quantize`` for the biases (unless ``bits_bias >= 32``), run +
+        synchronise: returns (codes, ranges, bits), each a list of one dict per network -- the biases' ranges under
+        key + '.bias', every bias bit for bit what ``quantize`` stores, ``bits[n][key]`` the width network n's layer got."""
+        self._ready('quantize_mixed')
+        g0 = self.nets[0][0]
+        tt = tuple(self.targ_type)
+        plans = [BatchMixedPlan(self, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, codes, True)]
+        try:
+            if bits_bias < 32 and any(type(l) in tt and l.bias is not None for l in g0.values()):
+                plans.append(BatchQuantPlan(self, plans[0].widths[-1], bits_bias, per_channel, signed, None, _biases_only=True))
+            for plan in plans:
+                plan.run()
+            _ffi.synchronize()
+            n = len(self.nets)
+            ranges = []
+            for i in range(n):
+                r = {}
+                for plan in plans:
+                    r.update({k: v.clone() for k, v in plan.ranges(i).items()})
+                ranges.append(r)
+            return ([{k: v.clone() for k, v in plans[0].codes(i).items()} for i in range(n)], ranges,
+                    [dict(plans[0].bits(i)) for i in range(n)])
+        finally:
+            for plan in plans:
+                plan.close()
+
     def absorb_plan(self, N=3, range_clip=None, absorb=True):
         """One plan (BatchAbsorbPlan) for ``bias_absorption(graph, relations, bottoms, N)`` followed, if ``range_clip`` is
         given, by ``clip_weight(graph, range_clip, targ_type)`` on every network of the batch, bit for bit.  ``absorb=False``
@@ -890,6 +934,61 @@ class BatchSquantPlan(_BatchPlan):
         the number of codes that differ from nearest rounding)"""
         row = self.stats_block[n]
         return {key: row[off:off + 2 * rows].view(rows, 2) for (key, off, rows) in self._stats_views}
+
+
+class BatchMixedPlan(_BatchPlan):
+    """Mixed-precision quantisation of the weights of every network of a NetworkBatch (dfq_batch_mixed_plan, include/dfq_hip.h,
+    which holds the definition): network 0's table of ``targ_type`` weights plus the batch's base addresses.  ``run()``
+    enqueues on the current stream -- ranges, the errors at every width, the allocation (one workgroup per network) and, with
+    ``apply``, the quantisation in place: ``launches`` of them, and nothing goes to the host in between.  The results lie in
+    blocks the plan owns, torch tensors that outlive ``close()``: ``bits_block`` int32 [n_nets, T], ``error_block`` float64
+    [n_nets, T, B], ``used_block`` int64 [n_nets, 2] = (used bits, steps), ``cost_block`` float64 [n_nets], ``range_block``
+    and, with ``codes``, ``code_block``.  ``widths``, ``budget`` (bits per network) and ``elements`` (weights per network) are
+    what the plan was made with.  Two runs of a plan without ``apply`` give bit-equal blocks, and a network's part does not
+    depend on the others."""
+    _c = 'dfq_batch_mixed_plan'
+
+    def __init__(self, batch, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, codes, apply):
+        g0 = batch.nets[0][0]
+        tt = tuple(batch.targ_type)
+        layers = [(key, layer.weight) for key, layer in g0.items() if type(layer) in tt]
+        if not layers:
+            raise ValueError('mixed_plan: the batch has no {} layer'.format(tt))
+        lay = _dfq._MixedLayout('mixed_plan', layers, lambda key, w: batch._in_slot(key, 'weight', w), len(batch.nets), widths,
+                                avg_bits, budget_bits, per_channel, signed, sensitivity, pin, codes, apply, batch.stage.device)
+        super().__init__(batch)
+        self._lay = lay
+        self.widths, self.budget, self.elements = lay.widths, lay.budget, lay.total
+        self.per_channel, self.signed, self.apply = lay.per_channel, lay.signed, lay.apply
+        self.keys, self.n_nets, self.n_tensors = lay.keys, lay.n_nets, lay.n_tensors
+        self.code_dtype = lay.code_dtype
+        self.bits_block, self.error_block, self.used_block, self.cost_block = lay.bits_block, lay.error_block, lay.used_block, lay.cost_block
+        self.range_block, self.code_block = lay.range_block, lay.code_block
+        self._create(lay.tables(), *lay.block_args())
+
+    def bits(self, n):
+        """``OrderedDict[graph key -> int]``: the width network n's weight got (one device-to-host copy)"""
+        return self._lay.bits(n)
+
+    def errors(self, n):
+        """``OrderedDict[graph key -> float64 numpy [B]]``: sum e^2 of network n's weight at every width of ``widths``"""
+        return self._lay.errors(n)
+
+    def used(self, n):
+        """(bits network n's allocation takes, steps the walk took); used > ``budget`` if the start alone exceeds it"""
+        return self._lay.used(n)
+
+    def cost(self, n):
+        """sum over the layers of sensitivity * sum e^2 at the chosen widths, added in the order of ``keys``"""
+        return self._lay.cost(n)
+
+    def ranges(self, n):
+        """{graph key: float32 [O, 2] (per channel) or [2]} of network n's weights: the (min, max) the quantiser used"""
+        return self._lay.ranges(n)
+
+    def codes(self, n):
+        """{graph key: integer codes of network n's weight, shaped like it} -- views of the code block; {} without codes"""
+        return self._lay.codes(n)
 
 
 def _kernel_len(w):

@@ -1256,6 +1256,169 @@ def clip_weight_mse(graph, bits_weight=8, per_channel=False, signed=False, candi
 
 
 # ------------------------------------------------------------------------------------------------
+# extension: a bit width per layer under a size budget (dfq_batch_mixed_plan, include/dfq_hip.h)
+# ------------------------------------------------------------------------------------------------
+_MIXED_ENTRIES = 4096            # T * B the allocation's table holds
+
+
+class _MixedLayout:
+    """The tensor table, the configuration and the output blocks of one dfq_batch_mixed_plan; every argument is checked here,
+    ValueError('<who>: ...') for what create would refuse.  ``layers``: [(graph key, weight)]; ``address(key, weight)`` gives
+    the weight's device address in network 0.  The blocks are torch tensors: ``bits_block`` int32 [n_nets, T], ``error_block``
+    float64 [n_nets, T, B], ``used_block`` int64 [n_nets, 2], ``cost_block`` float64 [n_nets], ``range_block`` float32
+    [n_nets, range_stride] and, with ``codes``, ``code_block``."""
+
+    def __init__(self, who, layers, address, n_nets, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, codes,
+                 apply, device):
+        import math
+        import numbers
+        from fractions import Fraction
+        ints = (int, numbers.Integral)
+        try:
+            widths = tuple(widths)
+        except TypeError:
+            raise ValueError('{}: widths must be a sequence of bit widths, got {!r}'.format(who, widths)) from None
+        if not 2 <= len(widths) <= 8:
+            raise ValueError('{}: 2 to 8 candidate widths, got {!r}'.format(who, widths))
+        if any(isinstance(b, bool) or not isinstance(b, ints) or not 2 <= b <= 16 for b in widths):
+            raise ValueError('{}: every width must be an int in [2, 16], got {!r}'.format(who, widths))
+        if any(b <= a for a, b in zip(widths, widths[1:])):
+            raise ValueError('{}: the widths must rise, got {!r}'.format(who, widths))
+        widths = tuple(int(b) for b in widths)
+        if not layers:
+            raise ValueError('{}: no layer to quantise'.format(who))
+        if len(layers) * len(widths) > _MIXED_ENTRIES:
+            raise ValueError('{}: {} layers x {} widths, the allocation holds {} entries'.format(who, len(layers), len(widths), _MIXED_ENTRIES))
+        if (avg_bits is None) == (budget_bits is None):
+            raise ValueError('{}: exactly one of avg_bits and budget_bits'.format(who))
+        total = sum(w.numel() for _, w in layers)
+        if avg_bits is not None:
+            if isinstance(avg_bits, bool) or not isinstance(avg_bits, numbers.Real) or not math.isfinite(avg_bits) or avg_bits < 0:
+                raise ValueError('{}: avg_bits must be a finite number >= 0, got {!r}'.format(who, avg_bits))
+            budget = int((Fraction(avg_bits) * total).__floor__())     # exact: the float's own value times an integer
+        else:
+            if isinstance(budget_bits, bool) or not isinstance(budget_bits, ints) or budget_bits < 0:
+                raise ValueError('{}: budget_bits must be an int >= 0, got {!r}'.format(who, budget_bits))
+            budget = int(budget_bits)
+        if budget >= 2 ** 63:
+            raise ValueError('{}: a budget of {} bits'.format(who, budget))
+        if codes not in (None, 'int32', 'int8'):
+            raise ValueError("{}: codes must be None, 'int32' or 'int8', got {!r}".format(who, codes))
+        if codes == 'int8' and widths[-1] > 8:
+            raise ValueError('{}: 1-byte codes need widths <= 8, got {!r}'.format(who, widths))
+        keys = [key for key, _ in layers]
+        sensitivity, pin = dict(sensitivity or {}), dict(pin or {})
+        for name, table in (('sensitivity', sensitivity), ('pin', pin)):
+            for key in table:
+                if key not in keys:
+                    raise ValueError('{}: {} names {!r}, which is no layer to quantise'.format(who, name, key))
+        for key, s in sensitivity.items():
+            if isinstance(s, bool) or not isinstance(s, numbers.Real) or not math.isfinite(s) or s < 0:
+                raise ValueError('{}: the sensitivity of {!r} must be a finite number >= 0, got {!r}'.format(who, key, s))
+        for key, b in pin.items():
+            if isinstance(b, bool) or not isinstance(b, ints) or int(b) not in widths:
+                raise ValueError('{}: {!r} is pinned to {!r}, which is none of the widths {!r}'.format(who, key, b, widths))
+        self.widths, self.budget, self.total = widths, budget, total
+        self.per_channel, self.signed, self.apply = bool(per_channel), bool(signed), bool(apply)
+        self.keys, self.n_nets, self.n_tensors = keys, n_nets, len(layers)
+        entries, self._code_views, self._range_views = [], [], []
+        code_stride = range_stride = 0
+        for key, w in layers:
+            rows = int(w.shape[0])
+            c_off = -1
+            if codes is not None:
+                c_off = code_stride
+                self._code_views.append((key, c_off, w.numel(), tuple(w.shape)))
+                code_stride += -(-w.numel() // 64) * 64
+            self._range_views.append((key, range_stride, (rows, 2) if self.per_channel else (2,)))
+            entries.append(_ffi.DfqBatchMixedTensor(address(key, w), rows, w.numel() // rows, float(sensitivity.get(key, 1.0)),
+                                                    int(pin.get(key, 0)), 0, c_off, range_stride))
+            range_stride += 2 * rows if self.per_channel else 2
+        self.table = (_ffi.DfqBatchMixedTensor * len(entries))(*entries)
+        self.config = _ffi.DfqBatchMixedConfig((ctypes.c_int32 * 8)(*widths), len(widths), int(self.signed), int(self.per_channel),
+                                               int(self.apply), {None: 0, 'int32': 4, 'int8': 1}[codes], 0, budget)
+        dtype = {None: torch.int32, 'int32': torch.int32, 'int8': torch.int8 if self.signed else torch.uint8}[codes]
+        self.code_dtype = None if codes is None else dtype
+        self.code_stride, self.range_stride = code_stride, range_stride
+        self.code_block = torch.zeros((n_nets, code_stride), dtype=dtype, device=device) if codes is not None else None
+        self.range_block = torch.zeros((n_nets, range_stride), dtype=torch.float32, device=device)
+        self.bits_block = torch.zeros((n_nets, len(entries)), dtype=torch.int32, device=device)
+        self.error_block = torch.zeros((n_nets, len(entries), len(widths)), dtype=torch.float64, device=device)
+        self.used_block = torch.zeros((n_nets, 2), dtype=torch.int64, device=device)
+        self.cost_block = torch.zeros((n_nets,), dtype=torch.float64, device=device)
+
+    def tables(self):
+        """(tensors, n_tensors, config) as dfq_batch_mixed_plan_create takes them in front of the bases"""
+        return (self.table, self.n_tensors, ctypes.byref(self.config))
+
+    def block_args(self):
+        """(bits, errors, used, cost, codes, code_stride, ranges, range_stride) as create takes them behind the bases"""
+        return (self.bits_block.data_ptr(), self.error_block.data_ptr(), self.used_block.data_ptr(), self.cost_block.data_ptr(),
+                None if self.code_block is None else self.code_block.data_ptr(), self.code_stride,
+                self.range_block.data_ptr(), self.range_stride)
+
+    def bits(self, n):
+        row = self.bits_block[n].cpu().tolist()
+        return OrderedDict((key, int(b)) for key, b in zip(self.keys, row))
+
+    def errors(self, n):
+        row = self.error_block[n].cpu().numpy()
+        return OrderedDict((key, row[i].copy()) for i, key in enumerate(self.keys))
+
+    def used(self, n):
+        used, steps = self.used_block[n].cpu().tolist()
+        return int(used), int(steps)
+
+    def cost(self, n):
+        return float(self.cost_block[n].cpu())
+
+    def ranges(self, n):
+        row = self.range_block[n]
+        return OrderedDict((key, row[off:off + 2 * (shape[0] if len(shape) == 2 else 1)].view(shape)) for (key, off, shape) in self._range_views)
+
+    def codes(self, n):
+        if self.code_block is None:
+            return {}
+        row = self.code_block[n]
+        return OrderedDict((key, row[off:off + numel].view(shape)) for (key, off, numel, shape) in self._code_views)
+
+
+def quantize_mixed(graph, widths=(2, 3, 4, 6, 8), avg_bits=None, budget_bits=None, per_channel=False, signed=False, sensitivity=None,
+                   pin=None, targ_type=[nn.Conv2d, nn.Linear]):
+    """Mixed-precision ``quantize_targ_layer`` for the weights (extension): every ``targ_type`` weight is quantised in place
+    at a width of its own out of ``widths``, chosen so that the network takes at most ``budget_bits`` bits (or ``avg_bits``
+    per weight on average: floor(avg_bits * number of weights)) and the sum of ``sensitivity[key]`` (default 1) times the
+    layer's sum of squared quantisation errors is least -- the greedy walk the comment of dfq_batch_mixed_plan_create
+    (include/dfq_hip.h) defines; ``pin[key]`` fixes a layer's width.  The single-network form of
+    ``NetworkBatch.mixed_plan``, the same plan over a batch of one; it stands where ``quantize_targ_layer`` stands, behind
+    equalisation, absorption and clipping.  Biases are left alone.  Returns
+    ``OrderedDict[key -> {'bits', 'err', 'range'}]``: the chosen width, the sum e^2 at it, and the (min, max) the quantiser
+    used ([2], or [O, 2] with ``per_channel``).  ValueError for what ``NetworkBatch.mixed_plan`` refuses."""
+    lib = _ffi.lib()
+    layers = [(key, graph[key].weight) for key in graph if type(graph[key]) in targ_type]
+    if not layers:
+        raise ValueError('quantize_mixed: the graph has no {} layer'.format(tuple(targ_type)))
+    with torch.no_grad():
+        stage = _ffi.entry_stage()
+        stage.prefetch([w for _, w in layers])
+        bufs = {key: stage.bind(w) for key, w in layers}
+        lay = _MixedLayout('quantize_mixed', layers, lambda key, w: bufs[key].data_ptr(), 1, widths, avg_bits, budget_bits, per_channel,
+                           signed, sensitivity, pin, None, True, stage.device)
+        bases = (ctypes.c_void_p * 1)(bufs[layers[0][0]].data_ptr())
+        plan = ctypes.c_void_p()
+        _ffi.check(lib.dfq_batch_mixed_plan_create(*lay.tables(), bases, 1, *lay.block_args(), ctypes.byref(plan)))
+        try:
+            _ffi.check(lib.dfq_batch_mixed_plan_run(plan, _ffi.stream_arg()))
+            _ffi.synchronize()
+            bits, errors, ranges = lay.bits(0), lay.errors(0), lay.ranges(0)
+        finally:
+            lib.dfq_batch_mixed_plan_destroy(plan)
+        stage.writeback()
+    return OrderedDict((key, {'bits': bits[key], 'err': float(errors[key][lay.widths.index(bits[key])]),
+                              'range': ranges[key].cpu().numpy().copy()}) for key in lay.keys)
+
+
+# ------------------------------------------------------------------------------------------------
 # dfq.py:173-293
 # ------------------------------------------------------------------------------------------------
 class BCPlan:

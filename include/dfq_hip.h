@@ -720,6 +720,81 @@ void dfq_batch_clip_plan_destroy(dfq_batch_clip_plan* plan);
 /* kernel launches per run: 1 for the units in registers and the long rows, 3 (4 with apply) for the flat pieces */
 int32_t dfq_batch_clip_plan_launches(const dfq_batch_clip_plan* plan);
 
+/* Mixed-precision weight quantisation of a whole batch of networks of one architecture (extension; a bit width per layer
+ * under a size budget, the allocation ZeroQ is known for, joined to the quantiser of dfq_batch_quant_plan).  `tensors` lists
+ * the weights of the FIRST of `n_nets` networks; network n's copy of a tensor lies bases[n] - bases[0] bytes further.  One run
+ * finds the ranges, the error of every tensor at every candidate width, a width per tensor and network, and quantises every
+ * tensor at its own width; nothing goes to the host in between.
+ * DEFINITION.  Candidate widths b_0 < b_1 < ... < b_{B-1}, integers in [2, 16], 2 <= B <= 8.  `symmetric` and `per_row`, one
+ * pair for the plan, mean what they mean in dfq_batch_quant_tensor.  Tensor t is [rows, row_len], n_t = rows * row_len, with a
+ * `sensitivity` s_t (float64, finite, >= 0) and `fixed_bits` (0: free; else one of the candidates, and the tensor is pinned).
+ *   errors      E[n][t][j] = sum of e^2 over tensor t of network n, e = fake_quant(w; qparams(min, max, b_j, symmetric)) - w
+ *               in float32, (min, max) the tensor's pair, or the row's with per_row: term for term the third sum
+ *               dfq_batch_error_plan_run reports for the configuration (b_j, symmetric, per_row).  The square and the sum are
+ *               float64; the order of the sum is the plan's own and depends on the tensor's shape alone, no floating-point
+ *               atomic is used: two runs are bit-identical, and network n's values do not depend on n_nets or on n's place in
+ *               the batch.  NaN is skipped by the ranges (Special values above); a tensor holding NaN gets NaN errors, nothing
+ *               else does.  All B errors of a weight come from one read of it.
+ *   allocation  per network.  Cost c[t][j] = s_t * E[n][t][j], one float64 multiplication.  Every free tensor starts at
+ *               j_t = 0, a pinned one at its width's index; used = sum_t n_t * b_{j_t} in int64.  The NEXT STEP of a free
+ *               tensor standing at j: for k > j, g(j, k) = (c[t][j] - c[t][k]) / (double)(n_t * (b_k - b_j)), one float64
+ *               subtraction and one float64 division; only k with g > 0 count (false for NaN); the step is the k of greatest
+ *               g, the largest such k on a tie; if no k counts the tensor is finished.  LOOP: among the unfinished free
+ *               tensors take the one whose next step has the greatest g, the lowest t on a tie; d = n_t * (b_k - b_j); if
+ *               used + d > budget_bits the allocation ENDS (it does not skip to a cheaper step); otherwise j_t = k,
+ *               used += d, and the loop goes on.  This is the greedy walk along every tensor's lower convex hull in order of
+ *               error removed per bit; its result is a Lagrangian minimiser: no allocation of at most `used` bits has a
+ *               smaller sum_t c[t][j_t], up to the rounding of g.  If the start alone exceeds the budget the start is the
+ *               allocation, and used > budget_bits tells the caller.  At most T (B - 1) steps.
+ *   quantise    with `apply`, tensor t of network n is quantised in place at b_{j_t}: the weight and the code are bit for bit
+ *               what dfq_batch_quant_plan_run stores for a tensor described with num_bits = b_{j_t} and the plan's symmetric /
+ *               per_row.  With apply = 0 no weight and no code is written.
+ * Outputs, blocks of the caller: `bits` int32 [n_nets, T] the chosen width; `errors` float64 [n_nets, T, B]; `used` int64
+ * [n_nets, 2] = (used bits, steps taken); `cost` float64 [n_nets] = sum_t c[t][j_t] added in rising t; `ranges` float32
+ * [n_nets, range_stride], (min, max) per row of a per_row plan, one pair per tensor otherwise -- what the quant plan writes,
+ * written with or without `apply`; `codes` [n_nets, code_stride] of code_bytes-wide elements (4 = int32; 1 = uint8, or int8
+ * with symmetric, only if b_{B-1} <= 8; 0 = no codes).  code_offset / range_offset are in elements of their block, -1 = none.
+ * Rows and tensors of at most dfq_batch_quant_register_elements() elements stay in registers between their range and their
+ * errors; a weight is read at most three times and written once.  Launches per run are fixed at creation (2 to 4: ranges of
+ * the long per-tensor tensors, errors, allocation -- one workgroup per network --, quantisation); no workgroup waits for
+ * another and nothing synchronises with the host.
+ * create: DFQ_ERR_ARG (and dfq_last_error) for null or empty tables, a null configuration, B outside 2..8, widths that do not
+ * rise or lie outside [2, 16], T * B above 4096, a fixed_bits that is not a candidate, a sensitivity that is negative or not
+ * finite, a negative budget, code_bytes other than 0, 1, 4, 1-byte codes with a width above 8, a weight that is null or not
+ * 16-byte aligned, rows <= 0 or row_len <= 0, a null bits / errors / used / cost block, a tensor that writes codes or ranges
+ * into a null block, offsets outside their strides, null bases, networks that are not 16-byte aligned to network 0.  Every
+ * tensor of network 0 must lie inside network 0's slot: nothing here can check that.  Synchronises (create only); run is
+ * asynchronous on `stream`. */
+typedef struct dfq_batch_mixed_plan dfq_batch_mixed_plan;
+typedef struct dfq_batch_mixed_tensor { /* addresses in network 0 */
+    float* data;            /* the layer's weight [rows, row_len], quantised in place with `apply`                   */
+    int64_t rows;
+    int64_t row_len;
+    double sensitivity;     /* s_t                                                                                   */
+    int32_t fixed_bits;     /* 0: free; else a candidate width the tensor is pinned to                               */
+    int32_t pad;
+    int64_t code_offset;    /* elements into a network's code block, or -1                                           */
+    int64_t range_offset;   /* floats into a network's range block, or -1                                            */
+} dfq_batch_mixed_tensor;
+typedef struct dfq_batch_mixed_config {
+    int32_t widths[8];      /* b_0 < b_1 < ...; the first n_widths count                                             */
+    int32_t n_widths;       /* B                                                                                     */
+    int32_t symmetric;      /* the signed recipe                                                                     */
+    int32_t per_row;        /* ranges per output row instead of per tensor                                           */
+    int32_t apply;          /* 0: allocate only                                                                      */
+    int32_t code_bytes;     /* 0, 1 or 4                                                                             */
+    int32_t pad;
+    int64_t budget_bits;    /* the same for every network                                                            */
+} dfq_batch_mixed_config;
+
+int dfq_batch_mixed_plan_create(const dfq_batch_mixed_tensor* tensors, int32_t n_tensors, const dfq_batch_mixed_config* config,
+                                const void* const* bases, int32_t n_nets, int32_t* bits, double* errors, int64_t* used, double* cost,
+                                void* codes, int64_t code_stride, float* ranges, int64_t range_stride, dfq_batch_mixed_plan** out_plan);
+int dfq_batch_mixed_plan_run(dfq_batch_mixed_plan* plan, void* stream);
+void dfq_batch_mixed_plan_destroy(dfq_batch_mixed_plan* plan);
+/* kernel launches per run (2 to 4), fixed at creation; the clear of the range words of the long tensors is a memset */
+int32_t dfq_batch_mixed_plan_launches(const dfq_batch_mixed_plan* plan);
+
 /* Analytic activation ranges of a whole batch of networks of one architecture (extension; set_quant_minmax,
  * utils/layer_transform.py:347-609, main_cls.py:188, for every network of a batch at once).  The caller walks the graph of
  * the FIRST network once (find_prev_bn, :299-344, and the branch grouping of :476-580) and hands over what the walk found
