@@ -280,6 +280,7 @@ SIGNATURES = {
     'dfq_bc_plan_destroy': (None, [c_void_p]),
     'dfq_bc_plan_run': (c_int32, [c_void_p, c_int32, c_void_p]),
     'dfq_bc_plan_run_per_channel': (c_int32, [c_void_p, c_int32, c_int32, c_void_p]),
+    'dfq_bc_plan_run_widths': (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_int64, POINTER(c_int32), c_int32, c_void_p]),
     'dfq_bc_plan_status': (c_int32, [c_void_p, c_void_p]),
     'dfq_bc_plan_eps': (c_void_p, [c_void_p, c_int32]),
     'dfq_bc_plan_correction': (c_void_p, [c_void_p, c_int32]),

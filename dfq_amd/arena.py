@@ -45,6 +45,10 @@ front of ``le_plan`` and behind it shows what equalisation bought.
 with a searched bound, standing where ``absorb_plan(range_clip=...)`` clips: fold_plan -> le_plan -> absorb_plan -> clip_plan
 -> bc_plan -> quant_plan -> act_range_plan.  A unit's own (min, max) is then the chosen range, so the plans behind it are
 unchanged (tests/test_batch_clip.py).
+With a width per layer the correction has to see the widths, so the allocation comes first and the quantisation last:
+fold_plan -> le_plan -> absorb_plan -> clip_plan -> mixed_plan(apply=False) -> bc_plan.run(widths=) -> mixed_plan ->
+act_range_plan; ``bc_plan().run(widths=that plan)`` reads every (network, layer)'s width on the device, where the allocation
+left it, and ``quantize_mixed(correct=True)`` is the three steps and the biases in one call (tests/test_bc_widths.py).
 """
 from __future__ import annotations
 
@@ -398,6 +402,7 @@ class NetworkBatch:
         t = self._tables(self._bc)
         t.n_steps, t.n_sources = self._bc.n_steps, self._bc.n_sources
         t.step_out_ch, t.step_in = self._bc.step_out_ch, self._bc.step_in
+        t.step_keys = list(self._bc.step_keys)               # run(widths=mixed_plan) finds every step's width by its graph key
         return _dfq.BCPlan(t, None, stage=self.stage)
 
     def quant_plan(self, bit_weight=8, bits_bias=16, per_channel=False, signed=False, codes=None):
@@ -481,19 +486,33 @@ class NetworkBatch:
         return BatchMixedPlan(self, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, codes, apply)
 
     def quantize_mixed(self, widths=(2, 3, 4, 6, 8), avg_bits=None, budget_bits=None, per_channel=False, signed=False, sensitivity=None,
-                       pin=None, codes='int32', bits_bias=16):
+                       pin=None, codes='int32', bits_bias=16, correct=False):
         """mixed_plan for the weights, the nearest rounding of ``quantize`` for the biases (unless ``bits_bias >= 32``), run +
         synchronise: returns (codes, ranges, bits), each a list of one dict per network -- the biases' ranges under
-        key + '.bias', every bias bit for bit what ``quantize`` stores, ``bits[n][key]`` the width network n's layer got."""
+        key + '.bias', every bias bit for bit what ``quantize`` stores, ``bits[n][key]`` the width network n's layer got.
+
+        ``correct=True`` puts the analytic bias correction between the allocation and the quantisation, at the widths the
+        allocation chose: an allocating plan (``apply=False``), ``bc_plan().run(signed=, per_channel=, widths=that plan)`` --
+        the widths are read on the device, where the allocation left them -- then the applying plan and the biases, which are
+        quantised AFTER their correction, as the reference orders the two (main_cls.py:176-181).  The correction writes no
+        weight, so the applying plan allocates what the first one did.  Everything stays on the stream until the one
+        synchronisation at the end."""
         self._ready('quantize_mixed')
         g0 = self.nets[0][0]
         tt = tuple(self.targ_type)
-        plans = [BatchMixedPlan(self, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, codes, True)]
+        plans, first = [], []
         try:
+            if correct:
+                first = [BatchMixedPlan(self, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, None, False), self.bc_plan()]
+                first[0].run()
+                first[1].run(signed=signed, per_channel=per_channel, widths=first[0])
+            plans.append(BatchMixedPlan(self, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, codes, True))
             if bits_bias < 32 and any(type(l) in tt and l.bias is not None for l in g0.values()):
                 plans.append(BatchQuantPlan(self, plans[0].widths[-1], bits_bias, per_channel, signed, None, _biases_only=True))
             for plan in plans:
                 plan.run()
+            if correct:
+                first[1].status()              # (synchronises; an abandoned wait of the one-launch chain surfaces here)
             _ffi.synchronize()
             n = len(self.nets)
             ranges = []
@@ -505,7 +524,7 @@ class NetworkBatch:
             return ([{k: v.clone() for k, v in plans[0].codes(i).items()} for i in range(n)], ranges,
                     [dict(plans[0].bits(i)) for i in range(n)])
         finally:
-            for plan in plans:
+            for plan in plans + first:
                 plan.close()
 
     def absorb_plan(self, N=3, range_clip=None, absorb=True):

@@ -18,6 +18,7 @@
 // gathers cached values.
 #include <algorithm>
 #include <cstdlib>
+#include <deque>
 #include <map>
 #include <unordered_map>
 #include <memory>
@@ -241,12 +242,110 @@ __global__ __launch_bounds__(kBlock) void bc_row_range_kernel(const BcRowLayerDe
     }
 }
 
+// ---- widths mode (an extension: the quantiser of every corrected layer at that layer's OWN bit width -- what quant_plan(bit_weight=b)
+// or mixed_plan will store for it) ----
+// The chain is the per-channel one: its kRows bodies read {scale, min_value} per row from the plan's table.  What differs is the
+// launch in front of it.  The width of step s of network n is widths[n * stride + index[s]] (int32 on the device: where mixed_plan left
+// it), or one host-given width; a value read on the device cannot be checked by the host, so it is CLAMPED to [2, 16] here, before any
+// shift is formed from it, and the clamped word is left per step where the chain finds it (the plan's `wbits`, and next to it `wq`:
+// qmax at that width, which depends on the width alone and is what the chain needs of it).  Per row (per_channel) one launch does everything, like bc_row_range_kernel.  Per tensor that launch
+// leaves the rows' (min, max) in the table and a second, small one (a workgroup per layer) merges them into the tensor's pair and
+// writes the tensor's {scale, min_value} to every row of the layer.  Nothing here waits for another workgroup.
+struct BcWidthsDev {
+    const int32_t* widths;   // device [.. n * stride + index ..], or null: `uniform` for every step
+    const int32_t* index;    // device [rep_steps]: where in a network's widths the step's width lies
+    int64_t stride;          // int32 words from one network's widths to the next
+    int32_t rep_steps;       // steps per network of a replicated plan (a plain plan: all its steps, so n == 0)
+    int32_t uniform;
+};
+__device__ __forceinline__ int bc_step_width(const BcWidthsDev& W, int s) {
+    int b = W.uniform;
+    if (W.widths) {
+        const int n = s / W.rep_steps;
+        b = W.widths[(int64_t)n * W.stride + W.index[s - n * W.rep_steps]];
+    }
+    return min(max(b, 2), 16);
+}
+
+// eps[o, i] = sum_k (Q(W) - W)[o, i, k] of the row a wave has in hand (DFQ_BC_EPS=1 plans; sequential float32 sum from 0.0f)
+__device__ __forceinline__ void bc_row_eps(const BcRowLayerDev& L, int o, const float* __restrict__ w, const QParams& p) {
+    for (int i = threadIdx.x % kWave; i < L.in_per_group; i += kWave) {
+        float acc = 0.0f, code;
+        for (int k = 0; k < L.khkw; ++k) {
+            const float v = w[(int64_t)i * L.khkw + k];
+            acc = acc + (fake_quant_one(v, p, &code) - v);
+        }
+        L.eps[(int64_t)o * L.in_per_group + i] = acc;
+    }
+}
+
+// one wave per row, one read of the weights.  Per row: the row's {scale, min_value} at the layer's width, and the eps matrices of
+// DFQ_BC_EPS=1 plans.  Per tensor: the row's (min, max) itself goes into the row's entry of the table, for bc_widths_tensor_kernel.
+__global__ __launch_bounds__(kBlock) void bc_widths_range_kernel(const BcRowLayerDev* __restrict__ layers, const int32_t* __restrict__ row_begin,
+                                                                 int n_layers, int total_rows, float* __restrict__ rowq, BcWidthsDev W,
+                                                                 int32_t* __restrict__ wbits, float* __restrict__ wq, int per_row, int symmetric) {
+    const int r = (int)blockIdx.x * (kBlock / kWave) + (int)threadIdx.x / kWave;
+    if (r >= total_rows) return;                       // (wave-uniform: the reductions below stay whole-wave)
+    const int lane = threadIdx.x % kWave;
+    const int l = find_segment(row_begin, n_layers, r);
+    const BcRowLayerDev L = layers[l];
+    const int o = r - L.row_base;
+    const int64_t len = (int64_t)L.in_per_group * L.khkw;
+    const float* w = L.w + (int64_t)o * len;
+    float mn, mx;
+    wave_row_range(w, len, mn, mx);
+    const int bits = bc_step_width(W, l);
+    if (o == 0 && lane == 0) {
+        // the step's width words: the clamped width, and qmax of qparams_double at it for the chain (an exact integer)
+        wbits[l] = bits;
+        wq[l] = qparams_double(0.0, 0.0, bits, symmetric).qmax;
+    }
+    if (!per_row) {
+        if (lane == 0) { rowq[2 * (int64_t)r + 0] = mn; rowq[2 * (int64_t)r + 1] = mx; }
+        return;
+    }
+    const QParams p = qparams_double((double)mn, (double)mx, bits, symmetric);
+    if (lane == 0) { rowq[2 * (int64_t)r + 0] = p.scale; rowq[2 * (int64_t)r + 1] = p.min_value; }
+    if (L.eps) bc_row_eps(L, o, w, p);
+}
+
+// per tensor, behind bc_widths_range_kernel: one workgroup per layer merges the rows' pairs (selections: exact in any order, the
+// identities of a row of nothing but NaN included; no atomic of any kind, so a network's result cannot depend on the batch around
+// it) and writes the tensor's {scale, min_value} at the layer's width over them -- every pair has been read when the reduction's
+// barrier is passed.  DFQ_BC_EPS=1 plans get their eps matrices here, a wave per row.
+__global__ __launch_bounds__(kBlock) void bc_widths_tensor_kernel(const BcRowLayerDev* __restrict__ layers, float* __restrict__ rowq,
+                                                                  const int32_t* __restrict__ wbits, int symmetric) {
+    const int l = blockIdx.x;
+    const BcRowLayerDev L = layers[l];
+    float* q = rowq + 2 * (int64_t)L.row_base;
+    float mn = INFINITY, mx = -INFINITY;
+    for (int o = threadIdx.x; o < L.out_ch; o += kBlock) range_merge(mn, mx, q[2 * o + 0], q[2 * o + 1]);
+    block_range(mn, mx);
+    const QParams p = qparams_double((double)mn, (double)mx, wbits[l], symmetric);
+    for (int o = threadIdx.x; o < L.out_ch; o += kBlock) { q[2 * o + 0] = p.scale; q[2 * o + 1] = p.min_value; }
+    if (L.eps) {
+        const int64_t len = (int64_t)L.in_per_group * L.khkw;
+        for (int o = threadIdx.x / kWave; o < L.out_ch; o += kBlock / kWave) bc_row_eps(L, o, L.w + (int64_t)o * len, p);
+    }
+}
+
 // the quantiser of row `r` of the table (see bc_row_range_kernel); `base` carries qmin / qmax of the run's bit width
 __device__ __forceinline__ QParams bc_row_qparams(const QParams& base, float scale, float min_value) {
     QParams q = base;
     q.scale = scale;
     q.min_value = min_value;
     q.neg_min = -min_value;
+    return q;
+}
+
+// the width word of a step as the chain reads it: qmax of qparams_double at the step's clamped width, as a float -- one
+// workgroup-uniform load.  qmin follows from it exactly: 0, or with `symmetric` -(qmax + 1) = -2^(b-1) (the rows bring scale and
+// min_value).  Written by bc_widths_range_kernel.
+__device__ __forceinline__ QParams bc_width_base(float qmax, int symmetric) {
+    QParams q;
+    q.qmax = qmax;
+    q.qmin = symmetric ? -(q.qmax + 1.0f) : 0.0f;
+    q.neg_min = 0.0f; q.scale = 0.0f; q.min_value = 0.0f;
     return q;
 }
 
@@ -371,6 +470,8 @@ struct BcDep {            // null counters: every step is its own launch (depend
     int32_t cache_blocks;
     int32_t num_bits;     // per-channel runs (kRows bodies only): the bit width of every row's quantiser
     const float* rowq;    // ... and the per-row quantiser table {scale, min_value} (bc_row_range_kernel)
+    float wqmax;          // widths runs (kWidths bodies only): the step's own width word, fetched with its descriptor, and ...
+    const float* wq;      // widths runs (kWidths bodies only): qmax at the clamped bit width of every step, by step index (bc_widths_range_kernel)
 };
 // The error word.  Counter protocol: cleared by the run's clear launch, any non-zero value = a wait of this run was abandoned.
 // Tagged protocol (no clear launch): it holds the EPOCH of the latest run in which a wait was abandoned (atomicMax: epochs
@@ -387,7 +488,10 @@ __device__ __forceinline__ void bc_raise_err(const BcDep& dep) { atomicMax(dep.e
 // (80 against 119 VGPRs: the batch of 32 measured 0.46 against 0.49 ms).
 // kRows: per-channel mode -- every row has its own quantiser (dep.rowq, staged through sh_q), at dep.num_bits; the per-tensor
 // instantiations (kRows = false) compile to what they were.
-template <int kExp, bool kOneGroup, bool kRows = false>
+// kWidths (with kRows): qmin / qmax come from the step's own width word (dep.wqmax = wq[step], one workgroup-uniform load that
+// the kernel requests with the descriptor) instead of dep.num_bits; a folded depthwise step is a layer with a width word of its
+// own (dep.wq[its step]).  Nothing else differs, and the instantiations without it compile to what they were.
+template <int kExp, bool kOneGroup, bool kRows = false, bool kWidths = false>
 __device__ __forceinline__ void bc_step_body(const BcStepDev& st, int blk, const BcSourceDev* __restrict__ sources,
                                              const BcFoldDev* __restrict__ folds, const BcDep& dep, float* sh_E, float* sh_corr, int* sh_flag,
                                              float* sh_q = nullptr) {
@@ -457,7 +561,9 @@ __device__ __forceinline__ void bc_step_body(const BcStepDev& st, int blk, const
         __syncthreads();
         if (*sh_flag == 0) return;           // abandoned: nothing has been stored
     }
-    const QParams qp = kRows ? qparams_double(0.0, 0.0, dep.num_bits, dep.symmetric)      // (qmin / qmax only: the rows bring the rest)
+    static_assert(kRows || !kWidths, "a widths body reads the per-row quantiser table");
+    const QParams qp = kWidths ? bc_width_base(dep.wqmax, dep.symmetric)                             // (mm_index: the step's index in the caller's order)
+                     : kRows ? qparams_double(0.0, 0.0, dep.num_bits, dep.symmetric)      // (qmin / qmax only: the rows bring the rest)
                              : qparams_double((double)slot_min(mm_slot(st.mm + dep.mm_off + 0)), (double)slot_max(mm_slot(st.mm + dep.mm_off + 1)), 8, dep.symmetric);
     if (kRows) {
         // the quantisers of this workgroup's rows, staged in LDS (one global load per row, requested behind the weights)
@@ -556,7 +662,7 @@ __device__ __forceinline__ void bc_step_body(const BcStepDev& st, int blk, const
         if (F.next_bn_bias) f_nb = F.next_bn_bias[o_tail];
         if (F.next_cache) f_nw = F.next_bn_weight[o_tail];
         if (dep.mm_arrive) mm_wait(dep.mm_arrive + F.mm_index, F.mm_blocks);      // (the few threads that own a row of it; an abandoned wait is noticed behind the merges)
-        const QParams fq = kRows ? bc_row_qparams(qp, dep.rowq[2 * ((int64_t)F.row_base + o_tail) + 0], dep.rowq[2 * ((int64_t)F.row_base + o_tail) + 1])
+        const QParams fq = kRows ? bc_row_qparams(kWidths ? bc_width_base(dep.wq[F.mm_index], dep.symmetric) : qp, dep.rowq[2 * ((int64_t)F.row_base + o_tail) + 0], dep.rowq[2 * ((int64_t)F.row_base + o_tail) + 1])
                                  : qparams_double((double)slot_min(mm_slot(F.mm + dep.mm_off + 0)), (double)slot_max(mm_slot(F.mm + dep.mm_off + 1)), 8, dep.symmetric);
         float acc = 0.0f, code;
 #pragma unroll
@@ -888,6 +994,28 @@ __global__ __launch_bounds__(kBlock) void bc_step_kernel_rows(BcStepDev st_inlin
                                     sh_E, sh_corr, &sh_flag, sh_q);
 }
 
+// ... widths mode (as the per-channel kernel, with every step's qmin / qmax from its own width word)
+template <int kExp>
+__global__ __launch_bounds__(kBlock) void bc_step_kernel_widths(BcStepDev st_inline, const BcStepDev* __restrict__ table,
+                                                                const BcSourceDev* __restrict__ sources, const BcFoldDev* __restrict__ folds, int symmetric,
+                                                                const float* __restrict__ wq, const float* __restrict__ rowq) {
+    __shared__ float sh_E[kExp + 1];       // (+ the zero word of bc_step_body)
+    __shared__ float sh_corr[kBlock];
+    __shared__ float sh_q[2 * kBlock];
+    __shared__ int sh_flag;
+    union { BcStepDev st; uint32_t u[kStepWords]; } desc;
+    if (table) bc_load_step(table + blockIdx.y, desc.u);
+    else desc.st = st_inline;
+    if ((int)blockIdx.x * desc.st.rows_per_block >= desc.st.out_ch) return;
+    // the step's width word goes into a VECTOR register here: this kernel's scalar file is full (its descriptor arrives by value), and
+    // qmin / qmax living there through the row sums cost twenty scalar spills more than the per-channel kernel has
+    float qmax = wq[desc.st.mm_index];
+    asm volatile("" : "+v"(qmax));
+    bc_step_body<kExp, false, true, true>(desc.st, blockIdx.x, sources, folds,
+                                          BcDep{nullptr, nullptr, -1, 0, -1, 0, nullptr, 0u, symmetric, 0, 0, nullptr, nullptr, 0, 0, rowq, qmax, wq},
+                                          sh_E, sh_corr, &sh_flag, sh_q);
+}
+
 // the whole chain of every network in one launch: 1-D grid over (step, workgroup) in chain order; a workgroup waits
 // for the previous step of its network (lower indices only -> no deadlock, see dfq_le.hip)
 // One-launch correction (round 5): the per-tensor min/max blocks are workgroups of the chain launch.  The plan interleaves them with
@@ -913,13 +1041,13 @@ struct BcFusedMm {
 };
 
 // (the batch body at 64 VGPRs -- amdgpu_waves_per_eu(8, 8): 17 registers spilled to scratch -- measured 0.44 against 0.40 ms)
-template <int kExp, bool kOneGroup, bool kRows>
+template <int kExp, bool kOneGroup, bool kRows, bool kWidths = false>
 __device__ __forceinline__ void bc_chain_block(const BcStepDev* __restrict__ table, const BcChainRef* __restrict__ refs,
                                                const BcSourceDev* __restrict__ sources, const BcFoldDev* __restrict__ folds,
                                                uint32_t* counters, uint32_t* err, unsigned long long* tags, uint32_t epoch,
                                                int symmetric, int spin_limit, int mm_off, uint32_t* slots_clear, int n_slots_clear,
                                                const BcFusedMm& fm, int num_bits, const float* rowq,
-                                               float* sh_E, float* sh_corr, int* sh_flag, float* sh_q) {
+                                               float* sh_E, float* sh_corr, int* sh_flag, float* sh_q, const float* wq = nullptr) {
     typedef int ivec4 __attribute__((vector_size(16)));
     // the tagged chain has no clear launch in front of it: its first workgroup clears the (min, max) slots the NEXT run's
     // min/max launch accumulates into (the other parity: nobody touches it in this run)
@@ -941,9 +1069,9 @@ __device__ __forceinline__ void bc_chain_block(const BcStepDev* __restrict__ tab
     }
     union { BcStepDev st; uint32_t u[kStepWords]; } desc;
     bc_load_step(table + step, desc.u);
-    bc_step_body<kExp, kOneGroup, kRows>(desc.st, blk, sources, folds,
+    bc_step_body<kExp, kOneGroup, kRows, kWidths>(desc.st, blk, sources, folds,
                        BcDep{counters, err, __builtin_amdgcn_readfirstlane(ref[2]), __builtin_amdgcn_readfirstlane(ref[3]), step, 0,
-                             tags, epoch, symmetric, spin_limit, mm_off, fm.arrive, fm.cache_arrive, fm.cache_blocks, num_bits, rowq},
+                             tags, epoch, symmetric, spin_limit, mm_off, fm.arrive, fm.cache_arrive, fm.cache_blocks, num_bits, rowq, kWidths ? wq[desc.st.mm_index] : 0.0f, wq},
                        sh_E, sh_corr, sh_flag, sh_q);
 }
 
@@ -975,6 +1103,22 @@ __global__ __launch_bounds__(kBlock) void bc_chain_kernel_rows(const BcStepDev* 
     __shared__ int sh_flag;
     bc_chain_block<kExp, kOneGroup, true>(table, refs, sources, folds, counters, err, tags, epoch, symmetric, spin_limit, mm_off,
                                           slots_clear, n_slots_clear, fm, num_bits, rowq, sh_E, sh_corr, &sh_flag, sh_q);
+}
+
+// ... widths mode (every step's qmin / qmax from its own width word)
+template <int kExp, bool kOneGroup>
+__global__ __launch_bounds__(kBlock) void bc_chain_kernel_widths(const BcStepDev* __restrict__ table,
+                                                                 const BcChainRef* __restrict__ refs,
+                                                                 const BcSourceDev* __restrict__ sources, const BcFoldDev* __restrict__ folds,
+                                                                 uint32_t* counters, uint32_t* err, unsigned long long* tags, uint32_t epoch,
+                                                                 int symmetric, int spin_limit, int mm_off, uint32_t* slots_clear, int n_slots_clear,
+                                                                 BcFusedMm fm, const float* __restrict__ wq, const float* __restrict__ rowq) {
+    __shared__ float sh_E[kExp + 1];       // (+ the zero word of bc_step_body)
+    __shared__ float sh_corr[kBlock];
+    __shared__ float sh_q[2 * kBlock];
+    __shared__ int sh_flag;
+    bc_chain_block<kExp, kOneGroup, true, true>(table, refs, sources, folds, counters, err, tags, epoch, symmetric, spin_limit, mm_off,
+                                                slots_clear, n_slots_clear, fm, 0, rowq, sh_E, sh_corr, &sh_flag, sh_q, wq);
 }
 
 }  // namespace dfq
@@ -1031,6 +1175,19 @@ struct dfq_bc_plan {
     BcRowLayerDev* d_row_layers = nullptr;
     int32_t* d_row_begin = nullptr;
     std::map<int, hipGraphExec_t> exec_rows;
+    // widths mode (dfq_bc_plan_run_widths), set up by its first run: one clamped width word per step and the index table
+    int rep_steps = 0;                     // steps per network as created (a plain plan: all of them)
+    int32_t* d_wbits = nullptr;
+    float* d_wq = nullptr;                 // qmax per step at its clamped width: what the chain reads
+    int32_t* d_width_index = nullptr;
+    std::deque<std::vector<int32_t>> width_index;   // back(): what d_width_index holds (uploaded again when a run brings another table)
+};
+
+// the arguments of a widths run (bc_run_direct)
+struct BcWidthsRun {
+    const int32_t* widths;                 // device, or null
+    int64_t stride;
+    int32_t uniform_bits, per_row;
 };
 
 extern "C" {
@@ -1082,7 +1239,9 @@ int dfq_bc_plan_create_replicated(const dfq_layer* layers, int32_t n_layers, con
             d.fake_bias = moved(d.fake_bias, by);
         }
     }
-    return dfq_bc_plan_create(L.data(), n_layers * n_nets, S.data(), n_steps * n_nets, C.data(), n_sources * n_nets, out_plan);
+    const int rc = dfq_bc_plan_create(L.data(), n_layers * n_nets, S.data(), n_steps * n_nets, C.data(), n_sources * n_nets, out_plan);
+    if (rc == DFQ_OK) (*out_plan)->rep_steps = n_steps;          // (a widths run indexes its table by the steps as created)
+    return rc;
 }
 
 int dfq_bc_plan_create(const dfq_layer* layers, int32_t n_layers, const dfq_bc_step* steps, int32_t n_steps,
@@ -1133,6 +1292,7 @@ int dfq_bc_plan_create(const dfq_layer* layers, int32_t n_layers, const dfq_bc_s
 
     dfq_bc_plan* p = new dfq_bc_plan();
     p->n_steps = n_steps;
+    p->rep_steps = n_steps;
     p->mm_chunk = mm_chunk;
     p->eps_elems = eps_true;
     hipError_t e;
@@ -1513,7 +1673,7 @@ int dfq_bc_plan_create(const dfq_layer* layers, int32_t n_layers, const dfq_bc_s
     return DFQ_OK;
 }
 
-static int bc_run_direct(dfq_bc_plan* p, int32_t symmetric, hipStream_t st, int row_bits = 0);
+static int bc_run_direct(dfq_bc_plan* p, int32_t symmetric, hipStream_t st, int row_bits = 0, const BcWidthsRun* wr = nullptr);
 
 int dfq_bc_plan_run(dfq_bc_plan* p, int32_t symmetric, void* stream) {
     if (!p) return fail_arg("dfq_bc_plan_run: null plan");
@@ -1540,10 +1700,8 @@ int dfq_bc_plan_run(dfq_bc_plan* p, int32_t symmetric, void* stream) {
 // Per-channel mode (extension; the per-output-channel counterpart of dfq.py:216-219): the correction of dfq_bc_plan_run with the
 // quantiser of every weight row formed from that row's own (min, max) at `num_bits` bits (utils/quantize.py:23-76, recipe A).  Every
 // hand-over protocol of the plan is kept; the per-row quantisers come from bc_row_range_kernel, a launch in front of the chain.
-int dfq_bc_plan_run_per_channel(dfq_bc_plan* p, int32_t symmetric, int32_t num_bits, void* stream) {
-    if (!p) return fail_arg("dfq_bc_plan_run_per_channel: null plan");
-    if (num_bits < 2 || num_bits > 16) return fail_arg("dfq_bc_plan_run_per_channel: num_bits %d outside [2, 16]", (int)num_bits);
-    hipStream_t st = as_stream(stream);
+// the per-row tables of the per-channel and widths modes, once per plan
+static int bc_ensure_row_tables(dfq_bc_plan* p) {
     if (!p->d_rowq) {
         // the per-row tables, once per plan (host copies of the steps carry everything)
         std::vector<BcRowLayerDev> rl(p->n_steps);
@@ -1563,6 +1721,14 @@ int dfq_bc_plan_run_per_channel(dfq_bc_plan* p, int32_t symmetric, int32_t num_b
         DFQ_HIP_TRY(hipMemcpy(p->d_row_begin, rb.data(), sizeof(int32_t) * (p->n_steps + 1), hipMemcpyHostToDevice));
         p->total_rows = total;
     }
+    return DFQ_OK;
+}
+
+int dfq_bc_plan_run_per_channel(dfq_bc_plan* p, int32_t symmetric, int32_t num_bits, void* stream) {
+    if (!p) return fail_arg("dfq_bc_plan_run_per_channel: null plan");
+    if (num_bits < 2 || num_bits > 16) return fail_arg("dfq_bc_plan_run_per_channel: num_bits %d outside [2, 16]", (int)num_bits);
+    hipStream_t st = as_stream(stream);
+    if (const int rc = bc_ensure_row_tables(p)) return rc;
     const char* ge = getenv("DFQ_GRAPH");
     if (!(ge && ge[0] == '1')) return bc_run_direct(p, symmetric, st, num_bits);
     hipGraphExec_t& exec = p->exec_rows[(symmetric ? 1 : 0) + 2 * num_bits];
@@ -1581,10 +1747,44 @@ int dfq_bc_plan_run_per_channel(dfq_bc_plan* p, int32_t symmetric, int32_t num_b
     return DFQ_OK;
 }
 
-// row_bits: 0 = per-tensor (dfq_bc_plan_run), else the bit width of a per-channel run
-static int bc_run_direct(dfq_bc_plan* p, int32_t symmetric, hipStream_t st, int row_bits) {
+// Widths mode (extension): the correction of dfq_bc_plan_run / dfq_bc_plan_run_per_channel with every layer's quantiser at that
+// layer's own bit width (include/dfq_hip.h holds the definition).  Never recorded: its arguments are not fixed per plan, so
+// DFQ_GRAPH=1 runs it directly.
+int dfq_bc_plan_run_widths(dfq_bc_plan* p, int32_t symmetric, int32_t per_row, const int32_t* widths, int64_t width_stride,
+                           const int32_t* width_index, int32_t uniform_bits, void* stream) {
+    if (!p) return fail_arg("dfq_bc_plan_run_widths: null plan");
+    if (!widths && (uniform_bits < 2 || uniform_bits > 16))
+        return fail_arg("dfq_bc_plan_run_widths: uniform_bits %d outside [2, 16]", (int)uniform_bits);
+    if (widths && !width_index) return fail_arg("dfq_bc_plan_run_widths: device widths need a width_index table");
+    if (widths && width_stride < 0) return fail_arg("dfq_bc_plan_run_widths: negative width_stride");
+    if (widths)
+        for (int s = 0; s < p->rep_steps; ++s)
+            if (width_index[s] < 0) return fail_arg("dfq_bc_plan_run_widths: width_index[%d] is negative", s);
+    hipStream_t st = as_stream(stream);
+    if (const int rc = bc_ensure_row_tables(p)) return rc;
+    if (!p->d_wbits) {
+        DFQ_HIP_TRY(p->mem.alloc((void**)&p->d_wbits, sizeof(int32_t) * p->n_steps));
+        DFQ_HIP_TRY(p->mem.alloc((void**)&p->d_wq, sizeof(float) * (size_t)p->n_steps));
+        DFQ_HIP_TRY(p->mem.alloc((void**)&p->d_width_index, sizeof(int32_t) * p->rep_steps));
+    }
+    if (widths && (p->width_index.empty() || !std::equal(p->width_index.back().begin(), p->width_index.back().end(), width_index))) {
+        // On the run's stream: behind every earlier run that reads the table.  The source is a copy the plan keeps until it is
+        // destroyed, so nothing waits for the host; a caller that keeps changing tables pays a synchronisation every eighth change.
+        if (p->width_index.size() >= 8) {
+            DFQ_HIP_TRY(hipStreamSynchronize(st));
+            p->width_index.clear();
+        }
+        p->width_index.emplace_back(width_index, width_index + p->rep_steps);
+        DFQ_HIP_TRY(hipMemcpyAsync(p->d_width_index, p->width_index.back().data(), sizeof(int32_t) * p->rep_steps, hipMemcpyHostToDevice, st));
+    }
+    const BcWidthsRun wr{widths, width_stride, uniform_bits, per_row ? 1 : 0};
+    return bc_run_direct(p, symmetric, st, 0, &wr);
+}
+
+// row_bits: 0 = per-tensor (dfq_bc_plan_run), else the bit width of a per-channel run; wr: a widths run (row_bits unused)
+static int bc_run_direct(dfq_bc_plan* p, int32_t symmetric, hipStream_t st, int row_bits, const BcWidthsRun* wr) {
     const bool chain = p->merged && p->chain_blocks > 0;
-    const bool rows = row_bits > 0;
+    const bool rows = row_bits > 0 || wr != nullptr;
     // (the NULL stream is a caller's stream like any other: `capture_stream` is null until a graph is recorded, and until round 5
     //  a run on the NULL stream compared equal to it -- counter protocol, no guard: 250 instead of 130 us for a MobileNetV2)
     const bool capturing = p->capture_stream != nullptr && st == p->capture_stream;
@@ -1608,7 +1808,20 @@ static int bc_run_direct(dfq_bc_plan* p, int32_t symmetric, hipStream_t st, int 
     const int cache_blocks = (p->cache_total + kBlock - 1) / kBlock;
     // one-launch correction: the min/max blocks are workgroups of the tagged chain launch below
     const bool one_launch = tagged_run && p->fused_mm;
-    if (rows) {
+    if (wr) {
+        // widths: every row's quantiser at its layer's own width, the clamped width words (and, for DFQ_BC_EPS=1 plans, the eps
+        // matrices) in front of everything that reads them; per tensor in two launches (bc_widths_range_kernel)
+        const BcWidthsDev W{wr->widths, (const int32_t*)p->d_width_index, wr->stride, p->rep_steps, wr->uniform_bits};
+        hipLaunchKernelGGL(bc_widths_range_kernel, dim3((p->total_rows + kBlock / kWave - 1) / (kBlock / kWave)), dim3(kBlock), 0, st,
+                           (const BcRowLayerDev*)p->d_row_layers, (const int32_t*)p->d_row_begin, p->n_steps, p->total_rows, p->d_rowq, W,
+                           p->d_wbits, p->d_wq, (int)wr->per_row, (int)symmetric);
+        DFQ_CHECK_LAUNCH();
+        if (!wr->per_row) {
+            hipLaunchKernelGGL(bc_widths_tensor_kernel, dim3(p->n_steps), dim3(kBlock), 0, st, (const BcRowLayerDev*)p->d_row_layers,
+                               p->d_rowq, (const int32_t*)p->d_wbits, (int)symmetric);
+            DFQ_CHECK_LAUNCH();
+        }
+    } else if (rows) {
         // per-channel: every row's quantiser (and, for DFQ_BC_EPS=1 plans, the eps matrices) in front of everything that reads them
         hipLaunchKernelGGL(bc_row_range_kernel, dim3((p->total_rows + kBlock / kWave - 1) / (kBlock / kWave)), dim3(kBlock), 0, st,
                            (const BcRowLayerDev*)p->d_row_layers, (const int32_t*)p->d_row_begin, p->n_steps, p->total_rows, p->d_rowq,
@@ -1651,7 +1864,13 @@ static int bc_run_direct(dfq_bc_plan* p, int32_t symmetric, hipStream_t st, int 
         const int grid_blocks = one_launch ? p->chain_blocks_fused : p->chain_blocks;
         const BcChainRef* ref_table = one_launch ? p->d_refs_fused : p->d_refs;
 #define DFQ_BC_CHAIN_LAUNCH(EXP, ONE)                                                                                                  \
-        do { if (rows)                                                                                                                 \
+        do { if (wr)                                                                                                                   \
+            hipLaunchKernelGGL((bc_chain_kernel_widths<EXP, ONE>), dim3(grid_blocks), dim3(kBlock), 0, st, (const BcStepDev*)p->d_steps, \
+                               ref_table, (const BcSourceDev*)p->d_sources, (const BcFoldDev*)p->d_folds, p->d_counters,                \
+                               err, tags, p->epoch, (int)symmetric, spin_limit, mm_off,                                                 \
+                               tagged_run ? p->d_slots + (parity ^ 1) * (3 * p->n_steps + 1) : nullptr, 3 * p->n_steps + 1, fm,         \
+                               (const float*)p->d_wq, (const float*)p->d_rowq);                                                         \
+        else if (rows)                                                                                                                 \
             hipLaunchKernelGGL((bc_chain_kernel_rows<EXP, ONE>), dim3(grid_blocks), dim3(kBlock), 0, st, (const BcStepDev*)p->d_steps, \
                                ref_table, (const BcSourceDev*)p->d_sources, (const BcFoldDev*)p->d_folds, p->d_counters,                \
                                err, tags, p->epoch, (int)symmetric, spin_limit, mm_off,                                                 \
@@ -1670,7 +1889,14 @@ static int bc_run_direct(dfq_bc_plan* p, int32_t symmetric, hipStream_t st, int 
     }
     for (const auto& L : p->launches) {
         const BcStepDev* table = (L.n == 1) ? nullptr : p->d_steps + L.begin;
-        if (rows) {
+        if (wr) {
+            if (L.max_expect <= kExpectSmall)
+                hipLaunchKernelGGL(bc_step_kernel_widths<kExpectSmall>, dim3(L.max_blocks, L.n), dim3(kBlock), 0, st, p->launch_steps[L.begin], table,
+                                   (const BcSourceDev*)p->d_sources, (const BcFoldDev*)p->d_folds, (int)symmetric, (const float*)p->d_wq, (const float*)p->d_rowq);
+            else
+                hipLaunchKernelGGL(bc_step_kernel_widths<kExpectMax>, dim3(L.max_blocks, L.n), dim3(kBlock), 0, st, p->launch_steps[L.begin], table,
+                                   (const BcSourceDev*)p->d_sources, (const BcFoldDev*)p->d_folds, (int)symmetric, (const float*)p->d_wq, (const float*)p->d_rowq);
+        } else if (rows) {
             if (L.max_expect <= kExpectSmall)
                 hipLaunchKernelGGL(bc_step_kernel_rows<kExpectSmall>, dim3(L.max_blocks, L.n), dim3(kBlock), 0, st, p->launch_steps[L.begin], table,
                                    (const BcSourceDev*)p->d_sources, (const BcFoldDev*)p->d_folds, (int)symmetric, row_bits, (const float*)p->d_rowq);

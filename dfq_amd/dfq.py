@@ -633,7 +633,7 @@ def _bc_template(graph, bottoms, targ_type, bn_type):
 def _fast_bc_tables(items, targ_type, bn_type, dev):
     T = _Tables()
     geo, steps, srcs = [], [], []
-    T.step_out_ch, T.step_in = [], []
+    T.step_out_ch, T.step_in, T.step_keys = [], [], []
     tens = []
     w_pos, b_row, b_pos, nx_row, nx_pos, sw_row, sw_pos, sb_row, sb_pos = [], [], [], [], [], [], [], [], []
     n_lay = n_stp = n_src = 0
@@ -677,6 +677,7 @@ def _fast_bc_tables(items, targ_type, bn_type, dev):
         srcs.append(t['src_arr'])
         T.step_out_ch.extend(t['step_out_ch'])
         T.step_in.extend(t['step_in'])
+        T.step_keys.extend(t['keys'][li] for (li, _, _) in t['steps'])
         n_lay += len(mods)
         n_stp += len(sa)
         n_src += len(t['src_arr'])
@@ -1431,15 +1432,20 @@ class BCPlan:
         self.stage = stage or _ffi.Stage()
         self._keep = []
         self._mutable, self._snapshot, self.repeated = [], None, 0      # see run(check=True)
+        # run(widths=): the graph keys of the steps as created (one network's; None where the builder does not know them), how
+        # many networks the plan replicates them for, and what the latest widths run must keep alive
+        self.keys, self.n_nets, self._widths_keep, self._widths_map = None, 1, None, None
         if isinstance(layers, _Tables):                     # prebuilt struct arrays (build_bc_plan_batch's fast path)
             t = layers
             self._keep = t.keep
             self._mutable = list(t.mutable)
             self.n_steps = t.n_steps
             self.step_out_ch, self.step_in = t.step_out_ch, t.step_in
+            self.keys = getattr(t, 'step_keys', None)
+            self._created_steps = t.n_steps
             self._plan = ctypes.c_void_p()
             if t.bases is not None:                         # one network's tables + a base address per network (arena.py)
-                n = len(t.bases)
+                n = self.n_nets = len(t.bases)
                 self.n_steps, self.step_out_ch, self.step_in = t.n_steps * n, t.step_out_ch * n, t.step_in * n
                 _ffi.check(_ffi.lib().dfq_bc_plan_create_replicated(
                     t.ptr('layers', _ffi.DfqLayer), t.n_layers, t.ptr('steps', _ffi.DfqBcStep), t.n_steps,
@@ -1471,7 +1477,7 @@ class BCPlan:
             self._mutable.append(dn)
             step_arr.append(_ffi.DfqBcStep(int(li), begin, len(srcs), dn.data_ptr() if dn is not None else None,
                                            int(net), 0))
-        self.n_steps = len(step_arr)
+        self.n_steps = self._created_steps = len(step_arr)
         self.step_out_ch = [int(layers[li][0].shape[0]) for (li, _, _, _) in steps]
         self.step_in = [int(layers[li][0].shape[1]) for (li, _, _, _) in steps]
         larr = (_ffi.DfqLayer * len(entries))(*entries)
@@ -1498,7 +1504,7 @@ class BCPlan:
         """From now on one launch per chain position: nothing waits, nothing can be abandoned (dfq_bc_plan_set_safe_mode)."""
         _ffi.check(_ffi.lib().dfq_bc_plan_set_safe_mode(self._plan))
 
-    def run(self, signed=False, check=False, recover=True, per_channel=False, bits=8):
+    def run(self, signed=False, check=False, recover=True, per_channel=False, bits=8, widths=None):
         """Enqueue the whole correction (asynchronous).  ``check`` synchronises; with ``recover`` (default) a run in which a
         workgroup of the one-launch chain gave up its wait (DFQ_ERR_ABANDONED) is then REPEATED instead of raised: biases and BN
         proxies go back to a device-side copy taken in front of the run, the plan switches to one launch per chain position for
@@ -1506,15 +1512,29 @@ class BCPlan:
         and an abandoned run surfaces at the next ``status()``.
 
         ``per_channel`` (extension): the quant error of output row o is Q_o(W) - W with row o's own (min, max) at ``bits``
-        bits (2..16; dfq_bc_plan_run_per_channel).  The per-tensor mode ignores ``bits`` (8, like dfq.py:218)."""
-        if per_channel:
+        bits (2..16; dfq_bc_plan_run_per_channel).  The per-tensor mode ignores ``bits`` (8, like dfq.py:218).
+
+        ``widths`` (extension; dfq_bc_plan_run_widths holds the definition): every layer's quant error at that layer's OWN bit
+        width -- per tensor, or per output row with ``per_channel`` -- the error of what ``quant_plan(bit_weight=that width)`` or
+        ``mixed_plan`` will store for it.  ``None``: the behaviour above in every respect.  An ``int``: one width for every
+        step (2..16), per tensor too.  A mapping ``graph key -> int``: plans that know their keys (``build_bc_plan``,
+        ``NetworkBatch.bc_plan``, ``bias_correction``); every network of a batch gets the same widths.  A ``BatchMixedPlan``:
+        its bits block is read on the device, where its run left it -- nothing goes to the host; its ``per_channel`` /
+        ``signed`` must be the run's.  ``(tensor, width_index[, width_stride])``: a device int32 tensor, the width of step s of
+        network n is ``tensor[n * width_stride + width_index[s]]`` (one index per step as created); values outside [2, 16]
+        that the device reads are clamped.  ValueError for a step without a width and for a host-given width outside [2, 16].
+        ``bits`` is not used by a widths run."""
+        wargs = None
+        if widths is not None:
+            wargs = self._widths_args(widths, per_channel, signed)
+        elif per_channel:
             _check_bits(bits)
         guard = check and recover and self.has_waits
         if guard:
             if self._snapshot is None:
                 self._snapshot = _Snapshot(self._mutable)
             self._snapshot.take()
-        self._launch(signed, per_channel, bits)
+        self._launch(signed, per_channel, bits, wargs)
         if check:
             try:
                 self.status()
@@ -1525,11 +1545,68 @@ class BCPlan:
                 self.set_safe_mode()
                 self.repeated += 1
                 degraded_runs['bc'] += 1
-                self._launch(signed, per_channel, bits)
+                self._launch(signed, per_channel, bits, wargs)
                 self.status()
 
-    def _launch(self, signed, per_channel, bits):
-        if per_channel:
+    def _widths_args(self, widths, per_channel, signed):
+        """(device int32 tensor or None, width_stride, host index table or None, uniform bits) of run(widths=)"""
+        from collections.abc import Mapping
+        if isinstance(widths, int) and not isinstance(widths, bool):
+            _check_width(widths, 'every step')
+            return (None, 0, None, int(widths))
+        if hasattr(widths, 'bits_block') and hasattr(widths, 'keys') and not isinstance(widths, Mapping):      # a BatchMixedPlan
+            if bool(widths.per_channel) != bool(per_channel) or bool(widths.signed) != bool(signed):
+                raise ValueError('BCPlan.run: the mixed plan allocated for per_channel={}, signed={}, the run corrects per_channel={}, '
+                                 'signed={}'.format(widths.per_channel, widths.signed, bool(per_channel), bool(signed)))
+            if widths.n_nets != self.n_nets:
+                raise ValueError('BCPlan.run: the mixed plan covers {} networks, this plan {}'.format(widths.n_nets, self.n_nets))
+            tensor, table, stride = widths.bits_block, list(widths.keys), widths.n_tensors
+        elif isinstance(widths, Mapping):
+            if self.keys is None:
+                raise ValueError('BCPlan.run: this plan does not know the graph keys of its steps; give (tensor, width_index)')
+            missing = [key for key in self.keys if key not in widths]
+            if missing:
+                raise ValueError('BCPlan.run: no width for the step(s) {!r}'.format(missing))
+            for key in self.keys:
+                _check_width(widths[key], repr(key))
+            values = tuple(int(widths[key]) for key in self.keys)
+            if self._widths_map is None or self._widths_map[0] != values:      # (one upload per distinct mapping)
+                self._widths_map = (values, torch.tensor(values, dtype=torch.int32, device=self.stage.device))
+            tensor, stride, index, table = self._widths_map[1], 0, list(range(len(values))), None
+        elif isinstance(widths, (tuple, list)) and len(widths) in (2, 3) and isinstance(widths[0], torch.Tensor):
+            tensor, index = widths[0], [int(i) for i in widths[1]]
+            stride = int(widths[2]) if len(widths) == 3 else 0
+            table = None
+        else:
+            raise ValueError('BCPlan.run: widths must be None, an int, a mapping key -> int, a BatchMixedPlan or '
+                             '(int32 device tensor, width_index[, width_stride]), got {!r}'.format(type(widths)))
+        if table is not None:
+            if self.keys is None:
+                raise ValueError('BCPlan.run: this plan does not know the graph keys of its steps; give (tensor, width_index)')
+            where = {key: i for i, key in enumerate(table)}
+            missing = [key for key in self.keys if key not in where]
+            if missing:
+                raise ValueError('BCPlan.run: no width for the step(s) {!r}'.format(missing))
+            index = [where[key] for key in self.keys]
+        dev = self.stage.device
+        same_device = tensor.device.type == dev.type and (dev.index is None or tensor.device.index == dev.index)
+        if tensor.dtype is not torch.int32 or not tensor.is_contiguous() or not same_device:
+            raise ValueError('BCPlan.run: the widths must be a contiguous int32 tensor on {}'.format(self.stage.device))
+        if len(index) != self._created_steps:
+            raise ValueError('BCPlan.run: width_index has {} entries, the plan was created with {} steps'.format(
+                len(index), self._created_steps))
+        if stride < 0 or min(index) < 0 or (self.n_nets - 1) * stride + max(index) >= tensor.numel():
+            raise ValueError('BCPlan.run: width_index / width_stride reach outside the {} widths given'.format(tensor.numel()))
+        return (tensor, stride, (ctypes.c_int32 * len(index))(*index), 0)
+
+    def _launch(self, signed, per_channel, bits, wargs=None):
+        if wargs is not None:
+            tensor, stride, index, uniform = wargs
+            self._widths_keep = wargs                       # (the device reads the tensor when the stream gets there)
+            _ffi.check(_ffi.lib().dfq_bc_plan_run_widths(self._plan, int(bool(signed)), int(bool(per_channel)),
+                                                         None if tensor is None else tensor.data_ptr(), stride, index, uniform,
+                                                         _ffi.stream_arg()))
+        elif per_channel:
             _ffi.check(_ffi.lib().dfq_bc_plan_run_per_channel(self._plan, int(bool(signed)), int(bits), _ffi.stream_arg()))
         else:
             _ffi.check(_ffi.lib().dfq_bc_plan_run(self._plan, int(bool(signed)), _ffi.stream_arg()))
@@ -1627,7 +1704,9 @@ def build_bc_plan(graph, bottoms, targ_type, bn_type=torch.nn.BatchNorm2d, stage
     """Walk the graph like dfq.py:194-293 and flatten what each layer's correction needs."""
     stage = stage or _ffi.Stage()
     layers, steps, keys = _bc_tables(graph, bottoms, targ_type, bn_type)
-    return BCPlan(layers, steps, stage=stage), keys
+    plan = BCPlan(layers, steps, stage=stage)
+    plan.keys = list(keys)
+    return plan, keys
 
 
 def _bc_tables(graph, bottoms, targ_type, bn_type, base=0, net=0):
@@ -1687,24 +1766,38 @@ def _bc_tables_cached(graph, bottoms, targ_type, bn_type):
     return layers, steps, [t['keys'][li] for (li, _, _) in t['steps']]
 
 
+def _check_width(bits, what):
+    """A host-given width of a widths run (BCPlan.run(widths=)): an int in [2, 16]."""
+    if isinstance(bits, bool) or not isinstance(bits, int) or not 2 <= bits <= 16:
+        raise ValueError('bias correction: the width of {} must be an int in [2, 16], got {!r}'.format(what, bits))
+
+
 def _check_bits(bits):
     """Bit widths of the per-channel quantisers: an int in [2, 16]."""
     if isinstance(bits, bool) or not isinstance(bits, int) or not 2 <= bits <= 16:
         raise ValueError('per-channel bit width must be an int in [2, 16], got {!r}'.format(bits))
 
 
-def bias_correction(graph, bottoms, targ_type, bits_weight=8, bn_type=torch.nn.BatchNorm2d, signed=False, per_channel=False):
+def bias_correction(graph, bottoms, targ_type, bits_weight=8, bn_type=torch.nn.BatchNorm2d, signed=False, per_channel=False,
+                    widths=None):
     """Analytic bias correction: b -= eps . E[x], propagated into the next BN's beta~.
 
     ``bits_weight`` is accepted and ignored -- the reference hard-codes 8 bits (dfq.py:218).
     ``per_channel=True`` (extension): eps is the quant error of a per-output-channel quantiser -- row o quantised with its own
     (min, max) at ``bits_weight`` bits (2..16, else ValueError) -- the error a per-channel int8 deployment makes.
+    ``widths`` (extension): an int, or ``{graph key: bits}`` with a width for every corrected layer (the ``'bits'`` entries of
+    ``quantize_mixed``'s result, the values of ``NetworkBatch.quantize_mixed``'s ``bits[n]``): eps is the quant error at each
+    layer's OWN width, per tensor or per channel -- ``BCPlan.run(widths=)``; ``bits_weight`` is then not used.  ValueError for a
+    corrected layer without a width and a width outside [2, 16].
     """
-    if per_channel:
+    from collections.abc import Mapping
+    if widths is not None and (isinstance(widths, bool) or not isinstance(widths, (int, Mapping))):
+        raise ValueError('bias_correction: widths must be None, an int or a mapping key -> int, got {!r}'.format(type(widths)))
+    if per_channel and widths is None:
         _check_bits(bits_weight)
     print("Start bias correction")
     with torch.no_grad(), _cache_lock:
-        layers, steps, _ = _bc_tables_cached(graph, bottoms, targ_type, bn_type)
+        layers, steps, step_keys = _bc_tables_cached(graph, bottoms, targ_type, bn_type)
         if not steps:
             return                                       # no layer behind a BN: nothing to correct (dfq.py:197-199)
         dev = _ffi.target_device()
@@ -1716,7 +1809,7 @@ def bias_correction(graph, bottoms, targ_type, bits_weight=8, bn_type=torch.nn.B
                 scope.prefetch([x for (w, b, g) in layers for x in (w, b)] +
                                [x for st in steps for (fw, fb, relu, concat) in st[1] for x in (fw, fb)] + [st[2] for st in steps])
             tk = lambda t: _tensor_key(t, dev, scope)    # noqa: E731
-            key = (_env_key(), 'per_channel' if per_channel else 'per_tensor') + tuple((tk(w), tk(b), g) for (w, b, g) in layers) + tuple(
+            key = (_env_key(), ('per_channel' if per_channel else 'per_tensor') + ('' if widths is None else '+widths')) + tuple((tk(w), tk(b), g) for (w, b, g) in layers) + tuple(
                 (li, tuple((tk(fw), tk(fb), bool(relu), bool(cat)) for (fw, fb, relu, cat) in srcs), tk(nxt)) for (li, srcs, nxt, _) in steps)
         except _Uncacheable:
             key = None
@@ -1729,10 +1822,11 @@ def bias_correction(graph, bottoms, targ_type, bits_weight=8, bn_type=torch.nn.B
         else:
             plan_cache_stats['bc_misses'] += 1
             plan = BCPlan(layers, steps, stage=stage)
+            plan.keys = list(step_keys)
             if key is not None:
                 _cache_put(_bc_plan_cache, key, (plan,))
         try:
-            plan.run(signed=signed, check=True, per_channel=per_channel, bits=bits_weight if per_channel else 8)
+            plan.run(signed=signed, check=True, per_channel=per_channel, bits=bits_weight if per_channel else 8, widths=widths)
         except Exception as exc:
             if key is not None:
                 _cache_drop(_bc_plan_cache, key)

@@ -941,6 +941,28 @@ int dfq_bc_plan_run(dfq_bc_plan* plan, int32_t symmetric, void* stream);
  * row o's own (min, max) at `num_bits` (2..16) bits.  One more launch in front of the chain reduces every row; every
  * hand-over protocol of the plan is kept.  DFQ_ERR_ARG for a null plan or a bad bit width.  Asynchronous. */
 int dfq_bc_plan_run_per_channel(dfq_bc_plan* plan, int32_t symmetric, int32_t num_bits, void* stream);
+/* Widths mode (extension): dfq_bc_plan_run (per_row == 0) or dfq_bc_plan_run_per_channel (per_row != 0) with exactly one
+ * thing replaced -- the correction step of layer t of network n uses
+ *     eps[o, i] = sum_k (fake_quant(w; qparams_double(min, max, b[n][t], symmetric)) - w)[o, i, k],
+ * a sequential float32 sum from 0.0f as in the other modes, with b[n][t] that layer's OWN bit width and (min, max) the
+ * tensor's pair, or with `per_row` row o's pair (NaN rule: "Special values").  E[x] and its add / cat merges, the grouped
+ * matvec, b -= bias, next beta~ += -bias, the chain order, the depthwise folds and every hand-over protocol are untouched, so
+ * eps is term for term the error of what a quantisation of that layer at b[n][t] bits (dfq_batch_quant_plan,
+ * dfq_batch_mixed_plan with the same per_channel / signed) will store -- computed before it is stored.
+ * Widths: `widths` is int32 on the device, the width of step s of network n is widths[n * width_stride + width_index[s]];
+ * `width_index` is a HOST table with one entry per step of the plan as created (a replicated plan: network 0's steps; a
+ * plain plan: all steps, network 0 throughout, width_stride unused).  It is uploaded when it differs from the last run's.
+ * widths == NULL: `uniform_bits` for every step.  Valid widths are 2..16.  A host-given width is checked here; a value read
+ * on the device cannot be, so the device CLAMPS it to [2, 16] before any shift is formed from it.
+ * One launch (per_row) or two (per tensor: a workgroup per layer merges the rows' pairs into the tensor's -- selections,
+ * exact in any order, no atomic -- and writes it to every row) in front of the chain, one read of the weights more than
+ * the chain's own.  Never recorded (DFQ_GRAPH=1 runs it directly: its arguments are not fixed per plan).
+ * dfq_bc_plan_set_safe_mode / dfq_bc_plan_status as for a per-channel run.  DFQ_ERR_ARG for a null plan, uniform_bits
+ * outside [2, 16] when widths is NULL, widths without width_index, a negative index or stride.  Asynchronous. */
+int dfq_bc_plan_run_widths(dfq_bc_plan* plan, int32_t symmetric, int32_t per_row,
+                           const int32_t* widths /* device, or NULL */, int64_t width_stride,
+                           const int32_t* width_index /* host, one per step as created; NULL with widths == NULL */,
+                           int32_t uniform_bits /* used when widths == NULL */, void* stream);
 /* device pointers into the plan's scratch (tests): the correction vector bias[O] of a step; eps[O*I/g] only for plans
  * created with DFQ_BC_EPS=1 in the environment (debug: one more launch materialises the row sums the chain computes on the
  * fly, same arithmetic) -- NULL otherwise */
