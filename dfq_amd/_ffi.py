@@ -113,6 +113,16 @@ class DfqBatchMixedConfig(Structure):
                 ('code_bytes', c_int32), ('pad', c_int32), ('budget_bits', c_int64)]
 
 
+class DfqBatchPackTensor(Structure):
+    _fields_ = [('code_offset', c_int64), ('numel', c_int64), ('num_bits', c_int32), ('width_index', c_int32), ('symmetric', c_int32),
+                ('pad', c_int32)]
+
+
+class DfqBatchUnpackTensor(Structure):
+    _fields_ = [('data', c_void_p), ('rows', c_int64), ('row_len', c_int64), ('code_offset', c_int64), ('numel', c_int64),
+                ('range_offset', c_int64), ('num_bits', c_int32), ('width_index', c_int32), ('symmetric', c_int32), ('per_row', c_int32)]
+
+
 class DfqBatchActResult(Structure):
     _fields_ = [('step_begin', c_int32), ('step_count', c_int32)]
 
@@ -267,6 +277,18 @@ SIGNATURES = {
     'dfq_batch_mixed_plan_run': (c_int32, [c_void_p, c_void_p]),
     'dfq_batch_mixed_plan_destroy': (None, [c_void_p]),
     'dfq_batch_mixed_plan_launches': (c_int32, [c_void_p]),
+    'dfq_batch_pack_plan_create': (c_int32, [POINTER(DfqBatchPackTensor), c_int32, POINTER(c_void_p), c_int32, c_void_p, c_int32, c_int64,
+                                             c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, POINTER(c_void_p)]),
+    'dfq_batch_pack_plan_run': (c_int32, [c_void_p, c_void_p]),
+    'dfq_batch_pack_plan_destroy': (None, [c_void_p]),
+    'dfq_batch_pack_plan_launches': (c_int32, [c_void_p]),
+    'dfq_batch_pack_chunk_elements': (c_int64, []),
+    'dfq_batch_unpack_plan_create': (c_int32, [POINTER(DfqBatchUnpackTensor), c_int32, POINTER(c_void_p), c_int32, c_void_p, c_int64,
+                                               c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32, c_int64, c_void_p,
+                                               POINTER(c_void_p)]),
+    'dfq_batch_unpack_plan_run': (c_int32, [c_void_p, c_void_p]),
+    'dfq_batch_unpack_plan_destroy': (None, [c_void_p]),
+    'dfq_batch_unpack_plan_launches': (c_int32, [c_void_p]),
     'dfq_batch_act_plan_create': (c_int32, [POINTER(DfqBatchActResult), c_int32, POINTER(DfqBatchActStep), c_int32,
                                             POINTER(DfqBatchActSource), c_int32, POINTER(c_void_p), c_int32, c_float, c_float,
                                             c_void_p, c_int64, POINTER(c_void_p)]),

@@ -49,6 +49,9 @@ With a width per layer the correction has to see the widths, so the allocation c
 fold_plan -> le_plan -> absorb_plan -> clip_plan -> mixed_plan(apply=False) -> bc_plan.run(widths=) -> mixed_plan ->
 act_range_plan; ``bc_plan().run(widths=that plan)`` reads every (network, layer)'s width on the device, where the allocation
 left it, and ``quantize_mixed(correct=True)`` is the three steps and the biases in one call (tests/test_bc_widths.py).
+``pack_plan`` packs the codes a ``quant_plan``, ``squant_plan`` or ``mixed_plan`` wrote densely, every tensor of every network at
+its own width (read on the device), ``unpack_plan`` rebuilds codes and weights from the packed words, and ``save_packed`` /
+``load_packed`` put a quantised batch into one ``.npz`` and back (tests/test_batch_pack.py).
 """
 from __future__ import annotations
 
@@ -527,6 +530,94 @@ class NetworkBatch:
             for plan in plans + first:
                 plan.close()
 
+    def pack_plan(self, source, word_stride=None):
+        """One plan (BatchPackPlan) that packs the integer codes of ``source`` -- a BatchQuantPlan, BatchSquantPlan or
+        BatchMixedPlan of this batch created with ``codes`` -- densely, every weight of every network at its own width: the
+        stream, the offsets and the status the comment of dfq_batch_pack_plan_create (include/dfq_hip.h) defines.  A mixed
+        plan must have been created with ``apply=True`` (its codes are what is packed); its ``bits_block`` is read on the
+        device, so ``source.run()`` and ``run()`` of this plan can be enqueued back to back.  The other two sources have one
+        width.  ``word_stride``: uint32 words per network of the packed block; by default the exact size for one width, and
+        ceil(budget / 32) + 5 T rounded up to 4 for a mixed plan -- enough whenever ``used <= budget``; ``status(n) == 1`` says so when it is
+        not.  ValueError for a source without codes, a mixed plan without ``apply``, a closed source, a source of another
+        batch."""
+        self.check()
+        return BatchPackPlan(self, source, word_stride)
+
+    def unpack_plan(self, packed, weights=True, codes=None):
+        """One plan (BatchUnpackPlan) for the way back: from the words of ``packed`` -- a BatchPackPlan of this batch that
+        has run, or the PackedBatch ``load_packed`` returns -- to the weights of every network, in place (``weights``), bit
+        for bit what the quantiser stored (up to the sign of a zero: "zero's sign" in include/dfq_hip.h), and / or to the
+        integer codes in a block of the plan (``codes``: None, 'int32' or 'int8', as in ``quant_plan``).  One launch.
+        ValueError for ``weights=False`` without ``codes``, 'int8' with a width above 8, keys or shapes that are not this
+        batch's."""
+        self._ready('unpack_plan')
+        return BatchUnpackPlan(self, packed, weights, codes)
+
+    def save_packed(self, path, source):
+        """pack_plan + run + synchronise, then ONE ``.npz`` (numpy only, nothing pickled): per network the packed words
+        trimmed to its size (``words_<n>``, uint32), ``offsets`` int64 [n_nets, T + 1], ``widths`` int32 [n_nets, T],
+        ``ranges`` float32 [n_nets, R] (the (min, max) pairs the quantiser used, in the order of ``keys``: one pair per
+        tensor, or per row with ``per_channel``), ``keys``, ``shapes`` int64 [T, 8] (padded with zeros), ``per_channel``,
+        ``signed``, ``version``, and the biases as float32 (``bias_keys``, ``biases`` [n_nets, B] concatenated in that
+        order).  ``source`` must have run.  RuntimeError if a network did not pack (status != 0).  Returns the closed pack
+        plan, whose blocks stay readable."""
+        plan = self.pack_plan(source)
+        try:
+            plan.run()
+            _ffi.synchronize()
+        finally:
+            plan.close()
+        status = plan.status_block.cpu().tolist()
+        if any(status):
+            raise RuntimeError('save_packed: network {} did not pack (status {})'.format(
+                next(n for n, s in enumerate(status) if s), next(s for s in status if s)))
+        offsets = plan.offset_block.cpu().numpy()
+        words = plan.packed_block.cpu().numpy().view(np.uint32)
+        out = {'version': np.int64(_PACKED_VERSION), 'keys': np.array(plan.keys, dtype=np.str_), 'offsets': offsets,
+               'widths': plan.widths_array(), 'per_channel': np.bool_(plan.per_channel), 'signed': np.bool_(plan.signed)}
+        shapes = np.zeros((len(plan.keys), 8), dtype=np.int64)
+        for i, (_, _, shape) in enumerate(plan._views):
+            shapes[i, :len(shape)] = shape
+        out['shapes'] = shapes
+        rng = plan.range_block.cpu().numpy()
+        out['ranges'] = np.concatenate([rng[:, off:off + _range_floats(shape)] for (_, off, shape) in plan._range_views], axis=1)
+        for n in range(plan.n_nets):
+            out['words_{}'.format(n)] = words[n, :int(offsets[n, -1])].copy()
+        bias_keys = [k for k in plan.keys if self.nets[0][0][k].bias is not None]
+        out['bias_keys'] = np.array(bias_keys, dtype=np.str_)
+        out['biases'] = np.stack([np.concatenate([g[k].bias.detach().cpu().numpy().reshape(-1).astype(np.float32) for k in bias_keys]
+                                                 or [np.zeros(0, dtype=np.float32)]) for (g, _, _) in self.nets])
+        with open(path, 'wb') as f:
+            np.savez(f, **out)
+        return plan
+
+    def load_packed(self, path):
+        """Read a file ``save_packed`` wrote into THIS batch: keys, shapes and the number of networks are checked against the
+        batch, the words, offsets, widths and ranges uploaded, the biases copied into the networks, and one unpack launch
+        rebuilds every weight in place.  Returns the PackedBatch that holds the blocks (``unpack_plan(it, ...)`` unpacks them
+        again, to codes for instance).  ValueError for a file of another architecture or batch size, an unknown ``version``,
+        and a file whose offsets do not fit its widths (unpack's status)."""
+        self._ready('load_packed')
+        packed = PackedBatch(self, path)
+        plan = BatchUnpackPlan(self, packed, True, None)
+        try:
+            plan.run()
+            _ffi.synchronize()
+        finally:
+            plan.close()
+        status = plan.status_block.cpu().tolist()
+        if any(status):
+            raise ValueError('load_packed: the offsets of network {} do not fit its widths (status {})'.format(
+                next(n for n, s in enumerate(status) if s), next(s for s in status if s)))
+        with torch.no_grad():
+            for n, (graph, _, _) in enumerate(self.nets):
+                at = 0
+                for k in packed._bias_keys:
+                    b = graph[k].bias
+                    b.copy_(torch.from_numpy(packed._biases[n, at:at + b.numel()].copy()).view(b.shape))
+                    at += b.numel()
+        return packed
+
     def absorb_plan(self, N=3, range_clip=None, absorb=True):
         """One plan (BatchAbsorbPlan) for ``bias_absorption(graph, relations, bottoms, N)`` followed, if ``range_clip`` is
         given, by ``clip_weight(graph, range_clip, targ_type)`` on every network of the batch, bit for bit.  ``absorb=False``
@@ -829,7 +920,7 @@ class BatchQuantPlan(_BatchPlan):
         if codes == 'int8' and bit_weight > 8:
             raise ValueError('quant_plan: 1-byte codes need bit_weight <= 8, got {}'.format(bit_weight))
         super().__init__(batch)
-        self.per_channel, self.signed = bool(per_channel), bool(signed)
+        self.per_channel, self.signed, self.bit_weight = bool(per_channel), bool(signed), bit_weight
         n_nets = len(batch.nets)
         dev = batch.stage.device
         g0 = batch.nets[0][0]
@@ -896,7 +987,7 @@ class BatchSquantPlan(_BatchPlan):
         if codes == 'int8' and bit_weight > 8:
             raise ValueError('squant_plan: 1-byte codes need bit_weight <= 8, got {}'.format(bit_weight))
         super().__init__(batch)
-        self.per_channel, self.signed = bool(per_channel), bool(signed)
+        self.per_channel, self.signed, self.bit_weight = bool(per_channel), bool(signed), bit_weight
         n_nets = len(batch.nets)
         dev = batch.stage.device
         g0 = batch.nets[0][0]
@@ -1008,6 +1099,221 @@ class BatchMixedPlan(_BatchPlan):
     def codes(self, n):
         """{graph key: integer codes of network n's weight, shaped like it} -- views of the code block; {} without codes"""
         return self._lay.codes(n)
+
+
+_PACKED_VERSION = 1            # of the file save_packed writes
+_PACK_MAX_BITS = 16
+
+
+def _range_floats(shape):
+    """floats of a range view: a pair per row ([O, 2]) or one pair ([2])"""
+    return 2 * (shape[0] if len(shape) == 2 else 1)
+
+
+def _extent_words(numel, bits):
+    """words of one tensor's stream: ceil(numel * bits / 32) rounded up to 4 (include/dfq_hip.h)"""
+    words = -(-numel * bits // 32)
+    return -(-words // 4) * 4
+
+
+class _Packed:
+    """What a BatchPackPlan and a loaded PackedBatch share -- the packed words of a batch and what unpacking them needs:
+    ``packed_block`` int32 [n_nets, word_stride] (the raw uint32 words), ``offset_block`` int64 [n_nets, T + 1],
+    ``status_block`` int32 [n_nets], ``range_block`` float32 [n_nets, range_stride], the widths -- one for all (``bits``), or
+    ``bits_block`` int32 [n_nets, T] on the device (``bits == 0``) --, ``keys``, ``per_channel`` and ``signed``."""
+
+    def words(self, n):
+        """``OrderedDict[graph key -> int32 view]`` of network n's packed words, tensor by tensor (one device-to-host copy of
+        its offsets); reinterpret as uint32 on the host (``.cpu().numpy().view(numpy.uint32)``)"""
+        off = self.offset_block[n].cpu().tolist()
+        row = self.packed_block[n]
+        return OrderedDict((key, row[off[i]:off[i + 1]]) for i, key in enumerate(self.keys))
+
+    def size_bits(self, n):
+        """bits network n's packed words take: 32 * offset[n][T]"""
+        return 32 * int(self.offset_block[n, -1].cpu())
+
+    def status(self, n):
+        """0: packed; 1: ``word_stride`` is too small (``size_bits(n)`` says what it takes); 2: a width on the device is no
+        width"""
+        return int(self.status_block[n].cpu())
+
+    def widths_array(self):
+        """int32 numpy [n_nets, T]: the width of every tensor of every network"""
+        if self.bits:
+            return np.full((self.n_nets, len(self.keys)), self.bits, dtype=np.int32)
+        return self.bits_block.cpu().numpy().astype(np.int32)
+
+
+class BatchPackPlan(_BatchPlan, _Packed):
+    """Dense bit-packing of the codes a quant, squant or mixed plan of a NetworkBatch wrote (dfq_batch_pack_plan,
+    include/dfq_hip.h, which holds the definition).  ``run()`` enqueues two launches on the current stream -- the offsets, one
+    workgroup per network, then the packing -- and nothing goes to the host.  The plan owns ``packed_block``,
+    ``offset_block`` and ``status_block`` (torch tensors that outlive ``close()``); the codes, the ranges and, for a mixed
+    source, the widths stay the source's blocks."""
+    _c = 'dfq_batch_pack_plan'
+
+    def __init__(self, batch, source, word_stride):
+        if not isinstance(source, (BatchQuantPlan, BatchSquantPlan, BatchMixedPlan)):
+            raise ValueError('pack_plan: the source must be a quant_plan, squant_plan or mixed_plan, got {!r}'.format(type(source).__name__))
+        if source._batch is not batch:
+            raise ValueError('pack_plan: the source is a plan of another batch')
+        if not source._plan:
+            raise ValueError('pack_plan: the source plan has been closed')
+        if source.code_block is None:
+            raise ValueError('pack_plan: the source was created without codes')
+        mixed = isinstance(source, BatchMixedPlan)
+        if mixed and not source.apply:
+            raise ValueError('pack_plan: a mixed plan created with apply=False writes no codes')
+        views = source._lay._code_views if mixed else source._code_views
+        range_views = source._lay._range_views if mixed else source._range_views
+        if word_stride is not None and (isinstance(word_stride, bool) or not isinstance(word_stride, (int, np.integer)) or word_stride < 0):
+            raise ValueError('pack_plan: word_stride must be an int >= 0, got {!r}'.format(word_stride))
+        super().__init__(batch)
+        self._source = source                                           # (its blocks are read by every run)
+        self.keys = [key for (key, _, _, _) in views]
+        self._views = [(key, numel, shape) for (key, _, numel, shape) in views]
+        wanted = set(self.keys)
+        self._range_views = [v for v in range_views if v[0] in wanted]  # (a quant plan's bias ranges are not the weights')
+        self.per_channel, self.signed = source.per_channel, source.signed
+        self.range_block, self.code_block, self.code_dtype = source.range_block, source.code_block, source.code_dtype
+        self.n_nets, self.n_tensors = len(batch.nets), len(views)
+        self.bits = 0 if mixed else int(source.bit_weight)
+        self.bits_block = source.bits_block if mixed else None
+        if not mixed and not 1 <= self.bits <= _PACK_MAX_BITS:
+            raise ValueError('pack_plan: codes of {} bits; the packing takes 1 to {}'.format(self.bits, _PACK_MAX_BITS))
+        if word_stride is None:
+            if mixed:
+                word_stride = -(-(-(-source.budget // 32) + 5 * self.n_tensors) // 4) * 4     # (every row on a 16-byte boundary)
+            else:
+                word_stride = sum(_extent_words(numel, self.bits) for (_, numel, _) in self._views)
+        self.word_stride = int(word_stride)
+        dev = batch.stage.device
+        self.packed_block = torch.empty((self.n_nets, self.word_stride), dtype=torch.int32, device=dev)
+        self.offset_block = torch.zeros((self.n_nets, self.n_tensors + 1), dtype=torch.int64, device=dev)
+        self.status_block = torch.zeros((self.n_nets,), dtype=torch.int32, device=dev)
+        P = _ffi.DfqBatchPackTensor
+        arr = (P * self.n_tensors)(*[P(off, numel, self.bits, i, int(self.signed), 0) for i, (_, off, numel, _) in enumerate(views)])
+        self._create((arr, self.n_tensors), self.code_block.data_ptr(), self.code_block.element_size(), self.code_block.shape[1],
+                     None if self.bits_block is None else self.bits_block.data_ptr(), self.n_tensors,
+                     self.packed_block.data_ptr(), self.word_stride, self.offset_block.data_ptr(), self.status_block.data_ptr())
+
+
+class PackedBatch(_Packed):
+    """The blocks of a file ``NetworkBatch.save_packed`` wrote, uploaded for ``batch``: what ``NetworkBatch.load_packed``
+    returns and ``NetworkBatch.unpack_plan`` takes.  ValueError for an unknown version and for keys, shapes or a number of
+    networks that are not the batch's."""
+
+    def __init__(self, batch, path):
+        with np.load(path, allow_pickle=False) as f:
+            if 'version' not in f.files or int(f['version']) != _PACKED_VERSION:
+                raise ValueError('load_packed: {} has format version {}, this library reads version {}'.format(
+                    path, int(f['version']) if 'version' in f.files else None, _PACKED_VERSION))
+            need = ['keys', 'shapes', 'offsets', 'widths', 'ranges', 'per_channel', 'signed', 'bias_keys', 'biases']
+            need += ['words_{}'.format(n) for n in range(len(batch.nets))]
+            missing = [k for k in need if k not in f.files]
+            if missing:
+                raise ValueError('load_packed: {} is no file of save_packed (it has no {!r})'.format(path, missing[0]))
+            data = {k: f[k] for k in f.files}
+        g0, tt = batch.nets[0][0], tuple(batch.targ_type)
+        mine = [(k, tuple(int(d) for d in m.weight.shape)) for k, m in g0.items() if type(m) in tt]
+        keys = [str(k) for k in data['keys']]
+        shapes = [tuple(int(d) for d in row if d) for row in data['shapes']]
+        if keys != [k for k, _ in mine] or shapes != [s for _, s in mine]:
+            raise ValueError('load_packed: {} holds another architecture (its keys or shapes are not this batch\'s)'.format(path))
+        offsets, widths = data['offsets'].astype(np.int64), data['widths'].astype(np.int32)
+        n_nets, T = len(batch.nets), len(keys)
+        if offsets.shape != (n_nets, T + 1) or widths.shape != (n_nets, T):
+            raise ValueError('load_packed: {} holds {} networks of {} tensors, the batch has {} of {}'.format(
+                path, offsets.shape[0], offsets.shape[1] - 1, n_nets, T))
+        self.keys, self.n_nets, self.n_tensors = keys, n_nets, T
+        self._views = [(k, int(np.prod(s)), s) for k, s in zip(keys, shapes)]
+        self.per_channel, self.signed = bool(data['per_channel']), bool(data['signed'])
+        self._range_views, at = [], 0
+        for k, s in zip(keys, shapes):
+            shape = (s[0], 2) if self.per_channel else (2,)
+            self._range_views.append((k, at, shape))
+            at += _range_floats(shape)
+        ranges = np.ascontiguousarray(data['ranges'], dtype=np.float32)
+        if ranges.shape != (n_nets, at):
+            raise ValueError('load_packed: {} holds {} range values per network, the batch needs {}'.format(path, ranges.shape[-1], at))
+        words = [np.ascontiguousarray(data['words_{}'.format(n)]).view(np.uint32) for n in range(n_nets)]
+        if any(len(w) != int(offsets[n, -1]) for n, w in enumerate(words)):
+            raise ValueError('load_packed: {}: a network\'s words are not as many as its offsets say'.format(path))
+        self.word_stride = max(4, max(len(w) for w in words))
+        host = np.zeros((n_nets, self.word_stride), dtype=np.uint32)
+        for n, w in enumerate(words):
+            host[n, :len(w)] = w
+        dev = batch.stage.device
+        self.packed_block = torch.from_numpy(host.view(np.int32)).to(dev)
+        self.offset_block = torch.from_numpy(offsets).to(dev)
+        self.status_block = torch.zeros((n_nets,), dtype=torch.int32, device=dev)
+        self.range_block = torch.from_numpy(ranges).to(dev)
+        self.bits, self.bits_block = 0, torch.from_numpy(widths).to(dev)
+        self._bias_keys = [str(k) for k in data['bias_keys']]
+        self._biases = np.ascontiguousarray(data['biases'], dtype=np.float32)
+        want = [k for k in keys if g0[k].bias is not None]
+        if self._bias_keys != want or self._biases.shape != (n_nets, sum(g0[k].bias.numel() for k in want)):
+            raise ValueError('load_packed: {}: its biases are not this batch\'s'.format(path))
+
+
+class BatchUnpackPlan(_BatchPlan):
+    """The way back from packed words (dfq_batch_unpack_plan, include/dfq_hip.h): one launch that rebuilds, for every network
+    of a NetworkBatch, the weights in place (``weights``) and / or the integer codes (``codes``: 'int32' or 'int8') in
+    ``code_block``, a block the plan owns (``codes(n)``).  ``status_block`` int32 [n_nets]: 0, or why a network was skipped."""
+    _c = 'dfq_batch_unpack_plan'
+
+    def __init__(self, batch, packed, weights, codes):
+        if not isinstance(packed, _Packed):
+            raise ValueError('unpack_plan: packed must be a pack_plan or a loaded PackedBatch, got {!r}'.format(type(packed).__name__))
+        if codes not in (None, 'int32', 'int8'):
+            raise ValueError("unpack_plan: codes must be None, 'int32' or 'int8', got {!r}".format(codes))
+        if not weights and codes is None:
+            raise ValueError('unpack_plan: nothing to unpack to (weights=False and codes=None)')
+        if codes == 'int8' and packed.bits > 8:
+            raise ValueError('unpack_plan: 1-byte codes need widths <= 8, got {}'.format(packed.bits))
+        g0, tt = batch.nets[0][0], tuple(batch.targ_type)
+        mine = [(k, tuple(m.weight.shape)) for k, m in g0.items() if type(m) in tt]
+        if [(k, tuple(s)) for (k, _, s) in packed._views] != mine:
+            raise ValueError('unpack_plan: the packed keys or shapes are not this batch\'s')
+        if packed.packed_block.shape[0] != len(batch.nets):
+            raise ValueError('unpack_plan: packed holds {} networks, the batch has {}'.format(packed.packed_block.shape[0], len(batch.nets)))
+        super().__init__(batch)
+        self._packed = packed
+        self.keys, self.n_nets, self.n_tensors = list(packed.keys), len(batch.nets), len(packed.keys)
+        self.per_channel, self.signed = packed.per_channel, packed.signed
+        dev = batch.stage.device
+        rng = {key: off for (key, off, _) in packed._range_views}
+        entries, self._code_views, code_stride = [], [], 0
+        P = _ffi.DfqBatchUnpackTensor
+        for i, (key, numel, shape) in enumerate(packed._views):
+            w = g0[key].weight
+            rows = int(shape[0])
+            entries.append(P(batch._in_slot(key, 'weight', w) if weights else None, rows, numel // rows, code_stride, numel, rng[key],
+                             packed.bits, i, int(self.signed), int(self.per_channel)))
+            self._code_views.append((key, code_stride, numel, tuple(shape)))
+            code_stride += -(-numel // 64) * 64
+        dtype = {None: None, 'int32': torch.int32, 'int8': torch.int8 if self.signed else torch.uint8}[codes]
+        self.code_dtype = dtype
+        self.code_block = torch.empty((self.n_nets, code_stride), dtype=dtype, device=dev) if codes is not None else None
+        self.status_block = torch.zeros((self.n_nets,), dtype=torch.int32, device=dev)
+        arr = (P * len(entries))(*entries)
+        self._create((arr, len(entries)), packed.packed_block.data_ptr(), packed.packed_block.shape[1], packed.offset_block.data_ptr(),
+                     None if packed.bits_block is None else packed.bits_block.data_ptr(), self.n_tensors,
+                     packed.range_block.data_ptr(), packed.range_block.shape[1],
+                     None if self.code_block is None else self.code_block.data_ptr(), 1 if codes == 'int8' else 4, code_stride,
+                     self.status_block.data_ptr())
+
+    def codes(self, n):
+        """{graph key: integer codes of network n's weight, shaped like it} -- views of the code block; {} without codes"""
+        if self.code_block is None:
+            return {}
+        row = self.code_block[n]
+        return OrderedDict((key, row[off:off + numel].view(shape)) for (key, off, numel, shape) in self._code_views)
+
+    def status(self, n):
+        """0, or 1 / 2: network n was skipped (its offsets do not fit its widths / a width on the device is no width)"""
+        return int(self.status_block[n].cpu())
 
 
 def _kernel_len(w):

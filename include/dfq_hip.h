@@ -795,6 +795,99 @@ void dfq_batch_mixed_plan_destroy(dfq_batch_mixed_plan* plan);
 /* kernel launches per run (2 to 4), fixed at creation; the clear of the range words of the long tensors is a memset */
 int32_t dfq_batch_mixed_plan_launches(const dfq_batch_mixed_plan* plan);
 
+/* Dense bit-packing of the integer codes of a whole batch, every tensor of every network at its own width, and the way back
+ * (extension; the artefact of a mixed-precision calibration: dfq_batch_quant_plan, dfq_batch_squant_plan and
+ * dfq_batch_mixed_plan leave one byte or four per weight, this leaves b / 8).  The tables describe ONE network; every block is
+ * [n_nets, stride] and owned by the caller.
+ * DEFINITION.
+ *   unsigned code  A tensor has a width b in [1, 16] and a `symmetric` flag: qmin = -2^(b-1) if symmetric, else 0.  The unsigned
+ *               code of a stored code q is u = (q - qmin) & (2^b - 1).  For the codes the quantisers above write the mask
+ *               changes nothing; for a caller's out-of-range codes the mask IS the behaviour, not an error.
+ *   stream      Tensor t of network n has n_t elements in the order of its weight (row-major [rows, row_len]) and the width
+ *               b = b[n][t].  Its stream is n_t * b bits; element i occupies bits [i b, (i + 1) b), least significant bit first;
+ *               uint32 word w holds bits [32 w, 32 w + 32), bit k of the stream at bit k mod 32 of word k div 32.  The stream
+ *               takes extent(n, t) = ceil(n_t b / 32) words rounded up to a multiple of 4 (16 bytes); every bit beyond n_t b up
+ *               to the end of the extent is written as ZERO, so the packed words of a network are a pure function of its codes
+ *               and widths.
+ *   offsets     int64 [n_nets, T + 1]: offset[n][0] = 0, offset[n][t + 1] = offset[n][t] + extent(n, t), computed on the device
+ *               by one workgroup per network (the widths are on the device; nothing goes to the host).  offset[n][T] is the
+ *               network's size in words, and 0 <= 32 offset[n][T] - sum_t n_t b[n][t] < 159 T (at most 31 bits to the word and
+ *               three words to the extent, per tensor): a network dfq_batch_mixed_plan allocated in `used` bits packs into
+ *               less than used + 159 T bits, so ceil(budget / 32) + 5 T words hold it whenever used <= budget.
+ *   widths      per tensor either `num_bits` in [1, 16], or num_bits = 0 and the width is read on the device from an int32 block
+ *               [n_nets, width_stride] at width_index -- what dfq_batch_mixed_plan writes as `bits`, and how
+ *               dfq_bc_plan_run_widths reads it.  A width read from the device outside [1, 16], or above 8 with one-byte codes,
+ *               gives status[n] = 2 and network n is skipped: nothing of its packed row and nothing of its offsets is written.
+ *   capacity    the packed block is uint32 [n_nets, word_stride].  offset[n][T] > word_stride gives status[n] = 1: nothing of
+ *               network n's packed row is written, its offsets ARE (the caller learns the size it needs).  status[n] = 0
+ *               otherwise.  The other networks are not affected, and words at and beyond offset[n][T] are never written.
+ *   unpack      from the words, the offsets, the widths and the range block a quantiser wrote ((min, max) float32, a pair per
+ *               tensor, or per row with per_row), either or both of
+ *                 (a) the codes q = u + qmin into a code block, int32 or one byte (uint8 / int8, the low byte of q, widths <= 8);
+ *                 (b) the weights, in place in the batch: y = (float)q * p.scale + p.min_value with
+ *                     p = qparams_double((double)min, (double)max, b, symmetric) of csrc/dfq_common.hpp -- two separately rounded
+ *                     float32 operations, exactly the last two of the quantisers' fake_quant_one.
+ *               It rounds nothing else and reads no weight.  Unpack does not recompute offsets: it reads those pack (or a
+ *               loader) left, and skips network n -- status 2 for a bad device width, else status 1 -- if offset[n][0] != 0, if
+ *               a tensor's extent as the offsets give it is not extent(n, t), or if offset[n][T] > word_stride.
+ *   zero's sign  a quantiser can store -0.0 where the integer code gives +0.0 (a unit whose min is -0.0 and an element whose q
+ *               came out as -0.0).  The definition above, from the integer code, is what unpack computes: against the
+ *               quantiser's stored weights it is equal in value everywhere, and bit for bit wherever no weight of the unit is a
+ *               zero.  Tensors holding NaN are outside the contract (their code is whatever the quantiser left).
+ * Launches: pack 2 (offsets, one workgroup per network; then pack), unpack 1.  No workgroup waits for another, no atomic
+ * touches a packed word (every word is composed by one lane from the at most ceil(32 / b) + 1 codes that reach into it), the
+ * packed block need not be cleared, nothing synchronises with the host outside create.  A tensor is cut into chunks of
+ * dfq_batch_pack_chunk_elements() elements, a multiple of 32: every chunk starts on a word boundary at every width, so the
+ * grid depends on the element counts alone; a workgroup takes a few consecutive chunks of one tensor, tail and padding included.
+ * create (both): DFQ_ERR_ARG (and dfq_last_error) for null or empty tables, code_bytes other than 1 or 4, a num_bits outside
+ * {0} and [1, 16] or above 8 with one-byte codes, num_bits = 0 with a null width block, a width_index outside width_stride,
+ * offsets outside their strides, numel <= 0, null bases or networks that are not 16-byte aligned to network 0.  pack: a null
+ * code, packed, offsets or status block.  unpack: a null words, offsets or status block; neither codes nor any weight to
+ * write; a tensor with a weight and no range block or a range_offset < 0, a weight that is not 16-byte aligned, rows * row_len
+ * != numel, row_len above 2^31 - 1; with a null code block code_bytes and the code offsets are ignored.  Synchronises (create
+ * only); run is asynchronous on `stream`. */
+typedef struct dfq_batch_pack_plan dfq_batch_pack_plan;
+typedef struct dfq_batch_pack_tensor {
+    int64_t code_offset;    /* elements into a network's code row                                                    */
+    int64_t numel;          /* n_t                                                                                   */
+    int32_t num_bits;       /* 1..16, or 0: read the width block                                                     */
+    int32_t width_index;    /* into a network's row of the width block (num_bits == 0)                               */
+    int32_t symmetric;
+    int32_t pad;
+} dfq_batch_pack_tensor;
+/* `bases` are taken and checked as by the other batch plans; pack itself reads nothing through them */
+int dfq_batch_pack_plan_create(const dfq_batch_pack_tensor* tensors, int32_t n_tensors, const void* const* bases, int32_t n_nets,
+                               const void* codes, int32_t code_bytes, int64_t code_stride, const int32_t* widths, int64_t width_stride,
+                               uint32_t* packed, int64_t word_stride, int64_t* offsets, int32_t* status, dfq_batch_pack_plan** out_plan);
+int dfq_batch_pack_plan_run(dfq_batch_pack_plan* plan, void* stream);
+void dfq_batch_pack_plan_destroy(dfq_batch_pack_plan* plan);
+/* kernel launches per run (2) */
+int32_t dfq_batch_pack_plan_launches(const dfq_batch_pack_plan* plan);
+/* elements of a tensor one workgroup takes (a multiple of 32) */
+int64_t dfq_batch_pack_chunk_elements(void);
+
+typedef struct dfq_batch_unpack_plan dfq_batch_unpack_plan;
+typedef struct dfq_batch_unpack_tensor {
+    float* data;            /* the weight in network 0, [rows, row_len], written in place; NULL: codes only          */
+    int64_t rows;
+    int64_t row_len;
+    int64_t code_offset;    /* elements into a network's code row (ignored with a null code block)                   */
+    int64_t numel;
+    int64_t range_offset;   /* floats into a network's range block: (min, max), per row with per_row                 */
+    int32_t num_bits;
+    int32_t width_index;
+    int32_t symmetric;
+    int32_t per_row;
+} dfq_batch_unpack_tensor;
+int dfq_batch_unpack_plan_create(const dfq_batch_unpack_tensor* tensors, int32_t n_tensors, const void* const* bases, int32_t n_nets,
+                                 const uint32_t* words, int64_t word_stride, const int64_t* offsets, const int32_t* widths,
+                                 int64_t width_stride, const float* ranges, int64_t range_stride, void* codes, int32_t code_bytes,
+                                 int64_t code_stride, int32_t* status, dfq_batch_unpack_plan** out_plan);
+int dfq_batch_unpack_plan_run(dfq_batch_unpack_plan* plan, void* stream);
+void dfq_batch_unpack_plan_destroy(dfq_batch_unpack_plan* plan);
+/* kernel launches per run (1) */
+int32_t dfq_batch_unpack_plan_launches(const dfq_batch_unpack_plan* plan);
+
 /* Analytic activation ranges of a whole batch of networks of one architecture (extension; set_quant_minmax,
  * utils/layer_transform.py:347-609, main_cls.py:188, for every network of a batch at once).  The caller walks the graph of
  * the FIRST network once (find_prev_bn, :299-344, and the branch grouping of :476-580) and hands over what the walk found
