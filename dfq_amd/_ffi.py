@@ -192,6 +192,7 @@ SIGNATURES = {
     'dfq_le_plan_defer_depth': (c_int32, [c_void_p]),
     'dfq_le_plan_lazy': (c_int32, [c_void_p]),
     'dfq_le_plan_lazy_stats': (c_int32, [c_void_p, c_void_p, c_void_p]),
+    'dfq_le_plan_set_ctl_stage': (c_int32, [c_void_p, c_int32]),
     'dfq_le_plan_free_running_elements': (c_int64, [c_void_p]),
     'dfq_le_plan_free_running_group': (c_int32, [c_void_p]),
     'dfq_le_plan_lean_background': (c_int32, [c_void_p]),

@@ -62,11 +62,13 @@
 // x converge_thres (default 1.5) or the count bound needs the exact verdict.  Its tiles, taking the stored value through the
 // remembered factors one rounding at a time, meet every term |fl(t h_j) - t| of the window's earlier sweeps on the way and leave
 // them, per wave and sweep, in the window arrays; the convergence launch then replays the reference's (diff, count) steps of those
-// sweeps in order with their full sums.  A lazy sweep whose bound does not prove "go on" is decided by le_resolve_kernel, launched
-// behind every convergence launch: one workgroup per such network recomputes the same partials from the stored elements
-// (replay_oneway), decides exactly, and the network reads in every later sweep of the run.  Where an enqueue call ends the same
-// kernel resolves the networks' lazy sweeps before le_flush_kernel stores.  4 (D + 1) / D -> 8 / D bytes per deferred element and
-// sweep, every value and the loop state bit-identical.
+// sweeps in order with their full sums.  A lazy sweep whose bound does not prove "go on" is decided inside the same convergence
+// launch: the network's workgroup goes on, recomputes the same partials from the stored elements (replay_oneway, through
+// resolve_network), decides exactly, and the network reads in every later sweep of the run.  Nothing is launched behind the
+// convergence launch: a sweep is the level launch and the convergence launch (plus the lean launch at the start of a group).
+// Where an enqueue call ends le_resolve_kernel -- the same resolve_network, one workgroup per network, all but those with
+// unresolved sweeps leave at once -- resolves the networks' lazy sweeps before le_flush_kernel stores.  4 (D + 1) / D -> 8 / D
+// bytes per deferred element and sweep, every value and the loop state bit-identical.
 //
 // Convergence (dfq.py:105-115): every element is written exactly once per sweep, by a pass that has
 // its pre-sweep value in a register, so each tile leaves float64 partials of sum|W - W_prev|; they are
@@ -107,6 +109,12 @@ constexpr int kBootAblate = DFQ_BOOT_ABLATE;   // tuning builds: 1 no row pass, 
 constexpr int kBootWork = 16384;       // elements per pass a bootstrap workgroup streams at most (larger blocks are split)
 constexpr int kCtlBlock = 1024;        // threads of the control kernel
 constexpr int kCtlStage = 6144;        // partials staged in LDS by the control kernel
+// the control kernel is compiled for two of its 16-wave workgroups per CU (eight waves per SIMD: 64 vector registers)
+#ifdef DFQ_EMU
+#define DFQ_CTL_OCCUPANCY
+#else
+#define DFQ_CTL_OCCUPANCY __attribute__((amdgpu_waves_per_eu(8, 8)))
+#endif
 
 
 // One relation.  The descriptors of a launch are passed BY VALUE (kernarg segment) and selected with
@@ -1617,62 +1625,64 @@ __global__ __launch_bounds__(kBlock) void le_bootstrap_kernel(const LeRelDev* __
 // row_tile / col_tile give their thread, in the same slots, adds the same terms in the same order (window_step, slot_abs_diff)
 // and its wave leaves the same butterfly sum in the same slot of window array j.  (Waves never straddle two tiles: kCtlBlock is
 // a multiple of kBlock.)  Used where a verdict is uncertain (le_control_kernel) and where a call ends (le_resolve_kernel).
+// It runs for a handful of network-sweeps per run, so its speed does not matter; its registers do, for it is part of the
+// convergence launch: the slot is the outer loop (one 16-byte vector per thread in flight), the window sweeps the inner one
+// (one running sum each, kHoldMax at most).  Per window array that is the tile's order -- slot u ascending, then wave_sum.
 struct LeOneway {
     int32_t rel;        // index in the level-sorted descriptor table
     int32_t side;       // 0: W1 (row tiles), 1: W2 (column tiles)
 };
+// a value every lane of the wave holds alike, moved to a scalar register (the compiler cannot see that it is uniform)
+__device__ __forceinline__ int wave_uniform(int x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_readfirstlane(x);
+#else
+    return x;
+#endif
+}
 __device__ __forceinline__ void replay_oneway(const LeRelDev* __restrict__ rels, const LeOneway* __restrict__ ow, int n_ow, int last,
                               double* __restrict__ win, int64_t part_stride) {
     constexpr int NV = kSlotsVec4;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" : "+v"(win), "+v"(ow));
-#endif
+    const int wave0 = wave_uniform((int)threadIdx.x / kWave) * kWave;       // first thread of this wave
+    const int tid = (int)threadIdx.x % kBlock;                               // the tile thread this thread stands for
     for (int e = 0; e < n_ow; ++e) {
-        // (the descriptor through a vector address: its fields in vector registers -- next to the convergence launch's own
-        // values they would not fit the scalar file)
-        int rel = ow[e].rel, side = ow[e].side;
-#if defined(__HIP_DEVICE_COMPILE__)
-        asm volatile("" : "+v"(rel), "+v"(side));
-#endif
+        // the descriptor, and below the geometry of the tile, are the same for the whole wave: scalar registers
+        const int rel = wave_uniform(ow[e].rel), side = wave_uniform(ow[e].side);
         const LeRelDev& R = rels[rel];
         const bool col = side != 0;
         const int n_tiles = col ? R.n_col_tiles : R.n_row_tiles;
         const int vec = col ? R.ct_vec : R.rt_vec;
-        for (int it = (int)threadIdx.x; it < n_tiles * kBlock; it += kCtlBlock) {
-            const int tile = it / kBlock, tid = it % kBlock;
-            const int slot = (R.partial_base + (col ? R.n_row_tiles : 0) + tile) * (kBlock / kWave) + tid / kWave;
-            // geometry of the thread (row_tile / col_tile)
-            int n_max, row0, pos, rstep, rstride, first, n_own = 0, lane_on = 1, nr;
-            int ci[4] = {0, 0, 0, 0};
-            int go = 1, gi = 0, i0 = 0;
-            const float* w;
+        const int slabs = col ? R.ct_slabs : R.rt_slabs, t_rows = col ? R.ct_rows : R.rt_rows, t_cols = col ? R.ct_cols : R.rt_cols;
+        const int rows = col ? R.o2 : R.o1;
+        const int rstride = col ? R.i2g * R.khkw : R.row_len;
+        const float* wbase = col ? R.w2 : R.w1;
+        const float* hold = col ? R.hold + R.o1 : R.hold;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(wbase), "+v"(hold), "+v"(win), "+v"(part_stride));      // (only vector instructions use them)
+#endif
+        const int slot0 = (R.partial_base + (col ? R.n_row_tiles : 0)) * (kBlock / kWave);
+        for (int it0 = wave0; it0 < n_tiles * kBlock; it0 += kCtlBlock) {
+            const int tile = it0 / kBlock;
+            const int slot = slot0 + tile * (kBlock / kWave) + (it0 % kBlock) / kWave;
+            // geometry of the tile and of the thread (row_tile / col_tile)
+            const int rblk = wave_uniform(small_div(tile, slabs));
+            const int slab = tile - rblk * slabs;
+            const int row0 = rblk * t_rows;
+            const int nr = min(t_rows, rows - row0);
+            const int p0 = slab * t_cols;
+            const int npv = min(t_cols, rstride - p0) / vec;
+            int n_max, pos, rstep, first, n_own = 0, lane_on;
             if (!col) {
-                const int rblk = small_div(tile, R.rt_slabs);
-                const int slab = tile - rblk * R.rt_slabs;
-                row0 = rblk * R.rt_rows;
-                nr = min(R.rt_rows, R.o1 - row0);
-                const int p0 = slab * R.rt_cols;
-                const int np = min(R.rt_cols, R.row_len - p0);
-                const int npv = np / vec;
-                const int JL = small_div(kBlock, npv);
+                const int JL = wave_uniform(small_div(kBlock, npv));
                 const int jl_raw = small_div(tid, npv);
                 lane_on = jl_raw < JL;
                 const int jl = lane_on ? jl_raw : 0;
                 pos = p0 + (lane_on ? (tid - jl_raw * npv) * vec : 0);
                 n_own = lane_on ? small_div(nr - jl + JL - 1, JL) : 0;
-                n_max = min(NV, small_div(nr + JL - 1, JL));
-                rstep = JL; rstride = R.row_len;
-                w = R.w1 + ((int64_t)row0 * R.row_len + pos);
+                n_max = min(NV, wave_uniform(small_div(nr + JL - 1, JL)));
+                rstep = JL;
                 first = jl;
             } else {
-                const int rblk = small_div(tile, R.ct_slabs);
-                const int slab = tile - rblk * R.ct_slabs;
-                row0 = rblk * R.ct_rows;
-                nr = min(R.ct_rows, R.o2 - row0);
-                const int row_len2 = R.i2g * R.khkw;
-                const int p0 = slab * R.ct_cols;
-                const int np = min(R.ct_cols, row_len2 - p0);
-                const int npv = np / vec;
                 int G = 1, lgG = 0;
                 while (G < npv) { G <<= 1; ++lgG; }
                 const int n_rowslots = kBlock >> lgG;
@@ -1681,58 +1691,46 @@ __device__ __forceinline__ void replay_oneway(const LeRelDev* __restrict__ rels,
                 lane_on = ln < npv;
                 pos = p0 + min(ln, npv - 1) * vec;
                 n_max = min(NV, (nr + n_rowslots - 1) >> (8 - lgG));
-                rstep = n_rowslots; rstride = row_len2;
-                w = R.w2 + ((int64_t)row0 * row_len2 + pos);
-                i0 = small_div(p0, R.khkw);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) ci[k] = (k < vec) ? small_div(pos + k, R.khkw) - i0 : 0;
-                go = R.go; gi = R.gi;
+                rstep = n_rowslots;
                 first = grp;
             }
-            float v[NV][4];
+            const float* const w = wbase + ((int64_t)row0 * rstride + pos);
+            // slot after slot (ascending, as the tile adds them), one 16-byte vector in flight, one running sum per window sweep
+            double aw[kHoldMax];
 #pragma unroll
-            for (int u = 0; u < NV; ++u) {
-                const int r = min(first + u * rstep, nr - 1);
+            for (int j = 0; j < kHoldMax; ++j) aw[j] = 0.0;
+#pragma unroll 1
+            for (int u = 0; u < n_max; ++u) {
+                const int r_raw = first + u * rstep;
+                const int r = min(r_raw, nr - 1);
+                const bool ok = col ? (lane_on && r_raw < nr) : (u < n_own);
+                // t: the stored value taken through the remembered factors of the sweeps before j, one rounding at a time --
+                // window_step's t of sweep j is its nv of sweep j - 1, the same float32 product
+                float t[4];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) v[u][k] = (u < n_max && k < vec) ? w[(int64_t)r * rstride + k] : 0.0f;
-            }
-            for (int j = 0; j <= last; ++j) {
-                double aw = 0.0;
+                for (int k = 0; k < 4; ++k) t[k] = (k < vec) ? w[(int64_t)r * rstride + k] : 0.0f;
+                const int c = col ? small_div(row0 + r, R.go) * R.gi : row0 + r;
 #pragma unroll
-                for (int u = 0; u < NV; ++u) {
-                    if (u >= n_max) continue;
-                    const int r_raw = first + u * rstep;
-                    const int r = min(r_raw, nr - 1);
-                    const bool ok = col ? (lane_on && r_raw < nr) : (u < n_own);
-                    if (!col) {
-                        const float* hold = R.hold;
-                        const int64_t c = row0 + r;
-                        auto h = [&](int i, int) { return hold[(int64_t)(2 * i) * R.o1 + c]; };
-                        if (vec == 4) {
-                            float t[4], nv[4];
-                            window_step<4>(v[u], j, h, t, nv);
-                            aw += slot_abs_diff<4>(ok, nv, t);
-                        } else {
-                            float x[1] = {v[u][0]}, t[1], nv[1];
-                            window_step<1>(x, j, h, t, nv);
-                            aw += slot_abs_diff<1>(ok, nv, t);
-                        }
+                for (int j = 0; j < kHoldMax; ++j) {
+                    if (j > last) continue;
+                    const float* const hj = hold + ((int64_t)(2 * j) * R.o1 + c);
+                    float nv[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) nv[k] = (k < vec) ? t[k] * hj[col ? small_div(pos + k, R.khkw) : 0] : 0.0f;
+                    if (vec == 4) {
+                        aw[j] += slot_abs_diff<4>(ok, nv, t);
                     } else {
-                        const int64_t cg = (int64_t)small_div(row0 + r, go) * gi + i0;
-                        const float* hold = R.hold + R.o1;
-                        auto h = [&](int i, int k) { return hold[(int64_t)(2 * i) * R.o1 + cg + ci[k]]; };
-                        if (vec == 4) {
-                            float t[4], nv[4];
-                            window_step<4>(v[u], j, h, t, nv);
-                            aw += slot_abs_diff<4>(ok, nv, t);
-                        } else {
-                            float x[1] = {v[u][0]}, t[1], nv[1];
-                            window_step<1>(x, j, h, t, nv);
-                            aw += slot_abs_diff<1>(ok, nv, t);
-                        }
+                        const float n1[1] = {nv[0]}, t1[1] = {t[0]};
+                        aw[j] += slot_abs_diff<1>(ok, n1, t1);
                     }
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) t[k] = nv[k];
                 }
-                const double tsum = wave_sum(aw);
+            }
+#pragma unroll
+            for (int j = 0; j < kHoldMax; ++j) {
+                if (j > last) continue;
+                const double tsum = wave_sum(aw[j]);
                 if (threadIdx.x % kWave == 0) win[(int64_t)j * part_stride + slot] = tsum;
             }
         }
@@ -1790,7 +1788,8 @@ __device__ __forceinline__ int le_next_lazy(const LeLazy& lz, bool latched, bool
 // the exact (diff, count) steps of `n` unresolved sweeps j0, j0 + 1, ... of one network: the deferred layers' means from the window
 // arrays, the others as the lazy sweep kept them, summed in graph order; log entries and the last diff_tmp as the eager loop
 // leaves them.  All threads of the workgroup; the results are valid in thread 0.
-__device__ __forceinline__ void resolve_window(const LeLazy& lz, const LeLayerDiff* __restrict__ layers, const LeLayerDiff* sh_layer, double* sh_m,
+template <class LZ>
+__device__ __forceinline__ void resolve_window(const LZ& lz, const LeLayerDiff* __restrict__ layers, const LeLayerDiff* sh_layer, double* sh_m,
                                const LeNetDesc& nd, int n_layers, int j0, int n, double* log, int log_cap, double& diff, int& count,
                                double& last) {
     const int tid = threadIdx.x, lane = tid % kWave, wave = tid / kWave;
@@ -1825,27 +1824,115 @@ __device__ __forceinline__ void resolve_window(const LeLazy& lz, const LeLayerDi
     }
 }
 
+// What a network's verdict is drawn from: the FIRST argument of le_control_kernel and of le_resolve_kernel, so that code both
+// share (resolve_network) can fetch a field from the kernarg segment where it uses it, cold(v).field, like the level kernel's
+// cold(a): nothing is then held in scalar registers across the replay of the deferred layers.
+struct LeVerdictArgs {
+    const LeLayerDiff* layers;
+    const LeNetDesc* nets;
+    LeState* states;
+    double converge_thres;
+    int32_t converge_count, max_sweeps;
+    int32_t uni_layers, uni_tiles;      // > 0: a batch of like networks, the descriptor is arithmetic
+    LeLazy lz;
+};
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ const LeVerdictArgs DFQ_CONSTANT_AS& cold(const LeVerdictArgs&) {
+    auto p = __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *(const LeVerdictArgs DFQ_CONSTANT_AS*)p;
+}
+#else
+__device__ __forceinline__ const LeVerdictArgs& cold(const LeVerdictArgs& v) { return v; }
+#endif
+template <class V>
+__device__ __forceinline__ LeNetDesc net_desc(const V& v, int net) {
+    LeNetDesc nd;
+    if (v.uni_layers > 0) {
+        nd.layer_begin = net * v.uni_layers; nd.n_layers = v.uni_layers;
+        nd.tile_begin = net * v.uni_tiles; nd.n_tiles = v.uni_tiles;
+    } else {
+        nd = v.nets[net];
+    }
+    return nd;
+}
+
+// The unresolved sweeps of this workgroup's network (lazy sweeps since its last reading sweep), exactly: their deferred layers'
+// |dW| partials from the stored elements and the remembered factors (replay_oneway), then their (diff, count) steps
+// (resolve_window).  All threads of the workgroup; `sh_layer` holds the network's layer table, `sh_m` one double per layer.
+// DECIDE: the last of those sweeps ended undecided (le_control_kernel) -- its go on / stop is drawn here and the network reads in
+// every later sweep of the run (`latched`); otherwise (le_resolve_kernel, where a call ends) the verdicts of those sweeps stand,
+// only their sums were missing.
+template <bool DECIDE>
+__device__ __forceinline__ void resolve_network(const LeVerdictArgs& v, const LeLayerDiff* sh_layer, double* sh_m) {
+    const int net = (int)blockIdx.x;
+    {
+        const auto& c = cold(v);
+        const int b0 = c.lz.ow_begin[net], b1 = c.lz.ow_begin[net + 1];
+        replay_oneway(c.lz.rels, c.lz.ow + b0, b1 - b0, (c.states[net].sweeps - 1) & (c.lz.defer - 1), c.lz.win, c.lz.part_stride);
+    }
+    __syncthreads();                               // (the window sums: global words of this workgroup, read back by it)
+    const auto& c = cold(v);
+    LeState* const state = c.states + net;
+    const LeNetDesc nd = net_desc(c, net);
+    const LeState before = *state;                 // (read here: held across the replay it would spill scalar registers)
+    double diff = before.diff, last = before.last_diff_tmp;
+    int count = before.count;
+    resolve_window(c.lz, c.layers + nd.layer_begin, sh_layer, sh_m, nd, nd.n_layers, before.sweeps - before.unres, before.unres, before.log,
+                   before.log_cap, diff, count, last);
+    if (threadIdx.x == 0) {
+        state->diff = diff;
+        state->count = count;
+        state->last_diff_tmp = last;
+        state->unres = 0;
+        if (DECIDE) {
+            const int max_sweeps = c.max_sweeps;
+            const bool go_on = (diff > c.converge_thres) && (count < c.converge_count) && (max_sweeps < 0 || before.sweeps < max_sweeps);
+            state->done = go_on ? 0 : 1;
+            if (go_on) state->happen = before.sweeps;
+            state->lazy = 0;
+            state->latched = 1;
+            state->n_uncertain = before.n_uncertain + 1;
+        }
+    }
+}
+
 // dfq.py:105-115 on the device.  One 16-wave workgroup per network: its per-wave partials and layer
 // table are staged into LDS with every load in flight at once, wave w then reduces layers w, w+16,
 // ... in a fixed order.  Extra workgroups (blockIdx >= n_nets) clear the stat buffers the next sweep
 // accumulates into: parity `cur` of the column stats (R2) and parity `nxt` of the in-sweep row stats
 // (leading part of the R1 arena).
-__global__ __launch_bounds__(kCtlBlock) void le_control_kernel(const LeLayerDiff* __restrict__ layers,
-                                                               const LeNetDesc* __restrict__ nets, int n_nets,
+//
+// The launch closes the sweep: nothing is launched behind it.  A lazy sweep whose bound leaves the verdict open is decided by
+// the network's own workgroup (resolve_network): it reads the network's deferred layers and the remembered factors, which
+// nobody writes between two level launches.  The other workgroups of the launch are unaffected: the helpers clear statistics
+// arenas the replay never reads, and the solver workgroups (cf_solve_block) write the factor rings of the free-running
+// relations, which are never deferred, and read nothing of the loop state but `done` -- where that is still 0 when the verdict
+// turns out "stop" their solve is unused, as it is for a network whose eager verdict is drawn late in the same launch.
+//
+// LDS is sized to the plan (dynamic): `stage_cap` staged partials (the plan's largest network, kCtlStage at most -- beyond it
+// partials are read from memory), `tab_cap` entries (the plan's most layers, 1024 at most -- beyond it likewise) of the layer
+// table and of the two mean tables.  At a batch of MobileNetV2 that is 15 KB, and two of these workgroups fit a CU: verdict,
+// clearing and solver workgroups are resident together.
+__global__ __launch_bounds__(kCtlBlock) DFQ_CTL_OCCUPANCY void le_control_kernel(LeVerdictArgs v, int n_nets,
                                                                const double* __restrict__ partials,
                                                                double* __restrict__ layer_mean,
                                                                uint32_t* __restrict__ r2_arena, int64_t r2_words,
                                                                uint32_t* __restrict__ r1_arena, int64_t r1_words,
-                                                               int64_t r1_zero_words, int parity,
-                                                               LeState* __restrict__ states, double converge_thres,
-                                                               int converge_count, int max_sweeps, int uni_layers, int uni_tiles,
-                                                               int n_clear, const LeCfSeg* __restrict__ cf_segs,
+                                                               int64_t r1_zero_words, int parity, int n_clear,
+                                                               const LeCfSeg* __restrict__ cf_segs,
                                                                const LeCfRel* __restrict__ cf_rels, const int32_t* __restrict__ cf_map,
-                                                               LeParams cf_p, int cf_k0, int cf_group, LeLazy lz) {
-    __shared__ double sh_part[kCtlStage];
-    __shared__ double sh_mean[1024];
-    __shared__ double sh_mean2[1024];              // the means of an unresolved sweep (resolve_window)
-    __shared__ LeLayerDiff sh_layer[1024];
+                                                               LeParams cf_p, int cf_k0, int cf_group, int stage_cap, int tab_cap) {
+    const LeLayerDiff* __restrict__ layers = v.layers;
+    LeState* __restrict__ const states = v.states;
+    const double converge_thres = v.converge_thres;
+    const int converge_count = v.converge_count, max_sweeps = v.max_sweeps;
+    const LeLazy& lz = v.lz;
+    DFQ_DYN_SMEM(smem);                            // ctl_smem_bytes(stage_cap, tab_cap)
+    double* const sh_part = reinterpret_cast<double*>(smem);
+    double* const sh_mean = sh_part + stage_cap;
+    double* const sh_mean2 = sh_mean + tab_cap;    // the means of an unresolved sweep (resolve_window)
+    LeLayerDiff* const sh_layer = reinterpret_cast<LeLayerDiff*>(sh_mean2 + tab_cap);
     const int tid = threadIdx.x;
     const int lane = tid % kWave;
     const int wave = tid / kWave;
@@ -1877,27 +1964,27 @@ __global__ __launch_bounds__(kCtlBlock) void le_control_kernel(const LeLayerDiff
     LeState* const state = states + blockIdx.x;
     // a batch of like networks (uni_layers > 0): the descriptor is arithmetic, and the partials, the layer table and the state are
     // requested at once instead of behind the descriptor's round trip through the memory system
-    LeNetDesc nd;
-    if (uni_layers > 0) {
-        nd.layer_begin = (int)blockIdx.x * uni_layers; nd.n_layers = uni_layers;
-        nd.tile_begin = (int)blockIdx.x * uni_tiles; nd.n_tiles = uni_tiles;
-    } else {
-        nd = nets[blockIdx.x];
-    }
+    const LeNetDesc nd = net_desc(v, (int)blockIdx.x);
     layers += nd.layer_begin;
     layer_mean += nd.layer_begin;
     const int n_layers = nd.n_layers;
     // every global read of the kernel is issued before the first wait: partials, layer table, state
     const int waves_per_tile = kBlock / kWave;
     const int64_t part0 = (int64_t)nd.tile_begin * waves_per_tile;
-    const int n_stage = min(nd.n_tiles * waves_per_tile, kCtlStage);
-    const LeState before = *state;       // requested with the partials: the verdict at the end does not wait for it again
+    const int n_stage = min(nd.n_tiles * waves_per_tile, stage_cap);
+    // (through a vector address: eighteen words that stay in use to the end of the kernel, in vector registers)
+    const LeState* state_v = state;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(state_v));
+#endif
+    const LeState before = *state_v;     // requested with the partials: the verdict at the end does not wait for it again
     for (int i = tid; i < n_stage; i += kCtlBlock) sh_part[i] = partials[part0 + i];
-    for (int i = tid; i < min(n_layers, 1024); i += kCtlBlock) sh_layer[i] = layers[i];
-    if (before.done) return;
+    for (int i = tid; i < min(n_layers, tab_cap); i += kCtlBlock) sh_layer[i] = layers[i];
+    // (what the control flow below hangs on: the same in every lane, told to the compiler -- the branches stay scalar)
+    if (wave_uniform(before.done)) return;
     __syncthreads();
     for (int l = wave; l < n_layers; l += kCtlBlock / kWave) {
-        const LeLayerDiff L = (l < 1024) ? sh_layer[l] : layers[l];
+        const LeLayerDiff L = (l < tab_cap) ? sh_layer[l] : layers[l];
         double s = 0.0;
         if (L.partial_begin >= 0) {
             // every tile left one partial per wave
@@ -1910,17 +1997,17 @@ __global__ __launch_bounds__(kCtlBlock) void le_control_kernel(const LeLayerDiff
         if (lane == 0) {
             // float(torch.mean(torch.abs(W - W_prev))): float32 mean, widened to double (dfq.py:108)
             const double m = (L.partial_begin >= 0) ? (double)(float)(s / L.n_elems) : 0.0;
-            if (l < 1024) sh_mean[l] = m; else layer_mean[l] = m;
+            if (l < tab_cap) sh_mean[l] = m; else layer_mean[l] = m;
         }
     }
     __syncthreads();
-    const int k = before.sweeps;                       // the sweep this launch closes
+    const int k = wave_uniform(before.sweeps);         // the sweep this launch closes
     const int phase = k & (lz.defer - 1);
-    const bool lazy = lz.on && before.lazy;            // (the deferred tiles of this sweep read nothing)
+    const bool lazy = lz.on && wave_uniform(before.lazy);      // (the deferred tiles of this sweep read nothing)
     if (lazy) {
         // a lazy sweep: the deferred layers' means are +0.0 above -- keep every mean for the sweep that resolves this one
         double* const keep = lz.mean_win + (int64_t)phase * lz.n_layers_all + nd.layer_begin;
-        for (int l = tid; l < n_layers; l += kCtlBlock) keep[l] = (l < 1024) ? sh_mean[l] : layer_mean[l];
+        for (int l = tid; l < n_layers; l += kCtlBlock) keep[l] = (l < tab_cap) ? sh_mean[l] : layer_mean[l];
     }
     // diff_tmp = sum of the layer means IN GRAPH ORDER (Python's left-to-right float64 sum), by wave 0 (every lane reads the same
     // word: a broadcast; adding +0.0 for missing layers is exact).  `lb`: the same sum without the deferred layers -- a lower
@@ -1929,8 +2016,8 @@ __global__ __launch_bounds__(kCtlBlock) void le_control_kernel(const LeLayerDiff
     if (wave == 0) {
         double diff_tmp = 0.0, lb = 0.0;
         for (int l = 0; l < n_layers; ++l) {
-            const double m = (l < 1024) ? sh_mean[l] : layer_mean[l];
-            const bool ow = ((l < 1024) ? sh_layer[l].oneway : layers[l].oneway) != 0;
+            const double m = (l < tab_cap) ? sh_mean[l] : layer_mean[l];
+            const bool ow = ((l < tab_cap) ? sh_layer[l].oneway : layers[l].oneway) != 0;
             diff_tmp += m;
             lb += ow ? 0.0 : m;
         }
@@ -1944,7 +2031,8 @@ __global__ __launch_bounds__(kCtlBlock) void le_control_kernel(const LeLayerDiff
         // the threshold or the loop would have ended) and `count` cannot reach converge_count even if every unresolved sweep
         // and this one counted; a max_sweeps end is decided as always
         const int unres = before.unres + 1;
-        if (max_end || (lb > converge_thres && before.count + unres < converge_count)) {
+        const bool certain = max_end || (lb > converge_thres && before.count + unres < converge_count);
+        if (wave_uniform(certain ? 1 : 0)) {
             if (tid == 0) {
                 state->sweeps = k + 1;
                 state->unres = unres;
@@ -1961,14 +2049,15 @@ __global__ __launch_bounds__(kCtlBlock) void le_control_kernel(const LeLayerDiff
             }
             return;
         }
-        // uncertain: the verdict is left to le_resolve_kernel, launched right behind this launch, which reads the network's
-        // deferred layers, decides exactly and latches the network on reading sweeps.  Nothing runs in between.
+        // uncertain: this workgroup goes on itself -- it reads the network's deferred layers, decides exactly and latches the
+        // network on reading sweeps (resolve_network; the state it starts from is read back behind the barrier)
         if (tid == 0) {
             state->sweeps = k + 1;
             state->unres = unres;
             state->n_lazy = before.n_lazy + 1;
-            state->lazy = -1;                          // undecided
         }
+        __syncthreads();
+        resolve_network<true>(v, sh_layer, sh_mean2);
         return;
     }
     // the unresolved sweeps, in order, with their full sums: (diff, count) advanced exactly as the reference advances them
@@ -1996,6 +2085,17 @@ __global__ __launch_bounds__(kCtlBlock) void le_control_kernel(const LeLayerDiff
                                            converge_thres, converge_count) : 0;
         state->lb_prev = lb;
     }
+}
+
+// dynamic LDS of le_control_kernel: the staged partials, the two mean tables, the layer table
+constexpr size_t ctl_smem_bytes(int stage_cap, int tab_cap) {
+    return sizeof(double) * ((size_t)stage_cap + 2 * (size_t)tab_cap) + sizeof(LeLayerDiff) * (size_t)tab_cap;
+}
+static_assert(ctl_smem_bytes(kCtlStage, 1024) <= 160 * 1024 - 1024, "the convergence launch's LDS at its caps fits a CU");
+// ... which a plan with a large network has to ask for beyond the default limit of a launch
+static hipError_t ctl_smem_allow(size_t bytes) {
+    if (bytes <= 48 * 1024) return hipSuccess;
+    return hipFuncSetAttribute((const void*)le_control_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
 __global__ void le_reset_kernel(LeState* states, int n_nets, double converge_thres, int converge_count, int max_sweeps,
@@ -2179,50 +2279,14 @@ __global__ __launch_bounds__(kBlock) void le_hold_reset_kernel(const LeRelDev* _
 // End of an enqueue call of a lazy plan: the sweeps of a network that are still unresolved (lazy sweeps since its last reading
 // sweep) get their deferred layers' |dW| partials from the stored elements and the remembered factors, and their exact (diff,
 // count) steps -- before le_flush_kernel brings the elements up to date.  One workgroup per network; most leave at once.
-// Launched behind every convergence launch too (`decide`): a network whose lazy sweep ended undecided (lazy == -1) gets its
-// exact verdict here -- the sweep's go on / stop, `happen`, the next sweep's mode -- and reads in every later sweep of the run.
-__global__ __launch_bounds__(kCtlBlock) void le_resolve_kernel(const LeLayerDiff* __restrict__ layers, const LeNetDesc* __restrict__ nets,
-                                                               int uni_layers, int uni_tiles, LeState* __restrict__ states, LeLazy lz,
-                                                               int decide, double converge_thres, int converge_count, int max_sweeps) {
-    __shared__ LeLayerDiff sh_layer[1024];
+// (An undecided verdict between the sweeps of a call is drawn by le_control_kernel itself, through the same resolve_network.)
+__global__ __launch_bounds__(kCtlBlock) void le_resolve_kernel(LeVerdictArgs v) {
+    __shared__ LeLayerDiff sh_layer[1024];         // (a lazy plan's networks have 1024 layers at most)
     __shared__ double sh_m[1024];
-    LeState* const state = states + blockIdx.x;
-    {
-        const LeState b = *state;
-        if (b.unres == 0 || (decide && b.lazy != -1)) return;
-    }
-    LeNetDesc nd;
-    if (uni_layers > 0) {
-        nd.layer_begin = (int)blockIdx.x * uni_layers; nd.n_layers = uni_layers;
-        nd.tile_begin = (int)blockIdx.x * uni_tiles; nd.n_tiles = uni_tiles;
-    } else {
-        nd = nets[blockIdx.x];
-    }
-    layers += nd.layer_begin;
-    for (int i = threadIdx.x; i < nd.n_layers; i += kCtlBlock) sh_layer[i] = layers[i];
-    replay_oneway(lz.rels, lz.ow + lz.ow_begin[blockIdx.x], lz.ow_begin[blockIdx.x + 1] - lz.ow_begin[blockIdx.x],
-                  (state->sweeps - 1) & (lz.defer - 1), lz.win, lz.part_stride);
-    __syncthreads();                               // (the window sums: global words of this workgroup, read back by it)
-    const LeState before = *state;                 // (read again: held across the replay it spilled scalar registers)
-    double diff = before.diff, last = before.last_diff_tmp;
-    int count = before.count;
-    resolve_window(lz, layers, sh_layer, sh_m, nd, nd.n_layers, before.sweeps - before.unres, before.unres, before.log, before.log_cap,
-                   diff, count, last);
-    if (threadIdx.x == 0) {
-        state->diff = diff;
-        state->count = count;
-        state->last_diff_tmp = last;
-        state->unres = 0;
-        if (before.lazy == -1) {
-            const bool go_on = (diff > converge_thres) && (count < converge_count) &&
-                               (max_sweeps < 0 || before.sweeps < max_sweeps);
-            state->done = go_on ? 0 : 1;
-            if (go_on) state->happen = before.sweeps;
-            state->lazy = 0;
-            state->latched = 1;
-            state->n_uncertain = before.n_uncertain + 1;
-        }
-    }
+    if (v.states[blockIdx.x].unres == 0) return;
+    const LeNetDesc nd = net_desc(v, (int)blockIdx.x);
+    for (int i = threadIdx.x; i < nd.n_layers; i += kCtlBlock) sh_layer[i] = v.layers[nd.layer_begin + i];
+    resolve_network<false>(v, sh_layer, sh_m);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2247,6 +2311,9 @@ struct dfq_le_plan {
     int n_layers = 0, n_rels = 0, n_nets = 1;
     LeNetDesc* d_nets = nullptr;
     int uni_layers = 0, uni_tiles = 0;       // > 0: every network of the plan has this many layers / tiles, laid out back to back
+    // LDS of the convergence launch, from the plan's largest network: staged partials (kCtlStage at most), entries of the layer
+    // and mean tables (1024 at most); what exceeds them is read from memory
+    int ctl_stage = 0, ctl_tab = 0;
     int32_t* d_boot_map = nullptr;         // bootstrap workgroup -> relation
     std::vector<LevelLaunch> levels;
     int64_t paired_total = 0;              // sum over relations of n1 + n2 (SURVEY 8d's Sigma_rel)
@@ -2785,6 +2852,13 @@ int dfq_le_plan_create_batch(const dfq_layer* layers, int32_t n_layers, const in
         p->uni_layers = uni ? nets[0].n_layers : 0;
         p->uni_tiles = uni ? nets[0].n_tiles : 0;
     }
+    {
+        int most_tiles = 0, most_layers = 0;
+        for (int n = 0; n < n_nets; ++n) { most_tiles = std::max(most_tiles, nets[n].n_tiles); most_layers = std::max(most_layers, nets[n].n_layers); }
+        p->ctl_stage = (int)std::min<int64_t>((int64_t)most_tiles * (kBlock / kWave), kCtlStage);
+        p->ctl_tab = std::min(most_layers, 1024);
+        if ((e = ctl_smem_allow(ctl_smem_bytes(p->ctl_stage, p->ctl_tab))) != hipSuccess) return fail_alloc(e);
+    }
     timer.tick("deferred");
     // ---- sort relations by level (stable) and lay out the launches ----
     std::vector<int> order(n_relations);
@@ -3269,6 +3343,11 @@ int64_t dfq_le_plan_deferred_elements(const dfq_le_plan* p) { return (p && !res_
 int32_t dfq_le_plan_defer_depth(const dfq_le_plan* p) { return (p && !res_on(p)) ? p->defer : 1; }
 // lazy sweeps of the deferred layers: 1 when the plan runs them (dfq_le.hip, "Lazy sweeps")
 int32_t dfq_le_plan_lazy(const dfq_le_plan* p) { return (p && lazy_active(p)) ? 1 : 0; }
+int32_t dfq_le_plan_set_ctl_stage(dfq_le_plan* p, int32_t n_partials) {
+    if (!p) return 0;
+    if (n_partials >= 0 && n_partials < p->ctl_stage) p->ctl_stage = n_partials;
+    return p->ctl_stage;
+}
 // out3 = (lazy sweeps, uncertain verdicts, sweeps) summed over the networks: the counts since the plan was made, the sweeps of the
 // current run (synchronises the stream)
 int dfq_le_plan_lazy_stats(dfq_le_plan* p, void* stream, int64_t* out3) {
@@ -3361,6 +3440,17 @@ static LeLazy lazy_args(const dfq_le_plan* p) {
     return z;
 }
 
+// (`cfg` null: where a call ends, no verdict is drawn)
+static LeVerdictArgs verdict_args(const dfq_le_plan* p, const dfq_le_config* cfg) {
+    LeVerdictArgs v;
+    v.layers = (const LeLayerDiff*)p->d_layer_diff; v.nets = (const LeNetDesc*)p->d_nets; v.states = p->d_state;
+    v.converge_thres = cfg ? cfg->converge_thres : 0.0;
+    v.converge_count = cfg ? (int32_t)cfg->converge_count : 0; v.max_sweeps = cfg ? (int32_t)cfg->max_sweeps : 0;
+    v.uni_layers = p->uni_layers; v.uni_tiles = p->uni_tiles;
+    v.lz = lazy_args(p);
+    return v;
+}
+
 static LeParams plan_params(const dfq_le_plan* p, const dfq_le_config* cfg) {
     LeParams q = make_params(cfg);
     q.defer = p->defer;
@@ -3410,8 +3500,7 @@ static int le_flush(dfq_le_plan* p, hipStream_t st) {
     if (rcj) return rcj;
     if (lazy_active(p)) {
         // the lazy sweeps' verdicts exactly, from the elements as they are stored now
-        hipLaunchKernelGGL(le_resolve_kernel, dim3(p->n_nets), dim3(kCtlBlock), 0, st, (const LeLayerDiff*)p->d_layer_diff,
-                           (const LeNetDesc*)p->d_nets, p->uni_layers, p->uni_tiles, p->d_state, lazy_args(p), 0, 0.0, 0, 0);
+        hipLaunchKernelGGL(le_resolve_kernel, dim3(p->n_nets), dim3(kCtlBlock), 0, st, verdict_args(p, nullptr));
         DFQ_CHECK_LAUNCH();
     }
     if (p->n_flush == 0) return DFQ_OK;
@@ -3547,23 +3636,17 @@ static int le_launch_control(dfq_le_plan* p, const dfq_le_config* cfg, hipStream
     const int n_helpers = std::max(1, n_clear);
     int rcb = le_bg_deadline(p, st);
     if (rcb) return rcb;
-    hipLaunchKernelGGL(le_control_kernel, dim3(p->n_nets + n_helpers + (solve ? p->n_cf_blocks : 0)), dim3(kCtlBlock), 0, st,
-                       (const LeLayerDiff*)p->d_layer_diff, (const LeNetDesc*)p->d_nets, p->n_nets,
-                       (const double*)sweep_partials(p), p->d_layer_mean, p->d_stats,
+    // (nothing is launched behind it: an undecided verdict of a lazy sweep is drawn by the network's own workgroup)
+    hipLaunchKernelGGL(le_control_kernel, dim3(p->n_nets + n_helpers + (solve ? p->n_cf_blocks : 0)), dim3(kCtlBlock),
+                       ctl_smem_bytes(p->ctl_stage, p->ctl_tab), st,
+                       verdict_args(p, cfg), p->n_nets, (const double*)sweep_partials(p), p->d_layer_mean, p->d_stats,
                        (int64_t)p->stat_words, p->d_stats + 2 * p->stat_words, (int64_t)p->stat_words,
-                       (int64_t)p->r1_zero_words, (int)(p->sweep_index & 1),
-                       p->d_state, cfg->converge_thres, (int)cfg->converge_count, (int)cfg->max_sweeps, p->uni_layers, p->uni_tiles,
-                       n_helpers, (const LeCfSeg*)p->d_cf_segs, (const LeCfRel*)p->d_cf_rels, (const int32_t*)p->d_cf_map,
-                       plan_params(p, cfg), (int)(p->sweep_index + 1 + (p->cf_bg ? p->cf_group : 0)), p->cf_group, lazy_args(p));
+                       (int64_t)p->r1_zero_words, (int)(p->sweep_index & 1), n_helpers,
+                       (const LeCfSeg*)p->d_cf_segs, (const LeCfRel*)p->d_cf_rels, (const int32_t*)p->d_cf_map,
+                       plan_params(p, cfg), (int)(p->sweep_index + 1 + (p->cf_bg ? p->cf_group : 0)), p->cf_group,
+                       p->ctl_stage, p->ctl_tab);
     DFQ_CHECK_LAUNCH();
-    if (lazy_active(p)) {
-        // the uncertain verdicts of lazy sweeps (le_resolve_kernel; a workgroup per network, all but those leave at once)
-        hipLaunchKernelGGL(le_resolve_kernel, dim3(p->n_nets), dim3(kCtlBlock), 0, st, (const LeLayerDiff*)p->d_layer_diff,
-                           (const LeNetDesc*)p->d_nets, p->uni_layers, p->uni_tiles, p->d_state, lazy_args(p), 1,
-                           cfg->converge_thres, (int)cfg->converge_count, (int)cfg->max_sweeps);
-        DFQ_CHECK_LAUNCH();
-    }
-    p->sweep_index += 1;             // the control launch closes a sweep
+    p->sweep_index += 1;            // the control launch closes a sweep
     return DFQ_OK;
 }
 

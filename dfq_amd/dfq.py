@@ -224,6 +224,11 @@ class LEPlan:
         _ffi.check(_ffi.lib().dfq_le_plan_lazy_stats(self._plan, _ffi.stream_arg(), out))
         return dict(lazy_sweeps=int(out[0]), uncertain=int(out[1]), sweeps=int(out[2]))
 
+    def set_control_stage(self, n_partials):
+        """Tests: lower the number of |dW| partials the convergence launch stages in LDS (what exceeds it is read from
+        memory); returns the stage in force."""
+        return int(_ffi.lib().dfq_le_plan_set_ctl_stage(self._plan, int(n_partials)))
+
     @property
     def sweep_bytes(self):
         """Bytes one sweep moves as executed (averaged over defer_depth sweeps and over a group of the free-running layers).

@@ -165,6 +165,10 @@ int32_t dfq_le_plan_lazy(const dfq_le_plan* plan);
 /* out3 = (lazy sweeps, uncertain verdicts resolved by the convergence launch, sweeps of the current run), summed over the
  * networks; the first two count since the plan was made.  Synchronises `stream`. */
 int dfq_le_plan_lazy_stats(dfq_le_plan* plan, void* stream, int64_t* out3);
+/* The convergence launch stages a network's |dW| partials in LDS, as many as the plan's largest network has (6144 at
+ * most), and reads what exceeds the stage from memory.  For tests of that second path: lower the stage to `n_partials`
+ * (>= 0; a value above the plan's own is ignored).  Returns the stage now in force. */
+int32_t dfq_le_plan_set_ctl_stage(dfq_le_plan* plan, int32_t n_partials);
 /* Free-running segments of the streaming engine (dfq_le_cf.hpp; DFQ_LE_CF=0 switches them off, DFQ_LE_CF_GROUP = G in
  * {2, 4, 8}, default 8 for a batched plan, 4 for a single network of >= 6 M paired elements, none for a smaller one: its
  * sweep is two launch latencies, and the lean launches only add to them).  A chain of relations whose every consumed range is closed-form -- a chain's first layer (rows * s,
