@@ -113,6 +113,17 @@ class DfqBatchMixedConfig(Structure):
                 ('code_bytes', c_int32), ('pad', c_int32), ('budget_bits', c_int64)]
 
 
+class DfqBatchNsrTensor(Structure):
+    _fields_ = [('data', c_void_p), ('rows', c_int64), ('row_len', c_int64), ('kernel_len', c_int64), ('groups', c_int32),
+                ('source_begin', c_int32), ('source_count', c_int32), ('pad', c_int32), ('moment_offset', c_int64),
+                ('row_offset', c_int64)]
+
+
+class DfqBatchNsrConfig(Structure):
+    _fields_ = [('widths', c_int32 * 8), ('n_widths', c_int32), ('symmetric', c_int32), ('per_row', c_int32), ('moment', c_int32),
+                ('input_moment', c_float), ('pad', c_int32)]
+
+
 class DfqBatchPackTensor(Structure):
     _fields_ = [('code_offset', c_int64), ('numel', c_int64), ('num_bits', c_int32), ('width_index', c_int32), ('symmetric', c_int32),
                 ('pad', c_int32)]
@@ -278,6 +289,13 @@ SIGNATURES = {
     'dfq_batch_mixed_plan_run': (c_int32, [c_void_p, c_void_p]),
     'dfq_batch_mixed_plan_destroy': (None, [c_void_p]),
     'dfq_batch_mixed_plan_launches': (c_int32, [c_void_p]),
+    'dfq_batch_mixed_plan_set_costs': (c_int32, [c_void_p, c_void_p]),
+    'dfq_batch_nsr_plan_create': (c_int32, [POINTER(DfqBatchNsrTensor), c_int32, c_void_p, c_int32, POINTER(DfqBatchNsrConfig),
+                                            POINTER(c_void_p), c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
+                                            POINTER(c_void_p)]),
+    'dfq_batch_nsr_plan_run': (c_int32, [c_void_p, c_void_p]),
+    'dfq_batch_nsr_plan_destroy': (None, [c_void_p]),
+    'dfq_batch_nsr_plan_launches': (c_int32, [c_void_p]),
     'dfq_batch_pack_plan_create': (c_int32, [POINTER(DfqBatchPackTensor), c_int32, POINTER(c_void_p), c_int32, c_void_p, c_int32, c_int64,
                                              c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, POINTER(c_void_p)]),
     'dfq_batch_pack_plan_run': (c_int32, [c_void_p, c_void_p]),

@@ -52,6 +52,10 @@ left it, and ``quantize_mixed(correct=True)`` is the three steps and the biases 
 ``pack_plan`` packs the codes a ``quant_plan``, ``squant_plan`` or ``mixed_plan`` wrote densely, every tensor of every network at
 its own width (read on the device), ``unpack_plan`` rebuilds codes and weights from the packed words, and ``save_packed`` /
 ``load_packed`` put a quantised batch into one ``.npz`` and back (tests/test_batch_pack.py).
+``nsr_plan`` gives the allocation a cost that knows the layer: every output channel's expected noise-to-signal ratio at every
+candidate width, from the weights and the BatchNorm proxies in front of the layer (the sources of the bias-correction walk);
+``mixed_plan(costs=that plan)`` and ``quantize_mixed(cost='nsr')`` allocate on it: nsr_plan -> mixed_plan(apply=False, costs=)
+-> bc_plan.run(widths=) -> mixed_plan(costs=) (tests/test_batch_nsr.py).
 """
 from __future__ import annotations
 
@@ -473,7 +477,7 @@ class NetworkBatch:
                 plan.close()
 
     def mixed_plan(self, widths=(2, 3, 4, 6, 8), avg_bits=None, budget_bits=None, per_channel=False, signed=False, sensitivity=None,
-                   pin=None, codes=None, apply=True):
+                   pin=None, codes=None, apply=True, costs=None):
         """One mixed-precision plan over the weights of the whole batch (BatchMixedPlan): every ``targ_type`` weight of every
         network gets a width of its own out of ``widths`` (rising ints in [2, 16], two to eight of them) so that the network
         takes at most ``budget_bits`` bits -- or, with ``avg_bits``, floor(avg_bits * number of weights), computed exactly;
@@ -484,12 +488,29 @@ class NetworkBatch:
         as ``quant_plan(bit_weight=that width, per_channel=, signed=)`` would; ``apply=False`` only allocates.  ``codes``:
         None, 'int32' or 'int8' (widths <= 8) as in ``quant_plan``.  The plan exposes ``bits(n)``, ``errors(n)``, ``used(n)``,
         ``cost(n)``, ``ranges(n)`` and ``codes(n)``.  Weights only.  ValueError for what create would refuse; RuntimeError
-        for a weight of network 0 that has left its slot."""
+        for a weight of network 0 that has left its slot.
+
+        ``costs``: a BatchNsrPlan of this batch with the same ``widths``, ``per_channel`` and ``signed`` (ValueError otherwise).
+        The allocation then weighs ``sensitivity[key]`` times the layer's summed noise-to-signal ratio (``nsr_plan``) in place of
+        its sum e^2, read on the device from that plan's ``cost_block`` -- run it first, on the same stream; ``errors(n)`` is
+        still the sum e^2, ``cost(n)`` the sum of the weighed costs at the chosen widths."""
         self._ready('mixed_plan')
-        return BatchMixedPlan(self, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, codes, apply)
+        return BatchMixedPlan(self, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, codes, apply, costs)
+
+    def nsr_plan(self, widths=(2, 3, 4, 6, 8), per_channel=False, signed=False, moment='variance', input_moment=1.0):
+        """One plan (BatchNsrPlan) for the data-free sensitivities ``mixed_plan(costs=)`` allocates on: for every ``targ_type``
+        weight of every network and every width of ``widths``, the sum over the output channels of the expected
+        noise-to-signal power ratio -- the quantisation error e^2 and the weight w^2 of every element weighed by the moment of
+        the input channel it reads, which comes from the BatchNorm proxies in front of the layer (the sources of the
+        bias-correction walk; dfq_batch_nsr_plan_create in include/dfq_hip.h holds the definition).  ``moment``: 'variance'
+        (what is left once bias correction has removed the mean term) or 'second_moment'; ``input_moment`` stands for the
+        channels of a layer fed by the data.  Nothing of the networks is written, no layer gets a bias.  The plan exposes
+        ``costs(n)``, ``rows(n)``, ``moments(n)`` and the blocks behind them."""
+        self._ready('nsr_plan')
+        return BatchNsrPlan(self, widths, per_channel, signed, moment, input_moment)
 
     def quantize_mixed(self, widths=(2, 3, 4, 6, 8), avg_bits=None, budget_bits=None, per_channel=False, signed=False, sensitivity=None,
-                       pin=None, codes='int32', bits_bias=16, correct=False):
+                       pin=None, codes='int32', bits_bias=16, correct=False, cost='mse', moment='variance', input_moment=1.0):
         """mixed_plan for the weights, the nearest rounding of ``quantize`` for the biases (unless ``bits_bias >= 32``), run +
         synchronise: returns (codes, ranges, bits), each a list of one dict per network -- the biases' ranges under
         key + '.bias', every bias bit for bit what ``quantize`` stores, ``bits[n][key]`` the width network n's layer got.
@@ -499,23 +520,35 @@ class NetworkBatch:
         the widths are read on the device, where the allocation left them -- then the applying plan and the biases, which are
         quantised AFTER their correction, as the reference orders the two (main_cls.py:176-181).  The correction writes no
         weight, so the applying plan allocates what the first one did.  Everything stays on the stream until the one
-        synchronisation at the end."""
+        synchronisation at the end.
+
+        ``cost='nsr'`` allocates on ``nsr_plan(widths, per_channel, signed, moment, input_moment)``, created and run first.  With
+        ``correct`` the order is nsr -> allocation -> correction -> applying plan on the SAME cost block: the correction moves
+        beta~ of later BatchNorms, so the costs are not computed again."""
         self._ready('quantize_mixed')
+        if cost not in ('mse', 'nsr'):
+            raise ValueError("quantize_mixed: cost must be 'mse' or 'nsr', got {!r}".format(cost))
         g0 = self.nets[0][0]
         tt = tuple(self.targ_type)
         plans, first = [], []
         try:
+            nsr = None
+            if cost == 'nsr':
+                nsr = BatchNsrPlan(self, widths, per_channel, signed, moment, input_moment)
+                first.append(nsr)
+                nsr.run()
             if correct:
-                first = [BatchMixedPlan(self, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, None, False), self.bc_plan()]
-                first[0].run()
-                first[1].run(signed=signed, per_channel=per_channel, widths=first[0])
-            plans.append(BatchMixedPlan(self, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, codes, True))
+                first += [BatchMixedPlan(self, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, None, False, nsr),
+                          self.bc_plan()]
+                first[-2].run()
+                first[-1].run(signed=signed, per_channel=per_channel, widths=first[-2])
+            plans.append(BatchMixedPlan(self, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, codes, True, nsr))
             if bits_bias < 32 and any(type(l) in tt and l.bias is not None for l in g0.values()):
                 plans.append(BatchQuantPlan(self, plans[0].widths[-1], bits_bias, per_channel, signed, None, _biases_only=True))
             for plan in plans:
                 plan.run()
             if correct:
-                first[1].status()              # (synchronises; an abandoned wait of the one-launch chain surfaces here)
+                first[-1].status()             # (synchronises; an abandoned wait of the one-launch chain surfaces here)
             _ffi.synchronize()
             n = len(self.nets)
             ranges = []
@@ -1058,12 +1091,22 @@ class BatchMixedPlan(_BatchPlan):
     depend on the others."""
     _c = 'dfq_batch_mixed_plan'
 
-    def __init__(self, batch, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, codes, apply):
+    def __init__(self, batch, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, codes, apply, costs=None):
         g0 = batch.nets[0][0]
         tt = tuple(batch.targ_type)
         layers = [(key, layer.weight) for key, layer in g0.items() if type(layer) in tt]
         if not layers:
             raise ValueError('mixed_plan: the batch has no {} layer'.format(tt))
+        if costs is not None:
+            if not isinstance(costs, BatchNsrPlan) or costs._batch is not batch:
+                raise ValueError('mixed_plan: costs must be a BatchNsrPlan of this batch')
+            try:
+                same = tuple(widths) == costs.widths
+            except TypeError:
+                same = False
+            if not same or bool(per_channel) != costs.per_channel or bool(signed) != costs.signed:
+                raise ValueError('mixed_plan: costs were made for widths {!r}, per_channel {}, signed {}; the plan asks for {!r}, {}, {}'.format(
+                    costs.widths, costs.per_channel, costs.signed, widths, bool(per_channel), bool(signed)))
         lay = _dfq._MixedLayout('mixed_plan', layers, lambda key, w: batch._in_slot(key, 'weight', w), len(batch.nets), widths,
                                 avg_bits, budget_bits, per_channel, signed, sensitivity, pin, codes, apply, batch.stage.device)
         super().__init__(batch)
@@ -1075,6 +1118,18 @@ class BatchMixedPlan(_BatchPlan):
         self.bits_block, self.error_block, self.used_block, self.cost_block = lay.bits_block, lay.error_block, lay.used_block, lay.cost_block
         self.range_block, self.code_block = lay.range_block, lay.code_block
         self._create(lay.tables(), *lay.block_args())
+        self._costs = None
+        if costs is not None:
+            self.set_costs(costs)
+
+    def set_costs(self, costs):
+        """Allocate on ``costs.cost_block`` (a BatchNsrPlan of the same batch, widths, per_channel and signed: the constructor
+        checks that, this does not) from the next run on; None: on the plan's own errors again."""
+        if not self._plan:
+            raise RuntimeError('BatchMixedPlan: the plan has been closed')
+        block = None if costs is None else costs.cost_block
+        _ffi.check(_ffi.lib().dfq_batch_mixed_plan_set_costs(self._plan, None if block is None else block.data_ptr()))
+        self._costs = block                        # (kept alive while the plan reads it)
 
     def bits(self, n):
         """``OrderedDict[graph key -> int]``: the width network n's weight got (one device-to-host copy)"""
@@ -1099,6 +1154,51 @@ class BatchMixedPlan(_BatchPlan):
     def codes(self, n):
         """{graph key: integer codes of network n's weight, shaped like it} -- views of the code block; {} without codes"""
         return self._lay.codes(n)
+
+
+class BatchNsrPlan(_BatchPlan):
+    """Data-free layer sensitivities of every network of a NetworkBatch (dfq_batch_nsr_plan, include/dfq_hip.h, which holds the
+    definition): network 0's table of ``targ_type`` weights, the source table of its bias-correction walk -- the batch's own, made
+    when the batch was put together -- and the batch's base addresses.  ``run()`` enqueues ``launches`` launches on the current
+    stream and writes nothing but the plan's blocks, torch tensors that outlive ``close()``: ``moment_block`` float32
+    [n_nets, moment_stride], ``row_block`` float64 [n_nets, row_stride, B] (R per output row), ``signal_block`` float64
+    [n_nets, row_stride] (S) and ``cost_block`` float64 [n_nets, T, B] (N, what ``mixed_plan(costs=)`` reads).  Two runs give
+    bit-equal blocks, and a network's part does not depend on the others."""
+    _c = 'dfq_batch_nsr_plan'
+
+    def __init__(self, batch, widths, per_channel, signed, moment, input_moment):
+        g0 = batch.nets[0][0]
+        tt = tuple(batch.targ_type)
+        layers = [(key, layer.weight, getattr(layer, 'groups', 1)) for key, layer in g0.items() if type(layer) in tt]
+        if not layers:
+            raise ValueError('nsr_plan: the batch has no {} layer'.format(tt))
+        steps, keys = batch._bc.arrays['steps'], [key for key, _, _ in layers]
+        ranges = {keys[int(li)]: (int(b), int(c)) for li, b, c in zip(steps['layer'], steps['source_begin'], steps['source_count'])}
+        lay = _dfq._NsrLayout('nsr_plan', layers, lambda key, w: batch._in_slot(key, 'weight', w), len(batch.nets),
+                              batch._bc.arrays['sources'], ranges, widths, per_channel, signed, moment, input_moment, batch.stage.device)
+        super().__init__(batch)
+        self._lay = lay
+        self.widths, self.per_channel, self.signed = lay.widths, lay.per_channel, lay.signed
+        self.moment, self.input_moment = lay.moment, lay.input_moment
+        self.keys, self.n_nets, self.n_tensors = lay.keys, lay.n_nets, lay.n_tensors
+        self.cost_block, self.row_block, self.signal_block, self.moment_block = lay.cost_block, lay.row_block, lay.signal_block, lay.moment_block
+        self._create(lay.tables(), *lay.block_args())
+
+    def costs(self, n):
+        """``OrderedDict[graph key -> float64 numpy [B]]``: N of network n's layer at every width of ``widths``"""
+        return self._lay.costs(n)
+
+    def rows(self, n):
+        """``OrderedDict[graph key -> float64 numpy [O, B]]``: R, the noise-to-signal ratio of every output row"""
+        return self._lay.rows(n)
+
+    def signal(self, n):
+        """``OrderedDict[graph key -> float64 numpy [O]]``: S, the weighed signal power of every output row"""
+        return self._lay.signal(n)
+
+    def moments(self, n):
+        """``OrderedDict[graph key -> float32 numpy [g * I/g]]``: a, the moment of every input channel the layer reads"""
+        return self._lay.moments(n)
 
 
 _PACKED_VERSION = 1            # of the file save_packed writes

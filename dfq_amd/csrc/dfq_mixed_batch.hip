@@ -14,7 +14,8 @@
 //      adds in the order (row set, register slot); wave_sum (a fixed butterfly) gives the wave's sums, block_sum a chunk's;
 //      they go to the plan's scratch [n_nets, parts, B], a part being a wave of the row tensors or a chunk.
 //   2. bm_alloc_kernel, one workgroup per network: a thread per (tensor, width) adds the tensor's parts in rising order (the
-//      errors block; cost = sensitivity * error into LDS), then the first wave walks the greedy allocation.  Lane l owns the
+//      errors block; cost = sensitivity * error, or * the caller's cost after set_costs, into LDS), then the first wave walks
+//      the greedy allocation.  Lane l owns the
 //      tensors l, l + 64, ...: their current index and their cached next step (g, k) lie in LDS and are touched by the owner
 //      alone, so the walk needs no barrier: per step a scan of the owned tensors, a butterfly argmax of (g, tensor) over the
 //      wave, a broadcast of the step's size from the owner, the budget test (the same in every lane), and the owner's
@@ -88,6 +89,7 @@ struct BmArgs {
     double* partial;              // [n_nets, parts_pn, n_widths]
     int32_t* bits;                // [n_nets, n_tensors]
     double* errors;               // [n_nets, n_tensors, n_widths]
+    const double* costs;          // [n_nets, n_tensors, n_widths] the allocation weighs in place of the errors, or null (set_costs)
     int64_t* used;                // [n_nets, 2]
     double* cost;                 // [n_nets]
     unsigned char* codes;
@@ -375,7 +377,7 @@ __global__ __launch_bounds__(kBlock) void bm_alloc_kernel(BmArgs a) {
 #pragma unroll 8
         for (int q = 0; q < D.n_parts; ++q) s += part[(int64_t)q * nb];
         ((gdouble*)a.errors)[((int64_t)net * nt + ti) * nb + j] = s;
-        cost[i] = D.sens * s;
+        cost[i] = D.sens * (a.costs ? ((const gdouble*)a.costs)[((int64_t)net * nt + ti) * nb + j] : s);
     }
     __syncthreads();
     long long used = 0;
@@ -607,6 +609,12 @@ int dfq_batch_mixed_plan_create(const dfq_batch_mixed_tensor* tensors, int32_t n
         return fail_hip(up.err, "batch mixed plan allocation", __FILE__, __LINE__);
     }
     *out_plan = p;
+    return DFQ_OK;
+}
+
+int dfq_batch_mixed_plan_set_costs(dfq_batch_mixed_plan* p, const double* costs) {
+    if (!p) return fail_arg("dfq_batch_mixed_plan_set_costs: null plan");
+    p->args.costs = costs;
     return DFQ_OK;
 }
 

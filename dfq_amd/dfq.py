@@ -1389,8 +1389,112 @@ class _MixedLayout:
         return OrderedDict((key, row[off:off + numel].view(shape)) for (key, off, numel, shape) in self._code_views)
 
 
+_NSR_MOMENTS = {'variance': 0, 'second_moment': 1}
+
+
+class _NsrLayout:
+    """The tensor table, the configuration and the output blocks of one dfq_batch_nsr_plan; every argument is checked here,
+    ValueError('<who>: ...') for what create would refuse.  ``layers``: [(graph key, weight, groups)]; ``address(key, weight)``
+    gives the weight's device address in network 0; ``sources``: the dfq_bc_source table of network 0 (numpy, _SRC_DT) and
+    ``source_range[key]`` = (begin, count) in it -- a key without an entry gets ``input_moment``.  The blocks are torch tensors:
+    ``moment_block`` float32 [n_nets, moment_stride], ``row_block`` float64 [n_nets, row_stride, B], ``signal_block`` float64
+    [n_nets, row_stride], ``cost_block`` float64 [n_nets, T, B]."""
+
+    def __init__(self, who, layers, address, n_nets, sources, source_range, widths, per_channel, signed, moment, input_moment, device):
+        import math
+        import numbers
+        try:
+            widths = tuple(widths)
+        except TypeError:
+            raise ValueError('{}: widths must be a sequence of bit widths, got {!r}'.format(who, widths)) from None
+        if not 1 <= len(widths) <= 8:
+            raise ValueError('{}: 1 to 8 candidate widths, got {!r}'.format(who, widths))
+        if any(isinstance(b, bool) or not isinstance(b, numbers.Integral) or not 2 <= b <= 16 for b in widths):
+            raise ValueError('{}: every width must be an int in [2, 16], got {!r}'.format(who, widths))
+        if any(b <= a for a, b in zip(widths, widths[1:])):
+            raise ValueError('{}: the widths must rise, got {!r}'.format(who, widths))
+        if moment not in _NSR_MOMENTS:
+            raise ValueError('{}: moment must be one of {}, got {!r}'.format(who, sorted(_NSR_MOMENTS), moment))
+        if isinstance(input_moment, bool) or not isinstance(input_moment, numbers.Real) or not math.isfinite(input_moment) \
+                or input_moment < 0 or float(input_moment) > 3.4028234663852886e38:
+            raise ValueError('{}: input_moment must be a finite float32 >= 0, got {!r}'.format(who, input_moment))
+        if not layers:
+            raise ValueError('{}: no layer to look at'.format(who))
+        self.widths = tuple(int(b) for b in widths)
+        self.per_channel, self.signed, self.moment, self.input_moment = bool(per_channel), bool(signed), moment, float(input_moment)
+        self.keys, self.n_nets, self.n_tensors = [key for key, _, _ in layers], n_nets, len(layers)
+        entries, self._views = [], []
+        moment_stride = row_stride = 0
+        for key, w, groups in layers:
+            rows = int(w.shape[0])
+            row_len = w.numel() // rows
+            klen = 1
+            for d in w.shape[2:]:
+                klen *= int(d)
+            channels = row_len // klen * int(groups)
+            begin, count = source_range.get(key, (0, 0))
+            self._views.append((key, moment_stride, channels, row_stride, rows))
+            entries.append(_ffi.DfqBatchNsrTensor(address(key, w), rows, row_len, klen, int(groups), int(begin), int(count), 0,
+                                                  moment_stride, row_stride))
+            moment_stride += -(-channels // 4) * 4
+            row_stride += rows
+        self.table = (_ffi.DfqBatchNsrTensor * len(entries))(*entries)
+        self.sources = _np.ascontiguousarray(sources, dtype=_SRC_DT)
+        self.config = _ffi.DfqBatchNsrConfig((ctypes.c_int32 * 8)(*self.widths), len(self.widths), int(self.signed), int(self.per_channel),
+                                             _NSR_MOMENTS[moment], self.input_moment, 0)
+        B = len(self.widths)
+        self.moment_stride, self.row_stride = moment_stride, row_stride
+        self.moment_block = torch.zeros((n_nets, moment_stride), dtype=torch.float32, device=device)
+        self.row_block = torch.zeros((n_nets, row_stride, B), dtype=torch.float64, device=device)
+        self.signal_block = torch.zeros((n_nets, row_stride), dtype=torch.float64, device=device)
+        self.cost_block = torch.zeros((n_nets, len(entries), B), dtype=torch.float64, device=device)
+
+    def tables(self):
+        """(tensors, n_tensors, sources, n_sources, config) as dfq_batch_nsr_plan_create takes them in front of the bases"""
+        return (self.table, self.n_tensors, ctypes.c_void_p(self.sources.ctypes.data if len(self.sources) else None), len(self.sources),
+                ctypes.byref(self.config))
+
+    def block_args(self):
+        """(moments, moment_stride, rows, signal, row_stride, costs) as create takes them behind the bases"""
+        return (self.moment_block.data_ptr(), self.moment_stride, self.row_block.data_ptr(), self.signal_block.data_ptr(),
+                self.row_stride, self.cost_block.data_ptr())
+
+    def costs(self, n):
+        block = self.cost_block[n].cpu().numpy()
+        return OrderedDict((key, block[i].copy()) for i, key in enumerate(self.keys))
+
+    def rows(self, n):
+        block = self.row_block[n].cpu().numpy()
+        return OrderedDict((key, block[off:off + rows].copy()) for (key, _, _, off, rows) in self._views)
+
+    def signal(self, n):
+        block = self.signal_block[n].cpu().numpy()
+        return OrderedDict((key, block[off:off + rows].copy()) for (key, _, _, off, rows) in self._views)
+
+    def moments(self, n):
+        block = self.moment_block[n].cpu().numpy()
+        return OrderedDict((key, block[off:off + ch].copy()) for (key, off, ch, _, _) in self._views)
+
+
+def _nsr_sources(graph, bottoms, targ_type, bn_type, address):
+    """The dfq_bc_source table of one network for the layer sensitivities, from the bias-correction walk run WITHOUT its side
+    effect (no layer gets a bias): (numpy _SRC_DT, {graph key: (begin, count)}).  ``address(tensor)``: its device address."""
+    keys = [k for k in graph if type(graph[k]) in targ_type]
+    _, steps, _ = _bc_tables(graph, bottoms, targ_type, bn_type, ensure_bias=False)
+    rows, ranges = [], {}
+    for (li, srcs, _, _) in steps:
+        ranges[keys[li]] = (len(rows), len(srcs))
+        for (fw, fb, relu, cat) in srcs:
+            rows.append((0 if fw is None else address(fw), address(fb), int(fb.numel()), int(bool(relu)), int(bool(cat))))
+    arr = _np.zeros(len(rows), dtype=_SRC_DT)
+    for i, (fw, fb, ch, relu, cat) in enumerate(rows):
+        arr['fake_weight'][i], arr['fake_bias'][i], arr['channels'][i], arr['relu'][i], arr['concat'][i] = fw, fb, ch, relu, cat
+    return arr, ranges
+
+
 def quantize_mixed(graph, widths=(2, 3, 4, 6, 8), avg_bits=None, budget_bits=None, per_channel=False, signed=False, sensitivity=None,
-                   pin=None, targ_type=[nn.Conv2d, nn.Linear]):
+                   pin=None, targ_type=[nn.Conv2d, nn.Linear], cost='mse', bottoms=None, bn_type=torch.nn.BatchNorm2d,
+                   moment='variance', input_moment=1.0):
     """Mixed-precision ``quantize_targ_layer`` for the weights (extension): every ``targ_type`` weight is quantised in place
     at a width of its own out of ``widths``, chosen so that the network takes at most ``budget_bits`` bits (or ``avg_bits``
     per weight on average: floor(avg_bits * number of weights)) and the sum of ``sensitivity[key]`` (default 1) times the
@@ -1399,29 +1503,60 @@ def quantize_mixed(graph, widths=(2, 3, 4, 6, 8), avg_bits=None, budget_bits=Non
     ``NetworkBatch.mixed_plan``, the same plan over a batch of one; it stands where ``quantize_targ_layer`` stands, behind
     equalisation, absorption and clipping.  Biases are left alone.  Returns
     ``OrderedDict[key -> {'bits', 'err', 'range'}]``: the chosen width, the sum e^2 at it, and the (min, max) the quantiser
-    used ([2], or [O, 2] with ``per_channel``).  ValueError for what ``NetworkBatch.mixed_plan`` refuses."""
+    used ([2], or [O, 2] with ``per_channel``).  ValueError for what ``NetworkBatch.mixed_plan`` refuses.
+
+    ``cost='nsr'`` allocates on the data-free layer sensitivities instead of the plain sum e^2 (dfq_batch_nsr_plan,
+    include/dfq_hip.h: every output channel's expected noise-to-signal ratio under the BatchNorm proxies in front of the layer;
+    ``NetworkBatch.nsr_plan`` for a batch of one).  It needs ``bottoms`` (ValueError without) and the proxies
+    ``merge_batchnorm`` leaves on the ``bn_type`` modules; ``moment`` ('variance' or 'second_moment') and ``input_moment`` are
+    ``nsr_plan``'s.  Each layer's dict then also holds ``'nsr'``, N at the chosen width.  No layer is given a bias."""
     lib = _ffi.lib()
     layers = [(key, graph[key].weight) for key in graph if type(graph[key]) in targ_type]
     if not layers:
         raise ValueError('quantize_mixed: the graph has no {} layer'.format(tuple(targ_type)))
+    if cost not in ('mse', 'nsr'):
+        raise ValueError("quantize_mixed: cost must be 'mse' or 'nsr', got {!r}".format(cost))
+    if cost == 'nsr' and bottoms is None:
+        raise ValueError("quantize_mixed: cost='nsr' reads the BatchNorms in front of every layer and needs `bottoms`")
     with torch.no_grad():
         stage = _ffi.entry_stage()
-        stage.prefetch([w for _, w in layers])
+        proxies = []
+        if cost == 'nsr':
+            proxies = [t for m in graph.values() if type(m) == bn_type for t in (getattr(m, 'fake_weight', None), getattr(m, 'fake_bias', None))
+                       if t is not None]
+        stage.prefetch([w for _, w in layers] + proxies)
         bufs = {key: stage.bind(w) for key, w in layers}
         lay = _MixedLayout('quantize_mixed', layers, lambda key, w: bufs[key].data_ptr(), 1, widths, avg_bits, budget_bits, per_channel,
                            signed, sensitivity, pin, None, True, stage.device)
         bases = (ctypes.c_void_p * 1)(bufs[layers[0][0]].data_ptr())
-        plan = ctypes.c_void_p()
-        _ffi.check(lib.dfq_batch_mixed_plan_create(*lay.tables(), bases, 1, *lay.block_args(), ctypes.byref(plan)))
+        plan, nsr, nlay = ctypes.c_void_p(), ctypes.c_void_p(), None
         try:
+            if cost == 'nsr':
+                sources, ranges_of = _nsr_sources(graph, bottoms, targ_type, bn_type, lambda t: stage.bind(t).data_ptr())
+                nlay = _NsrLayout('quantize_mixed', [(key, w, getattr(graph[key], 'groups', 1)) for key, w in layers],
+                                  lambda key, w: bufs[key].data_ptr(), 1, sources, ranges_of, lay.widths, per_channel, signed, moment,
+                                  input_moment, stage.device)
+                _ffi.check(lib.dfq_batch_nsr_plan_create(*nlay.tables(), bases, 1, *nlay.block_args(), ctypes.byref(nsr)))
+                _ffi.check(lib.dfq_batch_nsr_plan_run(nsr, _ffi.stream_arg()))
+            _ffi.check(lib.dfq_batch_mixed_plan_create(*lay.tables(), bases, 1, *lay.block_args(), ctypes.byref(plan)))
+            if nlay is not None:
+                _ffi.check(lib.dfq_batch_mixed_plan_set_costs(plan, nlay.cost_block.data_ptr()))
             _ffi.check(lib.dfq_batch_mixed_plan_run(plan, _ffi.stream_arg()))
             _ffi.synchronize()
             bits, errors, ranges = lay.bits(0), lay.errors(0), lay.ranges(0)
+            costs = nlay.costs(0) if nlay is not None else None
         finally:
-            lib.dfq_batch_mixed_plan_destroy(plan)
-        stage.writeback()
-    return OrderedDict((key, {'bits': bits[key], 'err': float(errors[key][lay.widths.index(bits[key])]),
-                              'range': ranges[key].cpu().numpy().copy()}) for key in lay.keys)
+            if plan:
+                lib.dfq_batch_mixed_plan_destroy(plan)
+            if nsr:
+                lib.dfq_batch_nsr_plan_destroy(nsr)
+        stage.writeback(unchanged=proxies)
+    out = OrderedDict((key, {'bits': bits[key], 'err': float(errors[key][lay.widths.index(bits[key])]),
+                             'range': ranges[key].cpu().numpy().copy()}) for key in lay.keys)
+    if costs is not None:
+        for key in lay.keys:
+            out[key]['nsr'] = float(costs[key][lay.widths.index(bits[key])])
+    return out
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1714,7 +1849,9 @@ def build_bc_plan(graph, bottoms, targ_type, bn_type=torch.nn.BatchNorm2d, stage
     return plan, keys
 
 
-def _bc_tables(graph, bottoms, targ_type, bn_type, base=0, net=0):
+def _bc_tables(graph, bottoms, targ_type, bn_type, base=0, net=0, ensure_bias=True):
+    """``ensure_bias=False``: the walk alone -- which BatchNorms feed each layer and how they merge -- without giving the layers
+    it corrects a zero bias (the sources of the layer sensitivities, ``_nsr_sources``: that reader must not change the network)."""
     keys = [k for k in graph if type(graph[k]) in targ_type]
     index = {k: base + i for i, k in enumerate(keys)}
     bn_module, relu_attached = {}, {}
@@ -1747,7 +1884,8 @@ def _bc_tables(graph, bottoms, targ_type, bn_type, base=0, net=0):
             srcs = []
             for j, (bn, _, relu, ctype) in enumerate(ordered):
                 srcs.append((bn.fake_weight, bn.fake_bias, relu, j > 0 and ctype == 'cat'))
-            _ensure_bias(node)
+            if ensure_bias:
+                _ensure_bias(node)
             step = [index[key], srcs, None, net]
             steps.append(step)
             pending = step

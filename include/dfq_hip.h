@@ -798,6 +798,93 @@ int dfq_batch_mixed_plan_run(dfq_batch_mixed_plan* plan, void* stream);
 void dfq_batch_mixed_plan_destroy(dfq_batch_mixed_plan* plan);
 /* kernel launches per run (2 to 4), fixed at creation; the clear of the range words of the long tensors is a memset */
 int32_t dfq_batch_mixed_plan_launches(const dfq_batch_mixed_plan* plan);
+/* Allocate on given costs (extension): with `costs` set -- float64 on the device, [n_nets, T, B] with the plan's own T and B,
+ * which nothing here can check -- the allocation of every later run forms c[t][j] = s_t * costs[n][t][j] in place of
+ * s_t * E[n][t][j]; `cost` then reports the sum of those c at the chosen widths.  Everything else of the definition above is
+ * unchanged: E is still computed and reported in `errors`, the walk, its ties, the pins, the budget rule and the quantisation
+ * are the same.  Every cost must be finite or NaN; a NaN cost takes no step (g > 0 is false), as a NaN error does.  The block
+ * is read by the allocation launch of a run, so whatever writes it (dfq_batch_nsr_plan_run) goes onto the same stream in
+ * front.  NULL, the default: the plan's own errors again, every result bit for bit that of a plan that never had costs.
+ * DFQ_ERR_ARG for a null plan. */
+int dfq_batch_mixed_plan_set_costs(dfq_batch_mixed_plan* plan, const double* costs /* device [n_nets, T, B], or NULL */);
+
+/* Data-free layer sensitivities of a whole batch of networks of one architecture (extension): the expected noise-to-signal
+ * power ratio of every output channel of every layer at every candidate width, from the weights and the BatchNorm proxies
+ * alone -- the costs dfq_batch_mixed_plan_set_costs takes.  `tensors` and `sources` describe the FIRST of `n_nets` networks;
+ * network n's copy of a tensor or proxy lies bases[n] - bases[0] bytes further.  Nothing is written but the output blocks.
+ * DEFINITION.  Layer t of network n has the weight W [O, I/g, K] (rows = O, row_len = I/g * K, kernel_len = K = kH * kW,
+ * groups = g); element (o, i, k) of row o reads input channel c(o, i) = (o / (O/g)) * (I/g) + i.
+ *   moments     a[n][t][c], float32, c in [0, g * I/g), from the layer's sources [source_begin, source_begin + source_count)
+ *               of the dfq_bc_source table: the BatchNorms the bias-correction walk lists for it, in its order.  Per source
+ *               (mean, var) is bit for bit what dfq_relu_moments gives at mode 1 if `relu` is set, else mode 0; a source
+ *               without fake_weight has mean = beta~ and var = 0.  The first source sets the pair; a source with `concat`
+ *               continues at the next channel; any other adds mean and var onto the channels so far, in source order, one
+ *               float32 addition each, as `accumulate` of dfq_relu_moments does.  Then, with v = var < 0 ? 0 : var,
+ *                 moment = 0 (variance):       a_c = v -- the noise that remains once bias correction has removed the mean
+ *                                              term (sum e * mu)^2;
+ *                 moment = 1 (second moment):  a_c = (float)((double)mean * (double)mean + (double)v).
+ *               NaN stays NaN.  A layer with source_count = 0 -- the first convolution, any layer fed by the data -- gets
+ *               a_c = input_moment for every c (float32, finite, >= 0).
+ *   rows        per row o and width j, in float64.  e_j = fake_quant(w; qparams(min, max, b_j, symmetric)) - w in float32,
+ *               term for term the e of dfq_batch_error_plan and dfq_batch_mixed_plan; (min, max) is the tensor's pair, or
+ *               row o's with per_row; NaN is skipped by the ranges.
+ *                 Ne[o][j] = sum over (i, k) of (double)a_c(o,i) * (e_j * e_j)    (the square is exact, the product one rounding)
+ *                 S[o]     = sum over (i, k) of (double)a_c(o,i) * (w * w)
+ *                 R[o][j]  = S[o] == 0 ? 0 : Ne[o][j] / S[o], one division.
+ *               The order of the two sums is the plan's own and depends on the row's length alone.  No floating-point atomic
+ *               is used: two runs are bit-identical, and network n's values depend neither on n_nets nor on n's place in the
+ *               batch.  R is the expected noise-to-signal power ratio of output channel o under independent input channels
+ *               and positions with those moments; numerator and denominator share the model, so no BatchNorm behind the
+ *               layer is needed.
+ *   costs       N[n][t][j] = R[0][j] + R[1][j] + ... in rising o, from 0.0, one float64 addition each.
+ * A tensor holding a NaN weight gets NaN in its own slots only; a NaN moment does the same for the rows that read it.
+ * Candidate widths b_0 < ... < b_{B-1}, integers in [2, 16], 1 <= B <= 8.
+ * Outputs, blocks of the caller: `moments` float32 [n_nets, moment_stride], layer t's a at moment_offset; `rows` float64
+ * [n_nets, row_stride, B], R of layer t's row o at (row_offset + o); `signal` float64 [n_nets, row_stride], S, may be NULL;
+ * `costs` float64 [n_nets, T, B].  Nothing else in the blocks is touched.
+ * Launches per run, fixed at creation (3, or 4 per tensor): the moments, a workgroup per (network, layer); per tensor the
+ * tensors' (min, max); the rows; the fold.  A row of at most dfq_batch_quant_register_elements() elements stays in registers
+ * from its range through all B errors, L lanes per row with L taken from the row length and B + 1 float64 accumulators per
+ * lane; longer rows get a looping wave.  Every weight is read once with per_row, twice per tensor.  No workgroup waits for
+ * another and nothing synchronises with the host.
+ * create: DFQ_ERR_ARG (and dfq_last_error) for null or empty tables, a null configuration, B outside 1..8, widths that do not
+ * rise or lie outside [2, 16], row_len % kernel_len != 0, rows % groups != 0, sources whose channels do not sum to
+ * groups * row_len / kernel_len (or an add of another length, or a null proxy), a source range outside the table, an
+ * input_moment that is negative or not finite, an unknown `moment`, a weight that is null or not 16-byte aligned, rows <= 0 or
+ * row_len <= 0, a null moments / rows / costs block, offsets outside their strides, null bases, networks that are not 16-byte
+ * aligned to network 0.  Synchronises (create only); run is asynchronous on `stream`. */
+typedef struct dfq_batch_nsr_plan dfq_batch_nsr_plan;
+typedef struct dfq_batch_nsr_tensor { /* addresses in network 0 */
+    const float* data;      /* the layer's weight [rows, row_len]; read only                                         */
+    int64_t rows;           /* O                                                                                     */
+    int64_t row_len;        /* I/g * K                                                                               */
+    int64_t kernel_len;     /* K = kH * kW                                                                           */
+    int32_t groups;         /* g                                                                                     */
+    int32_t source_begin;   /* range in the dfq_bc_source table; source_count = 0: input_moment                     */
+    int32_t source_count;
+    int32_t pad;
+    int64_t moment_offset;  /* floats into a network's moment block                                                  */
+    int64_t row_offset;     /* rows into a network's row and signal blocks                                           */
+} dfq_batch_nsr_tensor;
+typedef struct dfq_batch_nsr_config {
+    int32_t widths[8];      /* b_0 < b_1 < ...; the first n_widths count                                             */
+    int32_t n_widths;       /* B                                                                                     */
+    int32_t symmetric;      /* the signed recipe                                                                     */
+    int32_t per_row;        /* ranges per output row instead of per tensor                                           */
+    int32_t moment;         /* 0: variance, 1: second moment                                                         */
+    float input_moment;     /* a_c of a layer without sources                                                        */
+    int32_t pad;
+} dfq_batch_nsr_config;
+struct dfq_bc_source;       /* defined with the bias correction, below */
+
+int dfq_batch_nsr_plan_create(const dfq_batch_nsr_tensor* tensors, int32_t n_tensors, const struct dfq_bc_source* sources,
+                              int32_t n_sources, const dfq_batch_nsr_config* config, const void* const* bases, int32_t n_nets,
+                              float* moments, int64_t moment_stride, double* rows, double* signal, int64_t row_stride, double* costs,
+                              dfq_batch_nsr_plan** out_plan);
+int dfq_batch_nsr_plan_run(dfq_batch_nsr_plan* plan, void* stream);
+void dfq_batch_nsr_plan_destroy(dfq_batch_nsr_plan* plan);
+/* kernel launches per run (3 or 4), fixed at creation; the clear of the range words of a per-tensor plan is a memset */
+int32_t dfq_batch_nsr_plan_launches(const dfq_batch_nsr_plan* plan);
 
 /* Dense bit-packing of the integer codes of a whole batch, every tensor of every network at its own width, and the way back
  * (extension; the artefact of a mixed-precision calibration: dfq_batch_quant_plan, dfq_batch_squant_plan and
