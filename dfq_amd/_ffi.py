@@ -113,6 +113,14 @@ class DfqBatchMixedConfig(Structure):
                 ('code_bytes', c_int32), ('pad', c_int32), ('budget_bits', c_int64)]
 
 
+class DfqBatchMixedClip(Structure):
+    _fields_ = [('candidates', c_int32), ('pad', c_int32), ('alpha_min', c_double), ('clip_ranges', c_void_p), ('clip_chosen', c_void_p),
+                ('unit_errors', c_void_p), ('unit_stride', c_int64), ('unit_offsets', POINTER(c_int64))]
+
+
+MIXED_ALLOCATE, MIXED_CLAMP, MIXED_QUANTISE = 1, 2, 4      # DFQ_MIXED_* of include/dfq_hip.h
+
+
 class DfqBatchNsrTensor(Structure):
     _fields_ = [('data', c_void_p), ('rows', c_int64), ('row_len', c_int64), ('kernel_len', c_int64), ('groups', c_int32),
                 ('source_begin', c_int32), ('source_count', c_int32), ('pad', c_int32), ('moment_offset', c_int64),
@@ -290,6 +298,10 @@ SIGNATURES = {
     'dfq_batch_mixed_plan_destroy': (None, [c_void_p]),
     'dfq_batch_mixed_plan_launches': (c_int32, [c_void_p]),
     'dfq_batch_mixed_plan_set_costs': (c_int32, [c_void_p, c_void_p]),
+    'dfq_batch_mixed_plan_create_clipped': (c_int32, [POINTER(DfqBatchMixedTensor), c_int32, POINTER(DfqBatchMixedConfig),
+                                                      POINTER(c_void_p), c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                      c_int64, c_void_p, c_int64, POINTER(DfqBatchMixedClip), POINTER(c_void_p)]),
+    'dfq_batch_mixed_plan_run_stages': (c_int32, [c_void_p, c_int32, c_void_p]),
     'dfq_batch_nsr_plan_create': (c_int32, [POINTER(DfqBatchNsrTensor), c_int32, c_void_p, c_int32, POINTER(DfqBatchNsrConfig),
                                             POINTER(c_void_p), c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
                                             POINTER(c_void_p)]),

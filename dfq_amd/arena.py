@@ -477,7 +477,7 @@ class NetworkBatch:
                 plan.close()
 
     def mixed_plan(self, widths=(2, 3, 4, 6, 8), avg_bits=None, budget_bits=None, per_channel=False, signed=False, sensitivity=None,
-                   pin=None, codes=None, apply=True, costs=None):
+                   pin=None, codes=None, apply=True, costs=None, clip=None, alpha_min=0.5):
         """One mixed-precision plan over the weights of the whole batch (BatchMixedPlan): every ``targ_type`` weight of every
         network gets a width of its own out of ``widths`` (rising ints in [2, 16], two to eight of them) so that the network
         takes at most ``budget_bits`` bits -- or, with ``avg_bits``, floor(avg_bits * number of weights), computed exactly;
@@ -493,9 +493,19 @@ class NetworkBatch:
         ``costs``: a BatchNsrPlan of this batch with the same ``widths``, ``per_channel`` and ``signed`` (ValueError otherwise).
         The allocation then weighs ``sensitivity[key]`` times the layer's summed noise-to-signal ratio (``nsr_plan``) in place of
         its sum e^2, read on the device from that plan's ``cost_block`` -- run it first, on the same stream; ``errors(n)`` is
-        still the sum e^2, ``cost(n)`` the sum of the weighed costs at the chosen widths."""
+        still the sum e^2, ``cost(n)`` the sum of the weighed costs at the chosen widths.
+
+        ``clip``: None for the plan above through its own entry point, or K, an int in [1, 64]: the clip-aware plan
+        (dfq_batch_mixed_plan_create_clipped).  The MSE-optimal clip of every unit -- a tensor, or an output row with
+        ``per_channel`` -- is searched among K candidates down to ``alpha_min`` (in (0, 1]) times the range at EVERY width, bit
+        for bit what ``clip_plan(that width, ..., candidates=K, alpha_min=)`` finds; the allocation walks on the errors of the
+        clipped ranges, and with ``apply`` every layer is clamped and quantised at its own width and that width's range, bit
+        for bit ``clip_plan(width, apply=True)`` then ``quant_plan(width)``.  ``ranges(n)`` is then the chosen width's (l, h);
+        ``clip_ranges(n)``, ``clip_chosen(n)`` and ``unit_errors(n)`` hold every width's, in ``clip_range_block`` float32
+        [n_nets, units, B, 2], ``clip_chosen_block`` int32 and ``unit_error_block`` float64 [n_nets, units, B].  At most 512
+        (width, candidate) pairs.  ``run(stages)`` / ``allocate()`` / ``clamp()`` / ``quantise()`` run the stages one by one."""
         self._ready('mixed_plan')
-        return BatchMixedPlan(self, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, codes, apply, costs)
+        return BatchMixedPlan(self, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, codes, apply, costs, clip, alpha_min)
 
     def nsr_plan(self, widths=(2, 3, 4, 6, 8), per_channel=False, signed=False, moment='variance', input_moment=1.0):
         """One plan (BatchNsrPlan) for the data-free sensitivities ``mixed_plan(costs=)`` allocates on: for every ``targ_type``
@@ -510,7 +520,8 @@ class NetworkBatch:
         return BatchNsrPlan(self, widths, per_channel, signed, moment, input_moment)
 
     def quantize_mixed(self, widths=(2, 3, 4, 6, 8), avg_bits=None, budget_bits=None, per_channel=False, signed=False, sensitivity=None,
-                       pin=None, codes='int32', bits_bias=16, correct=False, cost='mse', moment='variance', input_moment=1.0):
+                       pin=None, codes='int32', bits_bias=16, correct=False, cost='mse', moment='variance', input_moment=1.0,
+                       clip=None, alpha_min=0.5):
         """mixed_plan for the weights, the nearest rounding of ``quantize`` for the biases (unless ``bits_bias >= 32``), run +
         synchronise: returns (codes, ranges, bits), each a list of one dict per network -- the biases' ranges under
         key + '.bias', every bias bit for bit what ``quantize`` stores, ``bits[n][key]`` the width network n's layer got.
@@ -524,7 +535,15 @@ class NetworkBatch:
 
         ``cost='nsr'`` allocates on ``nsr_plan(widths, per_channel, signed, moment, input_moment)``, created and run first.  With
         ``correct`` the order is nsr -> allocation -> correction -> applying plan on the SAME cost block: the correction moves
-        beta~ of later BatchNorms, so the costs are not computed again."""
+        beta~ of later BatchNorms, so the costs are not computed again.
+
+        ``clip=K`` (``alpha_min``): ONE clip-aware plan (``mixed_plan(clip=K, alpha_min=)``) in place of the plans above.  Without
+        ``correct`` it is run, then the biases as above.  With ``correct`` its stages are run one by one: ALLOCATE, CLAMP,
+        ``bc_plan().run(widths=that plan)`` -- which reads the widths on the device and sees the clamped weights, as the
+        correction behind ``clip_weight`` always has --, QUANTISE, then the biases after their correction; no second
+        allocation is run (it would see clamped weights and could differ).  With ``cost='nsr'`` the nsr plan runs first, on the
+        unclamped weights, and the allocation walks on it; the ranges are still the sum-e^2-optimal ones.  ``clip=None`` is
+        the code path above, unchanged."""
         self._ready('quantize_mixed')
         if cost not in ('mse', 'nsr'):
             raise ValueError("quantize_mixed: cost must be 'mse' or 'nsr', got {!r}".format(cost))
@@ -537,6 +556,32 @@ class NetworkBatch:
                 nsr = BatchNsrPlan(self, widths, per_channel, signed, moment, input_moment)
                 first.append(nsr)
                 nsr.run()
+            if clip is not None:
+                plans.append(BatchMixedPlan(self, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, codes, True, nsr,
+                                            clip, alpha_min))
+                if bits_bias < 32 and any(type(l) in tt and l.bias is not None for l in g0.values()):
+                    plans.append(BatchQuantPlan(self, plans[0].widths[-1], bits_bias, per_channel, signed, None, _biases_only=True))
+                if correct:
+                    first.append(self.bc_plan())
+                    plans[0].run(BatchMixedPlan.ALLOCATE | BatchMixedPlan.CLAMP)
+                    first[-1].run(signed=signed, per_channel=per_channel, widths=plans[0])
+                    plans[0].run(BatchMixedPlan.QUANTISE)
+                else:
+                    plans[0].run()
+                for plan in plans[1:]:
+                    plan.run()
+                if correct:
+                    first[-1].status()
+                _ffi.synchronize()
+                n = len(self.nets)
+                ranges = []
+                for i in range(n):
+                    r = {}
+                    for plan in plans:
+                        r.update({k: v.clone() for k, v in plan.ranges(i).items()})
+                    ranges.append(r)
+                return ([{k: v.clone() for k, v in plans[0].codes(i).items()} for i in range(n)], ranges,
+                        [dict(plans[0].bits(i)) for i in range(n)])
             if correct:
                 first += [BatchMixedPlan(self, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, None, False, nsr),
                           self.bc_plan()]
@@ -1088,10 +1133,15 @@ class BatchMixedPlan(_BatchPlan):
     [n_nets, T, B], ``used_block`` int64 [n_nets, 2] = (used bits, steps), ``cost_block`` float64 [n_nets], ``range_block``
     and, with ``codes``, ``code_block``.  ``widths``, ``budget`` (bits per network) and ``elements`` (weights per network) are
     what the plan was made with.  Two runs of a plan without ``apply`` give bit-equal blocks, and a network's part does not
-    depend on the others."""
+    depend on the others.  With ``clip=K`` the plan is the clip-aware one (dfq_batch_mixed_plan_create_clipped): the range
+    search at every width in front of the allocation, the clamp in front of the quantisation, and the blocks
+    ``clip_range_block``, ``clip_chosen_block`` and ``unit_error_block`` (None otherwise); ``run(stages)`` runs the stages of
+    either kind of plan one by one."""
     _c = 'dfq_batch_mixed_plan'
+    ALLOCATE, CLAMP, QUANTISE = _ffi.MIXED_ALLOCATE, _ffi.MIXED_CLAMP, _ffi.MIXED_QUANTISE
 
-    def __init__(self, batch, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, codes, apply, costs=None):
+    def __init__(self, batch, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, codes, apply, costs=None, clip=None,
+                 alpha_min=0.5):
         g0 = batch.nets[0][0]
         tt = tuple(batch.targ_type)
         layers = [(key, layer.weight) for key, layer in g0.items() if type(layer) in tt]
@@ -1108,16 +1158,23 @@ class BatchMixedPlan(_BatchPlan):
                 raise ValueError('mixed_plan: costs were made for widths {!r}, per_channel {}, signed {}; the plan asks for {!r}, {}, {}'.format(
                     costs.widths, costs.per_channel, costs.signed, widths, bool(per_channel), bool(signed)))
         lay = _dfq._MixedLayout('mixed_plan', layers, lambda key, w: batch._in_slot(key, 'weight', w), len(batch.nets), widths,
-                                avg_bits, budget_bits, per_channel, signed, sensitivity, pin, codes, apply, batch.stage.device)
+                                avg_bits, budget_bits, per_channel, signed, sensitivity, pin, codes, apply, batch.stage.device, clip, alpha_min)
         super().__init__(batch)
         self._lay = lay
+        self.clip, self.alpha_min = lay.clip, lay.alpha_min
+        self.clip_range_block, self.clip_chosen_block, self.unit_error_block = lay.clip_range_block, lay.clip_chosen_block, lay.unit_error_block
         self.widths, self.budget, self.elements = lay.widths, lay.budget, lay.total
         self.per_channel, self.signed, self.apply = lay.per_channel, lay.signed, lay.apply
         self.keys, self.n_nets, self.n_tensors = lay.keys, lay.n_nets, lay.n_tensors
         self.code_dtype = lay.code_dtype
         self.bits_block, self.error_block, self.used_block, self.cost_block = lay.bits_block, lay.error_block, lay.used_block, lay.cost_block
         self.range_block, self.code_block = lay.range_block, lay.code_block
-        self._create(lay.tables(), *lay.block_args())
+        if lay.clip is None:
+            self._create(lay.tables(), *lay.block_args())
+        else:
+            self._plan = ctypes.c_void_p()
+            _ffi.check(lay.create(_ffi.lib(), batch.bases.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)), len(batch.nets), self._plan))
+            self.launches = int(_ffi.lib().dfq_batch_mixed_plan_launches(self._plan))
         self._costs = None
         if costs is not None:
             self.set_costs(costs)
@@ -1130,6 +1187,43 @@ class BatchMixedPlan(_BatchPlan):
         block = None if costs is None else costs.cost_block
         _ffi.check(_ffi.lib().dfq_batch_mixed_plan_set_costs(self._plan, None if block is None else block.data_ptr()))
         self._costs = block                        # (kept alive while the plan reads it)
+
+    def run(self, stages=None):
+        """Enqueue the plan on the current stream.  ``stages=None``: the whole plan (the allocation and, with ``apply``, the
+        quantisation).  Else a sum of ``BatchMixedPlan.ALLOCATE``, ``CLAMP`` (plans made with ``clip=``) and ``QUANTISE``
+        (dfq_batch_mixed_plan_run_stages, include/dfq_hip.h): CLAMP and QUANTISE work at the widths the plan's last ALLOCATE
+        left in the plan's own state, whatever ``apply`` says."""
+        if stages is None:
+            return super().run()
+        if self._batch.storage is None:
+            raise RuntimeError('NetworkBatch: the batch has been released')
+        if not self._plan:
+            raise RuntimeError('BatchMixedPlan: the plan has been closed')
+        _ffi.check(_ffi.lib().dfq_batch_mixed_plan_run_stages(self._plan, int(stages), _ffi.stream_arg()))
+
+    def allocate(self):
+        """``run(ALLOCATE)``: ranges, errors, allocation"""
+        self.run(self.ALLOCATE)
+
+    def clamp(self):
+        """``run(CLAMP)``: every unit clamped to the range of its layer's chosen width (plans made with ``clip=``)"""
+        self.run(self.CLAMP)
+
+    def quantise(self):
+        """``run(QUANTISE)``: clamp and quantise at the chosen widths"""
+        self.run(self.QUANTISE)
+
+    def clip_ranges(self, n):
+        """{graph key: float32 [B, 2] (or [O, B, 2] per channel) view}: (l, h) of k* at every width; plans made with ``clip=``"""
+        return self._lay.clip_ranges(n)
+
+    def clip_chosen(self, n):
+        """{graph key: int32 [B] (or [O, B]) view}: k* at every width (0 is the unit's own (min, max))"""
+        return self._lay.clip_chosen(n)
+
+    def unit_errors(self, n):
+        """{graph key: float64 [B] (or [O, B]) view}: sum e^2 of the unit under k* at every width"""
+        return self._lay.unit_errors(n)
 
     def bits(self, n):
         """``OrderedDict[graph key -> int]``: the width network n's weight got (one device-to-host copy)"""

@@ -29,6 +29,9 @@
 // are bit-identical, and network n's values depend on nothing but its weights.  NaN is skipped by every range (range_fold,
 // dfq_range.hpp); an element that is NaN has e = NaN, so a tensor holding one gets NaN errors, in its own slots only, and
 // takes no step (g > 0 is false).
+// A CLIPPED plan (dfq_batch_mixed_plan_create_clipped) is the same plan object with other launches in front of and behind
+// bm_alloc_kernel, which it uses as it is: dfq_mixed_clip.hpp, included below, holds them and says how they are cut.  The stages
+// (dfq_batch_mixed_plan_run_stages) of a plan without clipping are the launches above plus bm_state_kernel of that header.
 #include <limits.h>
 #include <math.h>
 
@@ -455,24 +458,29 @@ inline int bm_class(int len) {
 
 }  // namespace dfq
 
+#include "dfq_mixed_clip.hpp"      // the kernels of a clipped plan and of the stages (this file alone includes it)
+
 using namespace dfq;
 
 struct dfq_batch_mixed_plan {
     DevSlab mem;
     BmArgs args{};
     int n_nets = 0, apply = 0, launches = 0;
+    int32_t* state = nullptr;     // [n_nets, n_tensors]: the index j_t the last ALLOCATE stage left
+    bool allocated = false;       // an ALLOCATE stage has run since creation
+    bool clipped = false;
+    BxArgs cx{};                  // a clipped plan's own arguments
+    size_t word_bytes = 0;
+    int row_blocks = 0, piece_blocks = 0, fold_blocks = 0, finish_blocks = 0;
 };
 
-extern "C" {
+namespace {
 
-int32_t dfq_batch_mixed_plan_launches(const dfq_batch_mixed_plan* p) { return p ? p->launches : 0; }
-
-void dfq_batch_mixed_plan_destroy(dfq_batch_mixed_plan* p) { batch_plan_destroy(p); }
-
-int dfq_batch_mixed_plan_create(const dfq_batch_mixed_tensor* tensors, int32_t n_tensors, const dfq_batch_mixed_config* config,
-                                const void* const* bases, int32_t n_nets, int32_t* bits, double* errors, int64_t* used, double* cost,
-                                void* codes, int64_t code_stride, float* ranges, int64_t range_stride, dfq_batch_mixed_plan** out_plan) {
-    const char* me = "dfq_batch_mixed_plan_create";
+// what both entry points refuse and build; `clip` null: dfq_batch_mixed_plan_create, as it always was
+int bm_create(const char* me, const dfq_batch_mixed_tensor* tensors, int32_t n_tensors, const dfq_batch_mixed_config* config,
+              const void* const* bases, int32_t n_nets, int32_t* bits, double* errors, int64_t* used, double* cost, void* codes,
+              int64_t code_stride, float* ranges, int64_t range_stride, const dfq_batch_mixed_clip* clip, bool clipped,
+              dfq_batch_mixed_plan** out_plan) {
     if (!out_plan) return fail_arg("%s: no place for the plan", me);
     if (!tensors || n_tensors <= 0) return fail_arg("%s: the tensor table is null or empty (n_tensors %d)", me, (int)n_tensors);
     if (!config) return fail_arg("%s: no configuration", me);
@@ -495,12 +503,29 @@ int dfq_batch_mixed_plan_create(const dfq_batch_mixed_tensor* tensors, int32_t n
     if (!bits || !errors || !used || !cost) return fail_arg("%s: a null output block (bits, errors, used, cost)", me);
     if (code_stride < 0 || range_stride < 0) return fail_arg("%s: negative stride", me);
     const int per_row = cfg.per_row ? 1 : 0;
+    int K = 0;
+    if (clipped) {
+        if (!clip) return fail_arg("%s: no clip description", me);
+        K = clip->candidates;
+        if (K < 1 || K > kMxMaxCand) return fail_arg("%s: %d candidates (1..%d)", me, K, kMxMaxCand);
+        if (!(clip->alpha_min > 0.0 && clip->alpha_min <= 1.0)) return fail_arg("%s: alpha_min %g is not in (0, 1]", me, clip->alpha_min);
+        if (nb * K > kMxMaxPairs) return fail_arg("%s: %d widths x %d candidates, at most %d pairs", me, nb, K, kMxMaxPairs);
+        if (!clip->clip_ranges || !clip->clip_chosen) return fail_arg("%s: the block of the clip ranges or of the choices is null", me);
+        if (!clip->unit_offsets) return fail_arg("%s: no unit offsets", me);
+        if (clip->unit_stride <= 0) return fail_arg("%s: unit stride %lld", me, (long long)clip->unit_stride);
+        if (clip->unit_stride > INT64_MAX / 16 / nb / n_nets)
+            return fail_arg("%s: blocks of %d x %lld units", me, (int)n_nets, (long long)clip->unit_stride);
+    }
 
     std::vector<BmRowDev> rows;
     std::vector<BmChunkDev> chunks;
     std::vector<BmAllocDev> alloc;
     std::vector<int32_t> wave_tensor, chunk_tensor;
-    int64_t waves = 0, nchunks = 0, total = 0;
+    std::vector<BxRowDev> xrows;
+    std::vector<BxFlatDev> xflats;
+    std::vector<BxTensorDev> xtensors;
+    std::vector<int32_t> piece_tensor, part_tensor;
+    int64_t waves = 0, nchunks = 0, total = 0, parts = 0;
     for (int i = 0; i < n_tensors; ++i) {
         const dfq_batch_mixed_tensor& t = tensors[i];
         if (!t.data) return fail_arg("%s: tensor %d: null weight", me, i);
@@ -529,7 +554,42 @@ int dfq_batch_mixed_plan_create(const dfq_batch_mixed_tensor* tensors, int32_t n
             if (t.range_offset > range_stride - 2 * (per_row ? t.rows : 1)) return fail_arg("%s: tensor %d: ranges overflow the range stride", me, i);
         }
         BmAllocDev A{numel, t.sensitivity, 0, 0, fixed, 0};
-        if (!per_row && numel > kMixRegElems) {
+        if (clipped) {                                 // the clip plan's cut: a unit is a part of the allocation's fold
+            const int64_t units = per_row ? t.rows : 1, uo = clip->unit_offsets[i];
+            if (t.rows > 0x7fffffff - kWave || t.row_len > 0x7fffffff - 2 * kBatchPiece || t.rows > (0x7fffffff - 2 * kBatchPiece) / t.row_len)
+                return fail_arg("%s: tensor %d: a shape of [%lld, %lld]", me, i, (long long)t.rows, (long long)t.row_len);
+            if (uo < 0 || uo > clip->unit_stride - units)
+                return fail_arg("%s: tensor %d: %lld units at %lld lie outside the unit stride %lld", me, i, (long long)units, (long long)uo,
+                                (long long)clip->unit_stride);
+            if ((parts + units) * n_nets > 0x7fffffff / 2 / nb) return fail_arg("%s: too much work for one launch", me);
+            A.part_begin = (int32_t)parts;
+            A.n_parts = (int32_t)units;
+            xtensors.push_back(BxTensorDev{uo, t.range_offset, (int32_t)parts, 0});
+            part_tensor.insert(part_tensor.end(), (size_t)units, (int32_t)i);
+            if (!per_row && numel > kMixRegElems) {
+                BxFlatDev f{t.data, numel, uo, t.code_offset, t.range_offset, (int32_t)numel, 0, 0, (int32_t)xflats.size(), i, (int32_t)parts};
+                const int64_t begin = batch_add_pieces(piece_tensor, (int32_t)xflats.size(), numel, 0x7fffffff / n_nets / (nb * K));
+                if (begin < 0) return fail_arg("%s: too much work for one launch", me);
+                f.piece_begin = (int32_t)begin;
+                f.n_pieces = (int32_t)((int64_t)piece_tensor.size() - begin);
+                xflats.push_back(f);
+            } else {
+                BxRowDev r;
+                r.data = t.data; r.unit_off = uo; r.code_off = t.code_offset; r.range_off = t.range_offset;
+                r.rows = (int32_t)units;
+                r.len = (int32_t)(per_row ? t.row_len : numel);
+                r.cls = bm_class(r.len);
+                r.wave_begin = (int32_t)waves;
+                r.tensor = i; r.part_begin = (int32_t)parts;
+                const int64_t per_wave = r.cls == 5 || r.cls == 0 ? 1 : kWave / (2 << r.cls) * kMixGroupRows;
+                const int64_t w = (r.rows + per_wave - 1) / per_wave;
+                if ((waves + w) * n_nets > 0x7fffffff - kBlock) return fail_arg("%s: too much work for one launch", me);
+                wave_tensor.insert(wave_tensor.end(), (size_t)w, (int32_t)xrows.size());
+                xrows.push_back(r);
+                waves += w;
+            }
+            parts += units;
+        } else if (!per_row && numel > kMixRegElems) {
             BmChunkDev c;
             c.data = t.data; c.code_off = t.code_offset; c.range_off = t.range_offset; c.n = numel;
             c.chunk_begin = (int32_t)nchunks;
@@ -561,13 +621,17 @@ int dfq_batch_mixed_plan_create(const dfq_batch_mixed_tensor* tensors, int32_t n
             rows.push_back(r);
             waves += w;
         }
-        if ((waves + nchunks) * n_nets > 0x7fffffff / 2 / nb) return fail_arg("%s: too much work for one launch", me);
+        if (!clipped && (waves + nchunks) * n_nets > 0x7fffffff / 2 / nb) return fail_arg("%s: too much work for one launch", me);
         alloc.push_back(A);
     }
-    for (BmAllocDev& A : alloc)
-        if (A.part_begin < 0) A.part_begin = (int32_t)(waves + (-1 - A.part_begin));
+    if (!clipped) {
+        for (BmAllocDev& A : alloc)
+            if (A.part_begin < 0) A.part_begin = (int32_t)(waves + (-1 - A.part_begin));
+        parts = waves + nchunks;
+    }
     const int64_t row_blocks = (waves * n_nets + kBlock / kWave - 1) / (kBlock / kWave);
     if (row_blocks + nchunks * n_nets > 0x7fffffff) return fail_arg("%s: too much work for one launch", me);
+    if (clipped && (int64_t)xflats.size() * n_nets > 0x7fffffff) return fail_arg("%s: too much work for one launch", me);
 
     dfq_batch_mixed_plan* p = new dfq_batch_mixed_plan();
     BmArgs& a = p->args;
@@ -590,13 +654,13 @@ int dfq_batch_mixed_plan_create(const dfq_batch_mixed_tensor* tensors, int32_t n
     a.chunks_pn = (int32_t)nchunks;
     a.chunk_blocks = (int32_t)(nchunks * n_nets);
     a.chunk_tensors = (int32_t)chunks.size();
-    a.parts_pn = (int32_t)(waves + nchunks);
+    a.parts_pn = (int32_t)parts;
     p->n_nets = n_nets;
     p->apply = cfg.apply ? 1 : 0;
-    p->launches = (chunks.empty() ? 0 : 1) + 2 + p->apply;
+    p->clipped = clipped;
     BatchUpload up{p->mem};
     a.rows = up.put(rows);
-    a.wave_tensor = up.put(wave_tensor);
+    if (!clipped) a.wave_tensor = up.put(wave_tensor);
     a.chunks = up.put(chunks);
     a.chunk_tensor = up.put(chunk_tensor);
     a.alloc = up.put(alloc);
@@ -604,12 +668,157 @@ int dfq_batch_mixed_plan_create(const dfq_batch_mixed_tensor* tensors, int32_t n
     a.delta = up.put(batch_delta(bases, n_nets));
     a.slots = (uint32_t*)up.raw(nullptr, sizeof(uint32_t) * 2 * (size_t)a.chunk_tensors * n_nets);
     a.partial = (double*)up.raw(nullptr, sizeof(double) * (size_t)a.parts_pn * (size_t)n_nets * (size_t)nb);
+    p->state = (int32_t*)up.raw(nullptr, sizeof(int32_t) * (size_t)n_tensors * (size_t)n_nets);
+    if (!clipped) {
+        p->launches = (chunks.empty() ? 0 : 1) + 2 + p->apply;
+    } else {
+        BxArgs& x = p->cx;
+        const int64_t pieces = (int64_t)piece_tensor.size();
+        std::vector<double> alpha(K);
+        for (int k = 0; k < K; ++k) alpha[k] = K == 1 ? 1.0 : 1.0 - (double)k * (1.0 - clip->alpha_min) / (double)(K - 1);
+        x.rows = up.put(xrows);
+        x.wave_tensor = up.put(wave_tensor);
+        x.flats = up.put(xflats);
+        x.piece_tensor = up.put(piece_tensor);
+        x.tensors = up.put(xtensors);
+        x.part_tensor = up.put(part_tensor);
+        x.width_tab = a.width_tab;
+        x.delta = a.delta;
+        x.alpha = up.put(alpha);
+        p->word_bytes = sizeof(uint32_t) * 2 * xflats.size() * (size_t)n_nets;
+        x.words = (uint32_t*)up.raw(nullptr, p->word_bytes);
+        x.scratch = (double*)up.raw(nullptr, sizeof(double) * (size_t)pieces * (size_t)n_nets * (size_t)(nb * K));
+        x.partial = a.partial;
+        x.clip_ranges = clip->clip_ranges;
+        x.clip_chosen = clip->clip_chosen;
+        x.unit_errors = clip->unit_errors;
+        x.bits = bits;
+        x.state = p->state;
+        x.codes = (unsigned char*)codes;
+        x.ranges = ranges;
+        x.code_stride = code_stride;
+        x.range_stride = range_stride;
+        x.unit_stride = clip->unit_stride;
+        x.n_widths = nb;
+        x.symmetric = a.symmetric;
+        x.code_bytes = cfg.code_bytes;
+        x.n_tensors = n_tensors;
+        x.K = K;
+        x.row_wpn = (int32_t)waves;
+        x.row_waves = (int32_t)(waves * n_nets);
+        x.pieces_pn = (int32_t)pieces;
+        x.n_flats = (int32_t)xflats.size();
+        x.parts_pn = (int32_t)parts;
+        x.n_nets = n_nets;
+        p->row_blocks = (int)row_blocks;
+        p->piece_blocks = (int)(pieces * n_nets);
+        p->fold_blocks = (int)((int64_t)xflats.size() * n_nets);
+        p->finish_blocks = (int)((parts * n_nets + kBlock - 1) / kBlock);
+        p->launches = (p->piece_blocks ? 3 : 0) + (p->row_blocks ? 1 : 0) + 2 + p->apply * ((p->piece_blocks ? 1 : 0) + (p->row_blocks ? 1 : 0));
+    }
     if (up.err != hipSuccess) {
         batch_plan_destroy(p);
         return fail_hip(up.err, "batch mixed plan allocation", __FILE__, __LINE__);
     }
     *out_plan = p;
     return DFQ_OK;
+}
+
+// ranges, errors, allocation; the plan's state with `keep`
+int bm_allocate(dfq_batch_mixed_plan* p, hipStream_t st, bool keep) {
+    const BmArgs& a = p->args;
+    if (p->clipped) {
+        const BxArgs& x = p->cx;
+        if (p->piece_blocks > 0) {
+            DFQ_HIP_TRY(hipMemsetAsync(x.words, 0, p->word_bytes, st));
+            hipLaunchKernelGGL(bx_range_kernel, dim3(p->piece_blocks), dim3(kBlock), 0, st, x);
+            DFQ_CHECK_LAUNCH();
+            hipLaunchKernelGGL(bx_search_kernel, dim3(p->piece_blocks), dim3(kBlock), 0, st, x);
+            DFQ_CHECK_LAUNCH();
+            hipLaunchKernelGGL(bx_fold_kernel, dim3(p->fold_blocks), dim3(kWave), 0, st, x);
+            DFQ_CHECK_LAUNCH();
+        }
+        if (p->row_blocks > 0) {
+            hipLaunchKernelGGL(bx_row_kernel, dim3(p->row_blocks), dim3(kBlock), 0, st, x);
+            DFQ_CHECK_LAUNCH();
+        }
+        hipLaunchKernelGGL(bm_alloc_kernel, dim3(p->n_nets), dim3(kBlock), 0, st, a);
+        DFQ_CHECK_LAUNCH();
+        hipLaunchKernelGGL(bx_finish_kernel, dim3(p->finish_blocks), dim3(kBlock), 0, st, x);
+        DFQ_CHECK_LAUNCH();
+        p->allocated = true;
+        return DFQ_OK;
+    }
+    if (a.chunk_blocks > 0) {
+        DFQ_HIP_TRY(hipMemsetAsync(a.slots, 0, sizeof(uint32_t) * 2 * (size_t)a.chunk_tensors * (size_t)p->n_nets, st));
+        hipLaunchKernelGGL(bm_chunk_minmax_kernel, dim3(a.chunk_blocks), dim3(kBlock), 0, st, a);
+        DFQ_CHECK_LAUNCH();
+    }
+    const int blocks = a.chunk_blocks + (a.row_waves + kBlock / kWave - 1) / (kBlock / kWave);
+    hipLaunchKernelGGL(bm_error_kernel, dim3(blocks), dim3(kBlock), 0, st, a);
+    DFQ_CHECK_LAUNCH();
+    hipLaunchKernelGGL(bm_alloc_kernel, dim3(p->n_nets), dim3(kBlock), 0, st, a);
+    DFQ_CHECK_LAUNCH();
+    if (keep) {
+        const int64_t n = (int64_t)p->n_nets * a.n_tensors;
+        hipLaunchKernelGGL(bm_state_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a.width_tab, a.n_widths, a.bits, p->state,
+                           n, 0);
+        DFQ_CHECK_LAUNCH();
+        p->allocated = true;
+    }
+    return DFQ_OK;
+}
+
+// clamp (clipped plans), or clamp and quantise, at the widths of the plan's state
+int bm_apply(dfq_batch_mixed_plan* p, hipStream_t st, bool quantise, bool restore) {
+    const BmArgs& a = p->args;
+    if (p->clipped) {
+        const BxArgs& x = p->cx;
+        if (p->piece_blocks > 0) {
+            if (quantise) hipLaunchKernelGGL(bx_quant_flat_kernel, dim3(p->piece_blocks), dim3(kBlock), 0, st, x);
+            else hipLaunchKernelGGL(bx_clamp_flat_kernel, dim3(p->piece_blocks), dim3(kBlock), 0, st, x);
+            DFQ_CHECK_LAUNCH();
+        }
+        if (p->row_blocks > 0) {
+            if (quantise) hipLaunchKernelGGL(bx_quant_kernel, dim3(p->row_blocks), dim3(kBlock), 0, st, x);
+            else hipLaunchKernelGGL(bx_clamp_kernel, dim3(p->row_blocks), dim3(kBlock), 0, st, x);
+            DFQ_CHECK_LAUNCH();
+        }
+        return DFQ_OK;
+    }
+    if (restore) {
+        const int64_t n = (int64_t)p->n_nets * a.n_tensors;
+        hipLaunchKernelGGL(bm_state_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a.width_tab, a.n_widths, a.bits, p->state,
+                           n, 1);
+        DFQ_CHECK_LAUNCH();
+    }
+    const int blocks = a.chunk_blocks + (a.row_waves + kBlock / kWave - 1) / (kBlock / kWave);
+    hipLaunchKernelGGL(bm_quant_kernel, dim3(blocks), dim3(kBlock), 0, st, a);
+    DFQ_CHECK_LAUNCH();
+    return DFQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t dfq_batch_mixed_plan_launches(const dfq_batch_mixed_plan* p) { return p ? p->launches : 0; }
+
+void dfq_batch_mixed_plan_destroy(dfq_batch_mixed_plan* p) { batch_plan_destroy(p); }
+
+int dfq_batch_mixed_plan_create(const dfq_batch_mixed_tensor* tensors, int32_t n_tensors, const dfq_batch_mixed_config* config,
+                                const void* const* bases, int32_t n_nets, int32_t* bits, double* errors, int64_t* used, double* cost,
+                                void* codes, int64_t code_stride, float* ranges, int64_t range_stride, dfq_batch_mixed_plan** out_plan) {
+    return bm_create("dfq_batch_mixed_plan_create", tensors, n_tensors, config, bases, n_nets, bits, errors, used, cost, codes, code_stride,
+                     ranges, range_stride, nullptr, false, out_plan);
+}
+
+int dfq_batch_mixed_plan_create_clipped(const dfq_batch_mixed_tensor* tensors, int32_t n_tensors, const dfq_batch_mixed_config* config,
+                                        const void* const* bases, int32_t n_nets, int32_t* bits, double* errors, int64_t* used, double* cost,
+                                        void* codes, int64_t code_stride, float* ranges, int64_t range_stride,
+                                        const dfq_batch_mixed_clip* clip, dfq_batch_mixed_plan** out_plan) {
+    return bm_create("dfq_batch_mixed_plan_create_clipped", tensors, n_tensors, config, bases, n_nets, bits, errors, used, cost, codes,
+                     code_stride, ranges, range_stride, clip, true, out_plan);
 }
 
 int dfq_batch_mixed_plan_set_costs(dfq_batch_mixed_plan* p, const double* costs) {
@@ -621,21 +830,27 @@ int dfq_batch_mixed_plan_set_costs(dfq_batch_mixed_plan* p, const double* costs)
 int dfq_batch_mixed_plan_run(dfq_batch_mixed_plan* p, void* stream) {
     if (!p) return fail_arg("dfq_batch_mixed_plan_run: null plan");
     hipStream_t st = as_stream(stream);
-    const BmArgs& a = p->args;
-    if (a.chunk_blocks > 0) {
-        DFQ_HIP_TRY(hipMemsetAsync(a.slots, 0, sizeof(uint32_t) * 2 * (size_t)a.chunk_tensors * (size_t)p->n_nets, st));
-        hipLaunchKernelGGL(bm_chunk_minmax_kernel, dim3(a.chunk_blocks), dim3(kBlock), 0, st, a);
-        DFQ_CHECK_LAUNCH();
+    if (const int rc = bm_allocate(p, st, false)) return rc;       // (a plan without clipping: its launches as they always were)
+    return p->apply ? bm_apply(p, st, true, false) : DFQ_OK;
+}
+
+int dfq_batch_mixed_plan_run_stages(dfq_batch_mixed_plan* p, int32_t stages, void* stream) {
+    const char* me = "dfq_batch_mixed_plan_run_stages";
+    if (!p) return fail_arg("%s: null plan", me);
+    const int all = DFQ_MIXED_ALLOCATE | DFQ_MIXED_CLAMP | DFQ_MIXED_QUANTISE;
+    if (stages == 0 || (stages & ~all) != 0) return fail_arg("%s: stages %d (a sum of 1, 2 and 4)", me, (int)stages);
+    if ((stages & DFQ_MIXED_CLAMP) && !p->clipped) return fail_arg("%s: the clamp stage needs a clipped plan", me);
+    if ((stages & (DFQ_MIXED_CLAMP | DFQ_MIXED_QUANTISE)) && !(stages & DFQ_MIXED_ALLOCATE) && !p->allocated) {
+        set_error(std::string(me) + ": no allocation stage has run on this plan");
+        return DFQ_ERR_STATE;
     }
-    const int blocks = a.chunk_blocks + (a.row_waves + kBlock / kWave - 1) / (kBlock / kWave);
-    hipLaunchKernelGGL(bm_error_kernel, dim3(blocks), dim3(kBlock), 0, st, a);
-    DFQ_CHECK_LAUNCH();
-    hipLaunchKernelGGL(bm_alloc_kernel, dim3(p->n_nets), dim3(kBlock), 0, st, a);
-    DFQ_CHECK_LAUNCH();
-    if (p->apply) {
-        hipLaunchKernelGGL(bm_quant_kernel, dim3(blocks), dim3(kBlock), 0, st, a);
-        DFQ_CHECK_LAUNCH();
-    }
+    hipStream_t st = as_stream(stream);
+    if (stages & DFQ_MIXED_ALLOCATE)
+        if (const int rc = bm_allocate(p, st, true)) return rc;
+    if (stages & DFQ_MIXED_CLAMP)
+        if (const int rc = bm_apply(p, st, false, false)) return rc;
+    if (stages & DFQ_MIXED_QUANTISE)
+        if (const int rc = bm_apply(p, st, true, true)) return rc;
     return DFQ_OK;
 }
 

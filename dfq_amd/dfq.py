@@ -1265,6 +1265,7 @@ def clip_weight_mse(graph, bits_weight=8, per_channel=False, signed=False, candi
 # extension: a bit width per layer under a size budget (dfq_batch_mixed_plan, include/dfq_hip.h)
 # ------------------------------------------------------------------------------------------------
 _MIXED_ENTRIES = 4096            # T * B the allocation's table holds
+_MIXED_PAIRS = 512               # B * K a clipped plan searches
 
 
 class _MixedLayout:
@@ -1275,7 +1276,7 @@ class _MixedLayout:
     [n_nets, range_stride] and, with ``codes``, ``code_block``."""
 
     def __init__(self, who, layers, address, n_nets, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, codes,
-                 apply, device):
+                 apply, device, clip=None, alpha_min=0.5):
         import math
         import numbers
         from fractions import Fraction
@@ -1312,6 +1313,13 @@ class _MixedLayout:
             raise ValueError("{}: codes must be None, 'int32' or 'int8', got {!r}".format(who, codes))
         if codes == 'int8' and widths[-1] > 8:
             raise ValueError('{}: 1-byte codes need widths <= 8, got {!r}'.format(who, widths))
+        if clip is not None:
+            if isinstance(clip, bool) or not isinstance(clip, ints) or not 1 <= clip <= 64:
+                raise ValueError('{}: clip must be None or an int in [1, 64] (the candidates), got {!r}'.format(who, clip))
+            if isinstance(alpha_min, bool) or not isinstance(alpha_min, numbers.Real) or not 0.0 < float(alpha_min) <= 1.0:
+                raise ValueError('{}: alpha_min must be a number in (0, 1], got {!r}'.format(who, alpha_min))
+            if len(widths) * clip > _MIXED_PAIRS:
+                raise ValueError('{}: {} widths x {} candidates, at most {} pairs'.format(who, len(widths), clip, _MIXED_PAIRS))
         keys = [key for key, _ in layers]
         sensitivity, pin = dict(sensitivity or {}), dict(pin or {})
         for name, table in (('sensitivity', sensitivity), ('pin', pin)):
@@ -1327,10 +1335,12 @@ class _MixedLayout:
         self.widths, self.budget, self.total = widths, budget, total
         self.per_channel, self.signed, self.apply = bool(per_channel), bool(signed), bool(apply)
         self.keys, self.n_nets, self.n_tensors = keys, n_nets, len(layers)
-        entries, self._code_views, self._range_views = [], [], []
-        code_stride = range_stride = 0
+        entries, self._code_views, self._range_views, self._unit_views = [], [], [], []
+        code_stride = range_stride = unit_stride = 0
         for key, w in layers:
             rows = int(w.shape[0])
+            self._unit_views.append((key, unit_stride, rows if self.per_channel else 1))
+            unit_stride += rows if self.per_channel else 1
             c_off = -1
             if codes is not None:
                 c_off = code_stride
@@ -1352,6 +1362,42 @@ class _MixedLayout:
         self.error_block = torch.zeros((n_nets, len(entries), len(widths)), dtype=torch.float64, device=device)
         self.used_block = torch.zeros((n_nets, 2), dtype=torch.int64, device=device)
         self.cost_block = torch.zeros((n_nets,), dtype=torch.float64, device=device)
+        self.clip = None if clip is None else int(clip)
+        self.alpha_min = None if clip is None else float(alpha_min)
+        self.clip_range_block = self.clip_chosen_block = self.unit_error_block = self.clip_desc = None
+        if clip is not None:
+            B = len(widths)
+            self.unit_stride = unit_stride
+            self.clip_range_block = torch.zeros((n_nets, unit_stride, B, 2), dtype=torch.float32, device=device)
+            self.clip_chosen_block = torch.zeros((n_nets, unit_stride, B), dtype=torch.int32, device=device)
+            self.unit_error_block = torch.zeros((n_nets, unit_stride, B), dtype=torch.float64, device=device)
+            self._unit_offsets = (ctypes.c_int64 * len(entries))(*[off for _, off, _ in self._unit_views])
+            self.clip_desc = _ffi.DfqBatchMixedClip(self.clip, 0, self.alpha_min, self.clip_range_block.data_ptr(),
+                                                    self.clip_chosen_block.data_ptr(), self.unit_error_block.data_ptr(), unit_stride,
+                                                    self._unit_offsets)
+
+    def create(self, lib, bases, n_nets, plan):
+        """the plan through today's entry point, or through dfq_batch_mixed_plan_create_clipped with ``clip``; returns the status"""
+        if self.clip is None:
+            return lib.dfq_batch_mixed_plan_create(*self.tables(), bases, n_nets, *self.block_args(), ctypes.byref(plan))
+        return lib.dfq_batch_mixed_plan_create_clipped(*self.tables(), bases, n_nets, *self.block_args(), ctypes.byref(self.clip_desc),
+                                                       ctypes.byref(plan))
+
+    def _units(self, block, n):
+        """{graph key: view [B, ...] of the tensor's unit, or [O, B, ...] of its rows} of network n's part of a clip block"""
+        if block is None:
+            raise RuntimeError('mixed_plan: the plan was made without clip=')
+        row = block[n]
+        return OrderedDict((key, row[off:off + units] if self.per_channel else row[off]) for (key, off, units) in self._unit_views)
+
+    def clip_ranges(self, n):
+        return self._units(self.clip_range_block, n)
+
+    def clip_chosen(self, n):
+        return self._units(self.clip_chosen_block, n)
+
+    def unit_errors(self, n):
+        return self._units(self.unit_error_block, n)
 
     def tables(self):
         """(tensors, n_tensors, config) as dfq_batch_mixed_plan_create takes them in front of the bases"""
@@ -1494,7 +1540,7 @@ def _nsr_sources(graph, bottoms, targ_type, bn_type, address):
 
 def quantize_mixed(graph, widths=(2, 3, 4, 6, 8), avg_bits=None, budget_bits=None, per_channel=False, signed=False, sensitivity=None,
                    pin=None, targ_type=[nn.Conv2d, nn.Linear], cost='mse', bottoms=None, bn_type=torch.nn.BatchNorm2d,
-                   moment='variance', input_moment=1.0):
+                   moment='variance', input_moment=1.0, clip=None, alpha_min=0.5):
     """Mixed-precision ``quantize_targ_layer`` for the weights (extension): every ``targ_type`` weight is quantised in place
     at a width of its own out of ``widths``, chosen so that the network takes at most ``budget_bits`` bits (or ``avg_bits``
     per weight on average: floor(avg_bits * number of weights)) and the sum of ``sensitivity[key]`` (default 1) times the
@@ -1509,7 +1555,13 @@ def quantize_mixed(graph, widths=(2, 3, 4, 6, 8), avg_bits=None, budget_bits=Non
     include/dfq_hip.h: every output channel's expected noise-to-signal ratio under the BatchNorm proxies in front of the layer;
     ``NetworkBatch.nsr_plan`` for a batch of one).  It needs ``bottoms`` (ValueError without) and the proxies
     ``merge_batchnorm`` leaves on the ``bn_type`` modules; ``moment`` ('variance' or 'second_moment') and ``input_moment`` are
-    ``nsr_plan``'s.  Each layer's dict then also holds ``'nsr'``, N at the chosen width.  No layer is given a bias."""
+    ``nsr_plan``'s.  Each layer's dict then also holds ``'nsr'``, N at the chosen width.  No layer is given a bias.
+
+    ``clip=K`` (an int in [1, 64]; ``alpha_min`` in (0, 1]) searches the MSE-optimal clip of every unit at every width, allocates
+    on those errors and quantises every layer at its width's own range (dfq_batch_mixed_plan_create_clipped;
+    ``NetworkBatch.mixed_plan(clip=)`` for a batch of one): ``'err'`` and ``'range'`` are then the clipped ones and the dict also
+    holds ``'chosen'``, k* at the chosen width.  With ``cost='nsr'`` the costs come from the unclamped weights and the ranges are
+    still the sum-e^2-optimal ones."""
     lib = _ffi.lib()
     layers = [(key, graph[key].weight) for key in graph if type(graph[key]) in targ_type]
     if not layers:
@@ -1527,7 +1579,7 @@ def quantize_mixed(graph, widths=(2, 3, 4, 6, 8), avg_bits=None, budget_bits=Non
         stage.prefetch([w for _, w in layers] + proxies)
         bufs = {key: stage.bind(w) for key, w in layers}
         lay = _MixedLayout('quantize_mixed', layers, lambda key, w: bufs[key].data_ptr(), 1, widths, avg_bits, budget_bits, per_channel,
-                           signed, sensitivity, pin, None, True, stage.device)
+                           signed, sensitivity, pin, None, True, stage.device, clip, alpha_min)
         bases = (ctypes.c_void_p * 1)(bufs[layers[0][0]].data_ptr())
         plan, nsr, nlay = ctypes.c_void_p(), ctypes.c_void_p(), None
         try:
@@ -1538,13 +1590,14 @@ def quantize_mixed(graph, widths=(2, 3, 4, 6, 8), avg_bits=None, budget_bits=Non
                                   input_moment, stage.device)
                 _ffi.check(lib.dfq_batch_nsr_plan_create(*nlay.tables(), bases, 1, *nlay.block_args(), ctypes.byref(nsr)))
                 _ffi.check(lib.dfq_batch_nsr_plan_run(nsr, _ffi.stream_arg()))
-            _ffi.check(lib.dfq_batch_mixed_plan_create(*lay.tables(), bases, 1, *lay.block_args(), ctypes.byref(plan)))
+            _ffi.check(lay.create(lib, bases, 1, plan))
             if nlay is not None:
                 _ffi.check(lib.dfq_batch_mixed_plan_set_costs(plan, nlay.cost_block.data_ptr()))
             _ffi.check(lib.dfq_batch_mixed_plan_run(plan, _ffi.stream_arg()))
             _ffi.synchronize()
             bits, errors, ranges = lay.bits(0), lay.errors(0), lay.ranges(0)
             costs = nlay.costs(0) if nlay is not None else None
+            chosen = {key: v.cpu().numpy().copy() for key, v in lay.clip_chosen(0).items()} if lay.clip is not None else None
         finally:
             if plan:
                 lib.dfq_batch_mixed_plan_destroy(plan)
@@ -1556,6 +1609,9 @@ def quantize_mixed(graph, widths=(2, 3, 4, 6, 8), avg_bits=None, budget_bits=Non
     if costs is not None:
         for key in lay.keys:
             out[key]['nsr'] = float(costs[key][lay.widths.index(bits[key])])
+    if chosen is not None:
+        for key in lay.keys:
+            out[key]['chosen'] = chosen[key][..., lay.widths.index(bits[key])]
     return out
 
 

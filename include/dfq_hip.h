@@ -796,7 +796,10 @@ int dfq_batch_mixed_plan_create(const dfq_batch_mixed_tensor* tensors, int32_t n
                                 void* codes, int64_t code_stride, float* ranges, int64_t range_stride, dfq_batch_mixed_plan** out_plan);
 int dfq_batch_mixed_plan_run(dfq_batch_mixed_plan* plan, void* stream);
 void dfq_batch_mixed_plan_destroy(dfq_batch_mixed_plan* plan);
-/* kernel launches per run (2 to 4), fixed at creation; the clear of the range words of the long tensors is a memset */
+/* kernel launches per run, fixed at creation: 2 to 4 for a plan of dfq_batch_mixed_plan_create; 3 to 8 for a clipped plan (three
+ * for its flat pieces if it has any, one for its units in registers and looping rows if it has any, the allocation, the state
+ * and range launch behind it, and with `apply` one quantising launch for each of the two kinds of work present).  The clear
+ * of the range words of the long tensors is a memset.  Stages run through dfq_batch_mixed_plan_run_stages are not counted. */
 int32_t dfq_batch_mixed_plan_launches(const dfq_batch_mixed_plan* plan);
 /* Allocate on given costs (extension): with `costs` set -- float64 on the device, [n_nets, T, B] with the plan's own T and B,
  * which nothing here can check -- the allocation of every later run forms c[t][j] = s_t * costs[n][t][j] in place of
@@ -807,6 +810,78 @@ int32_t dfq_batch_mixed_plan_launches(const dfq_batch_mixed_plan* plan);
  * front.  NULL, the default: the plan's own errors again, every result bit for bit that of a plan that never had costs.
  * DFQ_ERR_ARG for a null plan. */
 int dfq_batch_mixed_plan_set_costs(dfq_batch_mixed_plan* plan, const double* costs /* device [n_nets, T, B], or NULL */);
+
+/* Clip-aware mixed precision (extension): the MSE-optimal clip of every unit at EVERY candidate width from one read of the
+ * weight, the allocation on those errors, and the clamp and the quantisation of every tensor at its own width and at that
+ * width's own range; nothing goes to the host in between.  Everything not mentioned here is dfq_batch_mixed_plan_create's
+ * definition, unchanged.
+ * DEFINITION.  Inputs: the candidate widths b_0 < ... < b_{B-1}, `symmetric`, `per_row`, K = `candidates` in [1, 64] and
+ * `alpha_min` in (0, 1].  A UNIT is a tensor, or an output row with `per_row`; its (mn, mx), its shrink factors a_k, its
+ * fixed point z and its candidate ends (l_k, h_k) are dfq_batch_clip_plan_create's, word for word: they do not depend on the
+ * width.
+ *   unit errors   U[n][u][j][k] = err_k of dfq_batch_clip_plan_create with num_bits = b_j: the error of the weight clamped to
+ *                 (l_k, h_k) and quantised, minus the weight as it is, in float64.  The order of each sum is the clip plan's
+ *                 for a unit of that shape -- the same lane classes, the same register bound, the same 4096-float pieces for
+ *                 longer per-tensor tensors, the same fold order -- so every U[n][u][j][k] is BIT FOR BIT the value
+ *                 dfq_batch_clip_plan_run reports for (b_j, symmetric, per_row, K, alpha_min).  No floating-point atomic: two
+ *                 runs are bit-equal, and a network's values do not depend on the batch or on its place in it.
+ *   choice        per width, k*_j = argmin_k U[..][j][k] found with err < best from k = 0 on, the clip plan's rule: a unit whose
+ *                 errors are NaN or all infinite keeps 0, and k*_j is exactly what the clip plan chooses at b_j.
+ *   tensor error  E[n][t][j] = U[n][u][j][k*_j] for a per-tensor plan; with per_row the float64 sum of U[n][r][j][k*_j(r)] over
+ *                 the rows r in rising order (one running sum from +0.0: the order depends on the row count alone).  `errors`
+ *                 reports it; the allocation walks on it, or on the costs of dfq_batch_mixed_plan_set_costs, in which case E
+ *                 is still reported.  The walk, its ties, the pins, the budget rule, `bits`, `used` and `cost` are unchanged.
+ *   clamp stage   every unit of tensor t of network n is clamped to (l, h) of k*_{j_t}, j_t the index of the chosen width:
+ *                 w < l ? l : (w > h ? h : w); NaN and -0.0 pass through; only what the clamp changes is stored, nothing
+ *                 where k* = 0.
+ *   quantise      clamps the same way and quantises in place at b_{j_t} with qparams(l, h, b_{j_t}, symmetric): the weight and
+ *                 the code are bit for bit what dfq_batch_clip_plan_run (b_{j_t}, apply) followed by dfq_batch_quant_plan_run
+ *                 (b_{j_t}) leave for that tensor of that network; quantising after a clamp stage gives the same bits as
+ *                 quantising alone.  `ranges` holds (l, h) of the chosen width for every unit (where that differs from the
+ *                 unit's own (min, max) after the clamp only in the sign of a zero, this is the clip plan's value); the
+ *                 allocation stage writes it, with or without `apply`.
+ * Outputs in blocks of the caller in addition to the mixed plan's, per unit as in the clip plan, a tensor's first unit at
+ * unit_offsets[t] and its rows behind it: `clip_ranges` float32 [n_nets, unit_stride, B, 2] = (l, h) of k*_j; `clip_chosen`
+ * int32 [n_nets, unit_stride, B] = k*_j; `unit_errors` float64 [n_nets, unit_stride, B] = U at k*_j, or null: not written.
+ * Special values follow from the two parent definitions: a unit holding NaN has NaN errors at every width and k* = 0, its
+ * tensor's E is NaN and the tensor takes no step.
+ * create: DFQ_ERR_ARG (and dfq_last_error) for everything dfq_batch_mixed_plan_create refuses, a null `clip`, candidates
+ * outside [1, 64], alpha_min not in (0, 1] (NaN included), B * K above 512, a null clip_ranges or clip_chosen block, null
+ * unit_offsets, unit_stride <= 0, units outside the stride, a shape dfq_batch_clip_plan_create refuses.  The plan is a
+ * dfq_batch_mixed_plan: run (the allocation stage, and with `apply` the quantising one), run_stages, set_costs, launches and
+ * destroy work on it. */
+typedef struct dfq_batch_mixed_clip {
+    int32_t candidates;          /* K                                                                                */
+    int32_t pad;
+    double alpha_min;
+    float* clip_ranges;          /* device [n_nets, unit_stride, B, 2]                                               */
+    int32_t* clip_chosen;        /* device [n_nets, unit_stride, B]                                                  */
+    double* unit_errors;         /* device [n_nets, unit_stride, B], or NULL                                         */
+    int64_t unit_stride;         /* units of one network in the three blocks                                         */
+    const int64_t* unit_offsets; /* host [n_tensors]: a tensor's first unit; read by create only                     */
+} dfq_batch_mixed_clip;
+
+int dfq_batch_mixed_plan_create_clipped(const dfq_batch_mixed_tensor* tensors, int32_t n_tensors, const dfq_batch_mixed_config* config,
+                                        const void* const* bases, int32_t n_nets, int32_t* bits, double* errors, int64_t* used, double* cost,
+                                        void* codes, int64_t code_stride, float* ranges, int64_t range_stride,
+                                        const dfq_batch_mixed_clip* clip, dfq_batch_mixed_plan** out_plan);
+
+/* The stages of a mixed plan one by one (extension), valid on every mixed plan; `stages` is a sum of the values below and they
+ * run in this order on `stream`:
+ *   DFQ_MIXED_ALLOCATE  ranges, errors, allocation; the allocation is also kept in the PLAN'S OWN state, an index j per
+ *                       (network, tensor)
+ *   DFQ_MIXED_CLAMP     the clamp at the chosen widths; clipped plans only, DFQ_ERR_ARG on others
+ *   DFQ_MIXED_QUANTISE  clamp and quantise at the chosen widths, whatever `apply` the plan was made with
+ * CLAMP and QUANTISE read the allocation the plan's last ALLOCATE stage (or, for a clipped plan, run) left in the plan's state,
+ * not the caller-writable `bits` block: a caller's write there cannot index past the tables (on a plan without clipping
+ * QUANTISE first writes the state's widths into `bits` again).  Without an allocation since creation they return
+ * DFQ_ERR_STATE; dfq_batch_mixed_plan_run of a plan without clipping is what it always was and leaves no state.  ALLOCATE |
+ * QUANTISE gives what run gives with `apply`, bit for bit.  DFQ_ERR_ARG for a null plan and for stages that are 0 or hold
+ * another bit. */
+#define DFQ_MIXED_ALLOCATE 1
+#define DFQ_MIXED_CLAMP 2
+#define DFQ_MIXED_QUANTISE 4
+int dfq_batch_mixed_plan_run_stages(dfq_batch_mixed_plan* plan, int32_t stages, void* stream);
 
 /* Data-free layer sensitivities of a whole batch of networks of one architecture (extension): the expected noise-to-signal
  * power ratio of every output channel of every layer at every candidate width, from the weights and the BatchNorm proxies
