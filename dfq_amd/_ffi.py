@@ -264,6 +264,7 @@ SIGNATURES = {
     'dfq_batch_squant_plan_run': (c_int32, [c_void_p, c_void_p]),
     'dfq_batch_squant_plan_destroy': (None, [c_void_p]),
     'dfq_batch_squant_plan_launches': (c_int32, [c_void_p]),
+    'dfq_batch_squant_plan_set_widths': (c_int32, [c_void_p, c_void_p, c_int64, POINTER(c_int32), c_void_p]),
     'dfq_batch_absorb_plan_create': (c_int32, [POINTER(DfqBatchAbsorbRelation), c_int32, POINTER(DfqBatchAbsorbClip), c_int32,
                                                POINTER(c_void_p), c_int32, c_float, c_float, c_float, c_void_p, c_int64,
                                                POINTER(c_void_p)]),

@@ -438,7 +438,7 @@ class NetworkBatch:
         finally:
             plan.close()
 
-    def squant_plan(self, bit_weight=8, per_channel=False, signed=False, codes=None):
+    def squant_plan(self, bit_weight=8, per_channel=False, signed=False, codes=None, widths=None):
         """One adaptive-rounding plan over the weights of the whole batch (BatchSquantPlan; SQuant, "Adaptive rounding" in
         include/dfq_hip.h): the ranges and the quantisation grid are ``quant_plan``'s (per tensor, or per output row with
         ``per_channel``; ``signed``: the symmetric recipe), but of the roundings to nearest the few that cost least are flipped
@@ -446,9 +446,20 @@ class NetworkBatch:
         ``quantize_targ_layer(..., rounding='squant')`` does to each network, bit for bit.  Weights only; ``bit_weight`` is an
         integer in [2, 16] in both range modes.  ``codes``: None, 'int32' or 'int8' as in ``quant_plan``.  The plan exposes
         ``codes(n)``, ``ranges(n)`` and ``stats(n)``.  ValueError for a layer whose rows are longer than
-        dfq_squant_max_row_len()."""
+        dfq_squant_max_row_len().
+
+        ``widths``: every layer at a width of its own.  A BatchMixedPlan of this batch with the same ``per_channel`` and
+        ``signed`` (ValueError otherwise, as for a closed plan, or 'int8' codes with a candidate width above 8): the width of
+        every (network, layer) is read on the device from its ``bits_block`` (dfq_batch_squant_plan_set_widths), so
+        ``mixed.run()`` -- or ``allocate()`` -- and ``run()`` of this plan go onto the stream back to back; ``bit_weight`` is then
+        not used, and ``status(n)`` is 2 where a width on the device was no width (that layer is left as it was).  Or a dict
+        ``key -> int in [2, 16]`` (ValueError for another value, an unknown key, 'int8' codes with a width above 8): the widths
+        go into the plan's table, layers without an entry get ``bit_weight``.  Either way the result is, bit for bit, what
+        ``squant_plan(that width)`` stores for that layer, and ``pack_plan`` packs every layer at its width.  The allocation of
+        a mixed plan walks on the errors of NEAREST rounding; adaptive rounding trades a slightly larger sum e^2 for bounded
+        row sums, so the widths are the nearest-rounding optimum, not this rounding's."""
         self._ready('squant_plan')
-        return BatchSquantPlan(self, bit_weight, per_channel, signed, codes)
+        return BatchSquantPlan(self, bit_weight, per_channel, signed, codes, widths)
 
     def quantize_squant(self, bit_weight=8, bits_bias=16, per_channel=False, signed=False, codes='int32'):
         """squant_plan for the weights, the nearest rounding of ``quantize`` for the biases (unless ``bits_bias >= 32``), run
@@ -521,7 +532,7 @@ class NetworkBatch:
 
     def quantize_mixed(self, widths=(2, 3, 4, 6, 8), avg_bits=None, budget_bits=None, per_channel=False, signed=False, sensitivity=None,
                        pin=None, codes='int32', bits_bias=16, correct=False, cost='mse', moment='variance', input_moment=1.0,
-                       clip=None, alpha_min=0.5):
+                       clip=None, alpha_min=0.5, rounding='nearest'):
         """mixed_plan for the weights, the nearest rounding of ``quantize`` for the biases (unless ``bits_bias >= 32``), run +
         synchronise: returns (codes, ranges, bits), each a list of one dict per network -- the biases' ranges under
         key + '.bias', every bias bit for bit what ``quantize`` stores, ``bits[n][key]`` the width network n's layer got.
@@ -543,10 +554,23 @@ class NetworkBatch:
         correction behind ``clip_weight`` always has --, QUANTISE, then the biases after their correction; no second
         allocation is run (it would see clamped weights and could differ).  With ``cost='nsr'`` the nsr plan runs first, on the
         unclamped weights, and the allocation walks on it; the ranges are still the sum-e^2-optimal ones.  ``clip=None`` is
-        the code path above, unchanged."""
+        the code path above, unchanged.
+
+        ``rounding='squant'`` rounds adaptively (``squant_plan``) at the allocated widths: the allocating plan (``apply=False``;
+        with ``clip=K`` the clipped plan's ALLOCATE and CLAMP stages), then ``squant_plan(widths=that plan, codes=)``, which reads
+        the widths on the device, then the biases as ``quantize_squant`` does them.  On clamped weights the squant plan's own
+        (min, max) is the chosen (l, h) in value.  ``ranges`` are the squant plan's.  The allocation still walks on
+        nearest-rounding errors (``squant_plan``).  ``correct=True`` is a ValueError here: the analytic correction models nearest
+        rounding; correct empirically with ``bias_correction_distill``.  ``rounding='nearest'`` is the code
+        path above, unchanged; anything else is a ValueError."""
         self._ready('quantize_mixed')
         if cost not in ('mse', 'nsr'):
             raise ValueError("quantize_mixed: cost must be 'mse' or 'nsr', got {!r}".format(cost))
+        if rounding not in ('nearest', 'squant'):
+            raise ValueError("quantize_mixed: rounding must be 'nearest' or 'squant', got {!r}".format(rounding))
+        if rounding == 'squant' and correct:
+            raise ValueError("quantize_mixed: correct=True models nearest rounding and does not go with rounding='squant'; "
+                             'correct the rounded networks with bias_correction_distill')
         g0 = self.nets[0][0]
         tt = tuple(self.targ_type)
         plans, first = [], []
@@ -556,6 +580,29 @@ class NetworkBatch:
                 nsr = BatchNsrPlan(self, widths, per_channel, signed, moment, input_moment)
                 first.append(nsr)
                 nsr.run()
+            if rounding == 'squant':
+                first.append(BatchMixedPlan(self, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, None, False, nsr,
+                                            clip, alpha_min))
+                alloc = first[-1]
+                plans.append(BatchSquantPlan(self, alloc.widths[-1], per_channel, signed, codes, alloc))
+                if bits_bias < 32 and any(type(l) in tt and l.bias is not None for l in g0.values()):
+                    plans.append(BatchQuantPlan(self, alloc.widths[-1], bits_bias, per_channel, signed, None, _biases_only=True))
+                alloc.run(None if clip is None else BatchMixedPlan.ALLOCATE | BatchMixedPlan.CLAMP)
+                for plan in plans:
+                    plan.run()
+                _ffi.synchronize()
+                if bool(plans[0].status_block.any()):
+                    raise RuntimeError('quantize_mixed: the allocation left a width that is no width (status {})'.format(
+                        plans[0].status_block.cpu().tolist()))
+                n = len(self.nets)
+                ranges = []
+                for i in range(n):
+                    r = {}
+                    for plan in plans:
+                        r.update({k: v.clone() for k, v in plan.ranges(i).items()})
+                    ranges.append(r)
+                return ([{k: v.clone() for k, v in plans[0].codes(i).items()} for i in range(n)], ranges,
+                        [dict(alloc.bits(i)) for i in range(n)])
             if clip is not None:
                 plans.append(BatchMixedPlan(self, widths, avg_bits, budget_bits, per_channel, signed, sensitivity, pin, codes, True, nsr,
                                             clip, alpha_min))
@@ -613,8 +660,9 @@ class NetworkBatch:
         BatchMixedPlan of this batch created with ``codes`` -- densely, every weight of every network at its own width: the
         stream, the offsets and the status the comment of dfq_batch_pack_plan_create (include/dfq_hip.h) defines.  A mixed
         plan must have been created with ``apply=True`` (its codes are what is packed); its ``bits_block`` is read on the
-        device, so ``source.run()`` and ``run()`` of this plan can be enqueued back to back.  The other two sources have one
-        width.  ``word_stride``: uint32 words per network of the packed block; by default the exact size for one width, and
+        device, so ``source.run()`` and ``run()`` of this plan can be enqueued back to back.  A squant plan made with
+        ``widths=`` is packed the same way, from the block its widths lie in (the mixed plan's, or the dict's); the other sources
+        have one width.  ``word_stride``: uint32 words per network of the packed block; by default the exact size for one width, and
         ceil(budget / 32) + 5 T rounded up to 4 for a mixed plan -- enough whenever ``used <= budget``; ``status(n) == 1`` says so when it is
         not.  ValueError for a source without codes, a mixed plan without ``apply``, a closed source, a source of another
         batch."""
@@ -1058,52 +1106,95 @@ class BatchSquantPlan(_BatchPlan):
     plan owns and hands out as views."""
     _c = 'dfq_batch_squant_plan'
 
-    def __init__(self, batch, bit_weight, per_channel, signed, codes):
+    def __init__(self, batch, bit_weight, per_channel, signed, codes, widths=None):
         bit_weight = _check_bits(bit_weight, True, 'bit_weight')        # [2, 16] in both range modes
         if codes not in (None, 'int32', 'int8'):
             raise ValueError("squant_plan: codes must be None, 'int32' or 'int8', got {!r}".format(codes))
         if codes == 'int8' and bit_weight > 8:
             raise ValueError('squant_plan: 1-byte codes need bit_weight <= 8, got {}'.format(bit_weight))
-        super().__init__(batch)
-        self.per_channel, self.signed, self.bit_weight = bool(per_channel), bool(signed), bit_weight
-        n_nets = len(batch.nets)
-        dev = batch.stage.device
+        own = {}                                                        # widths known on the host: into every tensor's num_bits
+        if isinstance(widths, BatchMixedPlan):
+            self._check_mixed(batch, widths, per_channel, signed, codes)
+        elif widths is not None:
+            if not isinstance(widths, dict):
+                raise ValueError('squant_plan: widths must be None, a mixed_plan of this batch or a dict key -> width, got {!r}'.format(
+                    type(widths).__name__))
+            keys = [key for key, layer in batch.nets[0][0].items() if type(layer) in tuple(batch.targ_type)]
+            for key, b in widths.items():
+                if key not in keys:
+                    raise ValueError('squant_plan: widths names {!r}, which is no layer to quantise'.format(key))
+                if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or not 2 <= b <= 16:
+                    raise ValueError('squant_plan: the width of {!r} must be an int in [2, 16], got {!r}'.format(key, b))
+                if codes == 'int8' and b > 8:
+                    raise ValueError('squant_plan: 1-byte codes need widths <= 8, got {} for {!r}'.format(b, key))
+            own = {key: int(b) for key, b in widths.items()}
         g0 = batch.nets[0][0]
         tt = tuple(batch.targ_type)
-        longest = int(_ffi.lib().dfq_squant_max_row_len())
-        entries, self._code_views, self._range_views, self._stats_views = [], [], [], []
-        code_stride = range_stride = stats_stride = 0
-        for key, layer in g0.items():
-            if type(layer) not in tt:
-                continue
-            w = layer.weight
-            rows = int(w.shape[0])
-            row_len = w.numel() // rows
-            if row_len > longest:
-                raise ValueError('squant_plan: {}: rows of {} weights, the longest row is {}'.format(key, row_len, longest))
-            c_off = -1
-            if codes is not None:
-                c_off = code_stride
-                self._code_views.append((key, c_off, w.numel(), tuple(w.shape)))
-                code_stride += -(-w.numel() // 64) * 64
-            self._range_views.append((key, range_stride, (rows, 2) if per_channel else (2,)))
-            self._stats_views.append((key, stats_stride, rows))
-            entries.append(_ffi.DfqBatchSquantTensor(batch._in_slot(key, 'weight', w), rows, row_len, bit_weight, int(self.signed),
-                                                     int(self.per_channel), 0, c_off, range_stride, _kernel_len(w), stats_stride))
-            range_stride += 2 * rows if per_channel else 2
-            stats_stride += 2 * rows
-        if not entries:
+        layers = [(key, layer.weight) for key, layer in g0.items() if type(layer) in tt]
+        if not layers:
             raise ValueError('squant_plan: the batch has no {} layer'.format(tt))
-        dtype = {None: torch.int32, 'int32': torch.int32, 'int8': torch.int8 if self.signed else torch.uint8}[codes]
-        self.code_dtype = None if codes is None else dtype
-        self.code_block = torch.empty((n_nets, code_stride), dtype=dtype, device=dev) if codes is not None else None
-        self.range_block = torch.empty((n_nets, range_stride), dtype=torch.float32, device=dev)
-        self.stats_block = torch.empty((n_nets, stats_stride), dtype=torch.int64, device=dev)
-        self.n_nets, self.n_tensors = n_nets, len(entries)
-        arr = (_ffi.DfqBatchSquantTensor * len(entries))(*entries)
-        self._create((arr, len(entries)), None if self.code_block is None else self.code_block.data_ptr(),
-                     1 if codes == 'int8' else 4, code_stride, self.range_block.data_ptr(), range_stride,
-                     self.stats_block.data_ptr(), stats_stride)
+        n_nets = len(batch.nets)
+        lay = _dfq._SquantLayout('squant_plan', layers, lambda key, w: batch._in_slot(key, 'weight', w), n_nets,
+                                 lambda key: own.get(key, bit_weight), per_channel, signed, codes, batch.stage.device)
+        super().__init__(batch)
+        self._lay = lay
+        self.per_channel, self.signed, self.bit_weight = lay.per_channel, lay.signed, bit_weight
+        self.keys, self.n_nets, self.n_tensors = lay.keys, n_nets, lay.n_tensors
+        self._code_views, self._range_views, self._stats_views = lay._code_views, lay._range_views, lay._stats_views
+        self.code_dtype, self.code_block, self.range_block = lay.code_dtype, lay.code_block, lay.range_block
+        self.stats_block, self.status_block = lay.stats_block, lay.status_block
+        self._create(lay.tables(), *lay.block_args())
+        # the width of every (network, layer): one for all (``bits_block`` None), the dict's -- a block of this plan, for
+        # pack_plan --, or the mixed plan's block, which every run reads on the device
+        self._codes_kind = codes
+        self._own_bits = self._own_budget = None
+        if own:
+            row = [own.get(key, bit_weight) for key in self.keys]
+            self._own_bits = torch.tensor([row] * n_nets, dtype=torch.int32, device=batch.stage.device)
+            self._own_budget = sum(w.numel() * b for (_, w), b in zip(layers, row))
+        self.bits_block, self.budget, self._mixed = self._own_bits, self._own_budget, None
+        if isinstance(widths, BatchMixedPlan):
+            self.set_widths(widths)
+
+    @staticmethod
+    def _check_mixed(batch, mixed, per_channel, signed, codes):
+        """the rules of mixed_plan(costs=): a live plan of this batch made for the same ranges"""
+        if mixed._batch is not batch:
+            raise ValueError('squant_plan: widths is a mixed_plan of another batch')
+        if not mixed._plan:
+            raise ValueError('squant_plan: the mixed_plan given as widths has been closed')
+        if bool(per_channel) != mixed.per_channel or bool(signed) != mixed.signed:
+            raise ValueError('squant_plan: the widths were allocated for per_channel {}, signed {}; the plan asks for {}, {}'.format(
+                mixed.per_channel, mixed.signed, bool(per_channel), bool(signed)))
+        if codes == 'int8' and mixed.widths[-1] > 8:
+            raise ValueError('squant_plan: 1-byte codes need widths <= 8, got {!r}'.format(mixed.widths))
+
+    def set_widths(self, mixed):
+        """Round every layer of every network at the width ``mixed`` -- a BatchMixedPlan of this batch, checked as
+        ``squant_plan(widths=)`` checks it -- leaves in its ``bits_block``, read on the device by every later run
+        (dfq_batch_squant_plan_set_widths, include/dfq_hip.h); None: at the plan's own widths again -- ``bit_weight``, or the
+        dict the plan was made with.  A ``pack_plan`` made of this plan before the call was made for the widths of then and
+        refuses to run (RuntimeError): make a new one."""
+        if not self._plan:
+            raise RuntimeError('BatchSquantPlan: the plan has been closed')
+        lib = _ffi.lib()
+        if mixed is None:
+            _ffi.check(lib.dfq_batch_squant_plan_set_widths(self._plan, None, 0, None, None))
+            self.bits_block, self.budget, self._mixed = self._own_bits, self._own_budget, None      # (a dict's widths: the table's)
+            return
+        if not isinstance(mixed, BatchMixedPlan):
+            raise ValueError('squant_plan: set_widths takes a mixed_plan of this batch or None, got {!r}'.format(type(mixed).__name__))
+        self._check_mixed(self._batch, mixed, self.per_channel, self.signed, self._codes_kind)
+        at = {key: i for i, key in enumerate(mixed.keys)}
+        index = (ctypes.c_int32 * len(self.keys))(*[at[key] for key in self.keys])
+        _ffi.check(lib.dfq_batch_squant_plan_set_widths(self._plan, mixed.bits_block.data_ptr(), mixed.bits_block.shape[1], index,
+                                                        self.status_block.data_ptr()))
+        self.bits_block, self.budget, self._mixed = mixed.bits_block, mixed.budget, mixed     # (kept alive while the plan reads it)
+
+    def status(self, n):
+        """0, or 2: a width network n's row of the device block held at the last run was no width (outside [2, 16], or above 8
+        with 'int8' codes), and that layer was left as it was; always 0 for a plan without device widths"""
+        return int(self.status_block[n].cpu())
 
     def codes(self, n):
         """{graph key: integer codes of network n's weight, shaped like it} -- views of the code block"""
@@ -1359,6 +1450,7 @@ class BatchPackPlan(_BatchPlan, _Packed):
         mixed = isinstance(source, BatchMixedPlan)
         if mixed and not source.apply:
             raise ValueError('pack_plan: a mixed plan created with apply=False writes no codes')
+        layered = mixed or getattr(source, 'bits_block', None) is not None       # a width per (network, layer), on the device
         views = source._lay._code_views if mixed else source._code_views
         range_views = source._lay._range_views if mixed else source._range_views
         if word_stride is not None and (isinstance(word_stride, bool) or not isinstance(word_stride, (int, np.integer)) or word_stride < 0):
@@ -1372,12 +1464,12 @@ class BatchPackPlan(_BatchPlan, _Packed):
         self.per_channel, self.signed = source.per_channel, source.signed
         self.range_block, self.code_block, self.code_dtype = source.range_block, source.code_block, source.code_dtype
         self.n_nets, self.n_tensors = len(batch.nets), len(views)
-        self.bits = 0 if mixed else int(source.bit_weight)
-        self.bits_block = source.bits_block if mixed else None
-        if not mixed and not 1 <= self.bits <= _PACK_MAX_BITS:
+        self.bits = 0 if layered else int(source.bit_weight)
+        self.bits_block = source.bits_block if layered else None
+        if not layered and not 1 <= self.bits <= _PACK_MAX_BITS:
             raise ValueError('pack_plan: codes of {} bits; the packing takes 1 to {}'.format(self.bits, _PACK_MAX_BITS))
         if word_stride is None:
-            if mixed:
+            if layered:
                 word_stride = -(-(-(-source.budget // 32) + 5 * self.n_tensors) // 4) * 4     # (every row on a 16-byte boundary)
             else:
                 word_stride = sum(_extent_words(numel, self.bits) for (_, numel, _) in self._views)
@@ -1391,6 +1483,14 @@ class BatchPackPlan(_BatchPlan, _Packed):
         self._create((arr, self.n_tensors), self.code_block.data_ptr(), self.code_block.element_size(), self.code_block.shape[1],
                      None if self.bits_block is None else self.bits_block.data_ptr(), self.n_tensors,
                      self.packed_block.data_ptr(), self.word_stride, self.offset_block.data_ptr(), self.status_block.data_ptr())
+
+
+    def run(self):
+        """Enqueue the two launches.  RuntimeError if the source's widths have been set anew since this plan was made
+        (``BatchSquantPlan.set_widths``): the plan would pack at the widths of then."""
+        if getattr(self._source, 'bits_block', None) is not self.bits_block:
+            raise RuntimeError('pack_plan: the widths of the source plan have changed since this plan was made; make a new pack_plan')
+        super().run()
 
 
 class PackedBatch(_Packed):

@@ -386,16 +386,44 @@ __device__ __forceinline__ void sq_row(const SqArgs& a, const SqTensorDev& T, in
     }
 }
 
+// A width per (network, tensor), read on the device (dfq_batch_squant_plan_set_widths): the second argument of the two
+// *_widths_kernel instantiations.  An item -- a wave of the rows kernel, a workgroup of the long-rows kernel -- belongs to one
+// tensor of one network, so its width is one scalar load.
+struct SqWidths {
+    const int32_t* widths;        // [n_nets, stride]
+    const int32_t* index;         // [n_tensors]: the tensor's place in a network's row of `widths`
+    int32_t* status;              // [n_nets], cleared in front of the launches; 2: a width that is no width
+    int64_t stride;
+};
+
+// The width of tensor ti of network `net`, or 0: it is no width (outside [2, 16], or above 8 where the tensor writes one-byte
+// codes); status[net] is then 2 and the item must write nothing else.  Everything here is uniform over the item.
+__device__ __forceinline__ int sq_width_of(const SqArgs& a, const SqWidths& wd, int net, int ti) {
+    const int bits = __builtin_amdgcn_readfirstlane(wd.widths[(int64_t)net * wd.stride + wd.index[ti]]);
+    if (bits < 2 || bits > 16 || (bits > 8 && a.code_bytes == 1 && a.tensors[ti].code_off >= 0)) {
+        if (threadIdx.x % kWave == 0) ((sq_gint32*)wd.status)[net] = 2;
+        return 0;
+    }
+    return bits;
+}
+
 // rows of up to kSqWaveElems elements: a wave per item, 64 / L rows of one tensor each
-__global__ __launch_bounds__(kBlock) void squant_rows_kernel(SqArgs a) {
-    __shared__ int32_t sP[kBlock / kWave][kSqWaveElems];
+template <bool kDeviceWidths>
+__device__ __forceinline__ void sq_rows_item(const SqArgs& a, const SqWidths& wd) {
+    __shared__ int32_t sP[kBlock / kWave][kSqWaveElems];       // (of the one kernel this instantiation is the body of)
     __shared__ int32_t sE[kBlock / kWave][kSqWaveElems / 2];
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kWave);
     const int w = (int)blockIdx.x * (kBlock / kWave) + wave;
     if (w >= a.waves) return;                          // (wave-uniform; no workgroup barrier in this kernel)
     const int net = w / a.waves_pn;
     const int lw = w - net * a.waves_pn;
-    const SqTensorDev T = a.tensors ? a.tensors[a.wave_tensor[lw]] : a.one;
+    int bits = 0;
+    if constexpr (kDeviceWidths) {                     // (a plan's launch: the tensors are a table)
+        bits = sq_width_of(a, wd, net, a.wave_tensor[lw]);
+        if (bits == 0) return;                         // (the whole wave, before any shuffle)
+    }
+    SqTensorDev T = a.tensors ? a.tensors[a.wave_tensor[lw]] : a.one;
+    if constexpr (kDeviceWidths) T.num_bits = bits;
     const int wi = lw - T.item_begin;
     const int lane = (int)threadIdx.x % kWave;
     int32_t* mine = sP[wave];
@@ -417,16 +445,29 @@ __global__ __launch_bounds__(kBlock) void squant_rows_kernel(SqArgs a) {
     }
 }
 
+__global__ __launch_bounds__(kBlock) void squant_rows_kernel(SqArgs a) { sq_rows_item<false>(a, SqWidths{}); }
+__global__ __launch_bounds__(kBlock) void squant_rows_widths_kernel(SqArgs a, SqWidths wd) { sq_rows_item<true>(a, wd); }
+
 // rows of up to kSqMaxRow elements: a workgroup per row
-__global__ __launch_bounds__(kBlock) void squant_long_rows_kernel(SqArgs a) {
+template <bool kDeviceWidths>
+__device__ __forceinline__ void sq_long_rows_item(const SqArgs& a, const SqWidths& wd) {
     __shared__ int32_t sP[kSqMaxRow];
     __shared__ int32_t sE[kSqMaxRow / 2];
     __shared__ long long sh[kBlock / kWave];
     const int net = (int)blockIdx.x / a.bigs_pn;
     const int lb = (int)blockIdx.x - net * a.bigs_pn;
-    const SqTensorDev T = a.tensors ? a.tensors[a.big_tensor[lb]] : a.one;
+    int bits = 0;
+    if constexpr (kDeviceWidths) {
+        bits = sq_width_of(a, wd, net, a.big_tensor[lb]);
+        if (bits == 0) return;                         // (the whole workgroup, before any barrier)
+    }
+    SqTensorDev T = a.tensors ? a.tensors[a.big_tensor[lb]] : a.one;
+    if constexpr (kDeviceWidths) T.num_bits = bits;
     sq_row<kBlock, 0>(a, T, net, lb - T.item_begin, true, sP, sE, SqGroup<kBlock>{sh});
 }
+
+__global__ __launch_bounds__(kBlock) void squant_long_rows_kernel(SqArgs a) { sq_long_rows_item<false>(a, SqWidths{}); }
+__global__ __launch_bounds__(kBlock) void squant_long_rows_widths_kernel(SqArgs a, SqWidths wd) { sq_long_rows_item<true>(a, wd); }
 
 // per-tensor ranges: every chunk of every network folded into its tensor's pair of words
 __global__ __launch_bounds__(kBlock) void squant_minmax_kernel(SqArgs a) {
@@ -457,18 +498,29 @@ inline int sq_class(int64_t len) {
 }
 inline int64_t sq_rows_per_wave(int cls) { return cls <= 5 ? kWave / (2 << cls) : 1; }
 
-inline int sq_launch(const SqArgs& a, hipStream_t st) {
+// wd: null, or the widths of a plan (its tensors are a table), read by the *_widths_kernel pair in place of the other two
+inline int sq_launch(const SqArgs& a, hipStream_t st, const SqWidths* wd = nullptr, int n_nets = 0) {
+    if (wd) DFQ_HIP_TRY(hipMemsetAsync(wd->status, 0, sizeof(int32_t) * (size_t)n_nets, st));
     if (a.chunks > 0) {
         DFQ_HIP_TRY(hipMemsetAsync(a.slots, 0, sizeof(uint32_t) * 2 * (size_t)a.n_slots * (size_t)(a.chunks / a.chunks_pn), st));
         hipLaunchKernelGGL(squant_minmax_kernel, dim3(a.chunks), dim3(kBlock), 0, st, a);
         DFQ_CHECK_LAUNCH();
     }
     if (a.waves > 0) {
-        hipLaunchKernelGGL(squant_rows_kernel, dim3((a.waves + kBlock / kWave - 1) / (kBlock / kWave)), dim3(kBlock), 0, st, a);
+        const dim3 grid((a.waves + kBlock / kWave - 1) / (kBlock / kWave));
+        if (wd) {
+            hipLaunchKernelGGL(squant_rows_widths_kernel, grid, dim3(kBlock), 0, st, a, *wd);
+        } else {
+            hipLaunchKernelGGL(squant_rows_kernel, grid, dim3(kBlock), 0, st, a);
+        }
         DFQ_CHECK_LAUNCH();
     }
     if (a.bigs > 0) {
-        hipLaunchKernelGGL(squant_long_rows_kernel, dim3(a.bigs), dim3(kBlock), 0, st, a);
+        if (wd) {
+            hipLaunchKernelGGL(squant_long_rows_widths_kernel, dim3(a.bigs), dim3(kBlock), 0, st, a, *wd);
+        } else {
+            hipLaunchKernelGGL(squant_long_rows_kernel, dim3(a.bigs), dim3(kBlock), 0, st, a);
+        }
         DFQ_CHECK_LAUNCH();
     }
     return DFQ_OK;
@@ -481,6 +533,8 @@ using namespace dfq;
 struct dfq_batch_squant_plan {
     DevSlab mem;
     SqArgs args{};
+    SqWidths widths{};            // widths.widths null: the table's widths (set_widths)
+    int32_t n_nets = 0, n_tensors = 0;
     int launches = 1;
 };
 
@@ -597,6 +651,9 @@ int dfq_batch_squant_plan_create(const dfq_batch_squant_tensor* tensors, int32_t
     a.chunk_tensor = up.put(chunk_tensor);
     a.delta = up.put(batch_delta(bases, n_nets));
     a.slots = (uint32_t*)up.raw(nullptr, sizeof(uint32_t) * 2 * (size_t)n_slots * n_nets);
+    p->widths.index = (const int32_t*)up.raw(nullptr, sizeof(int32_t) * (size_t)n_tensors);      // (filled by set_widths)
+    p->n_nets = n_nets;
+    p->n_tensors = n_tensors;
     if (up.err != hipSuccess) {
         batch_plan_destroy(p);
         return fail_hip(up.err, "batch squant plan allocation", __FILE__, __LINE__);
@@ -607,7 +664,28 @@ int dfq_batch_squant_plan_create(const dfq_batch_squant_tensor* tensors, int32_t
 
 int dfq_batch_squant_plan_run(dfq_batch_squant_plan* p, void* stream) {
     if (!p) return fail_arg("dfq_batch_squant_plan_run: null plan");
-    return sq_launch(p->args, as_stream(stream));
+    return sq_launch(p->args, as_stream(stream), p->widths.widths ? &p->widths : nullptr, p->n_nets);
+}
+
+int dfq_batch_squant_plan_set_widths(dfq_batch_squant_plan* p, const int32_t* widths, int64_t width_stride, const int32_t* width_index,
+                                     int32_t* status) {
+    const char* me = "dfq_batch_squant_plan_set_widths";
+    if (!p) return fail_arg("%s: null plan", me);
+    if (!widths) {
+        p->widths.widths = nullptr;
+        p->widths.status = nullptr;
+        return DFQ_OK;
+    }
+    if (!width_index || !status) return fail_arg("%s: widths without width_index or status", me);
+    for (int i = 0; i < p->n_tensors; ++i)
+        if (width_index[i] < 0 || width_index[i] >= width_stride)
+            return fail_arg("%s: tensor %d: width_index %d outside [0, %lld)", me, i, (int)width_index[i], (long long)width_stride);
+    dev_quiesce();                                         // (a run in flight may still read the index of the widths before)
+    DFQ_HIP_TRY(hipMemcpy((void*)p->widths.index, width_index, sizeof(int32_t) * (size_t)p->n_tensors, hipMemcpyHostToDevice));
+    p->widths.widths = widths;
+    p->widths.stride = width_stride;
+    p->widths.status = status;
+    return DFQ_OK;
 }
 
 }  // extern "C"

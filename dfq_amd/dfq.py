@@ -1268,6 +1268,72 @@ _MIXED_ENTRIES = 4096            # T * B the allocation's table holds
 _MIXED_PAIRS = 512               # B * K a clipped plan searches
 
 
+class _SquantLayout:
+    """The tensor table and the output blocks of one dfq_batch_squant_plan, shared by ``NetworkBatch.squant_plan`` and
+    ``quantize_mixed(rounding='squant')``.  ``layers``: [(graph key, weight)]; ``address(key, weight)`` gives the weight's device
+    address in network 0; ``bits_of(key)`` the width that goes into the tensor's table entry.  The blocks are torch tensors
+    [n_nets, stride]: ``range_block`` float32, ``stats_block`` int64, ``status_block`` int32 [n_nets] and, with ``codes``
+    ('int32' or 'int8'), ``code_block``.  ValueError('<who>: ...') for a row longer than dfq_squant_max_row_len()."""
+
+    def __init__(self, who, layers, address, n_nets, bits_of, per_channel, signed, codes, device):
+        longest = int(_ffi.lib().dfq_squant_max_row_len())
+        self.per_channel, self.signed = bool(per_channel), bool(signed)
+        self.keys, self.n_nets, self.n_tensors = [key for key, _ in layers], n_nets, len(layers)
+        entries, self._code_views, self._range_views, self._stats_views = [], [], [], []
+        code_stride = range_stride = stats_stride = 0
+        for key, w in layers:
+            rows = int(w.shape[0])
+            row_len = w.numel() // rows
+            if row_len > longest:
+                raise ValueError('{}: {}: rows of {} weights, the longest row is {}'.format(who, key, row_len, longest))
+            klen = 1
+            for d in w.shape[2:]:
+                klen *= int(d)
+            c_off = -1
+            if codes is not None:
+                c_off = code_stride
+                self._code_views.append((key, c_off, w.numel(), tuple(w.shape)))
+                code_stride += -(-w.numel() // 64) * 64
+            self._range_views.append((key, range_stride, (rows, 2) if self.per_channel else (2,)))
+            self._stats_views.append((key, stats_stride, rows))
+            entries.append(_ffi.DfqBatchSquantTensor(address(key, w), rows, row_len, int(bits_of(key)), int(self.signed),
+                                                     int(self.per_channel), 0, c_off, range_stride, klen, stats_stride))
+            range_stride += 2 * rows if self.per_channel else 2
+            stats_stride += 2 * rows
+        self.table = (_ffi.DfqBatchSquantTensor * len(entries))(*entries)
+        dtype = {None: torch.int32, 'int32': torch.int32, 'int8': torch.int8 if self.signed else torch.uint8}[codes]
+        self.code_dtype = None if codes is None else dtype
+        self.code_bytes = 1 if codes == 'int8' else 4
+        self.code_stride, self.range_stride, self.stats_stride = code_stride, range_stride, stats_stride
+        self.code_block = torch.empty((n_nets, code_stride), dtype=dtype, device=device) if codes is not None else None
+        self.range_block = torch.empty((n_nets, range_stride), dtype=torch.float32, device=device)
+        self.stats_block = torch.empty((n_nets, stats_stride), dtype=torch.int64, device=device)
+        self.status_block = torch.zeros((n_nets,), dtype=torch.int32, device=device)
+
+    def tables(self):
+        """(tensors, n_tensors) as dfq_batch_squant_plan_create takes them in front of the bases"""
+        return (self.table, self.n_tensors)
+
+    def block_args(self):
+        """(codes, code_bytes, code_stride, ranges, range_stride, stats, stats_stride) as create takes them behind the bases"""
+        return (None if self.code_block is None else self.code_block.data_ptr(), self.code_bytes, self.code_stride,
+                self.range_block.data_ptr(), self.range_stride, self.stats_block.data_ptr(), self.stats_stride)
+
+    def codes(self, n):
+        if self.code_block is None:
+            return {}
+        row = self.code_block[n]
+        return {key: row[off:off + numel].view(shape) for (key, off, numel, shape) in self._code_views}
+
+    def ranges(self, n):
+        row = self.range_block[n]
+        return {key: row[off:off + 2 * (shape[0] if len(shape) == 2 else 1)].view(shape) for (key, off, shape) in self._range_views}
+
+    def stats(self, n):
+        row = self.stats_block[n]
+        return {key: row[off:off + 2 * rows].view(rows, 2) for (key, off, rows) in self._stats_views}
+
+
 class _MixedLayout:
     """The tensor table, the configuration and the output blocks of one dfq_batch_mixed_plan; every argument is checked here,
     ValueError('<who>: ...') for what create would refuse.  ``layers``: [(graph key, weight)]; ``address(key, weight)`` gives
@@ -1540,7 +1606,7 @@ def _nsr_sources(graph, bottoms, targ_type, bn_type, address):
 
 def quantize_mixed(graph, widths=(2, 3, 4, 6, 8), avg_bits=None, budget_bits=None, per_channel=False, signed=False, sensitivity=None,
                    pin=None, targ_type=[nn.Conv2d, nn.Linear], cost='mse', bottoms=None, bn_type=torch.nn.BatchNorm2d,
-                   moment='variance', input_moment=1.0, clip=None, alpha_min=0.5):
+                   moment='variance', input_moment=1.0, clip=None, alpha_min=0.5, rounding='nearest'):
     """Mixed-precision ``quantize_targ_layer`` for the weights (extension): every ``targ_type`` weight is quantised in place
     at a width of its own out of ``widths``, chosen so that the network takes at most ``budget_bits`` bits (or ``avg_bits``
     per weight on average: floor(avg_bits * number of weights)) and the sum of ``sensitivity[key]`` (default 1) times the
@@ -1561,13 +1627,22 @@ def quantize_mixed(graph, widths=(2, 3, 4, 6, 8), avg_bits=None, budget_bits=Non
     on those errors and quantises every layer at its width's own range (dfq_batch_mixed_plan_create_clipped;
     ``NetworkBatch.mixed_plan(clip=)`` for a batch of one): ``'err'`` and ``'range'`` are then the clipped ones and the dict also
     holds ``'chosen'``, k* at the chosen width.  With ``cost='nsr'`` the costs come from the unclamped weights and the ranges are
-    still the sum-e^2-optimal ones."""
+    still the sum-e^2-optimal ones.
+
+    ``rounding='squant'`` rounds adaptively at the allocated widths (``NetworkBatch.quantize_mixed(rounding='squant')`` for a
+    batch of one): the plan only allocates (and, with ``clip``, clamps), then one adaptive-rounding plan reads the widths on the
+    device (dfq_batch_squant_plan_set_widths).  ``'range'`` is then the adaptive rounding's, ``'err'`` still the sum e^2 of NEAREST
+    rounding at the chosen width -- what the allocation walked on -- and the dict also holds ``'flips'``, the number of codes
+    that differ from nearest.  ``'nearest'``, the default, is the path above; anything else is a ValueError."""
     lib = _ffi.lib()
     layers = [(key, graph[key].weight) for key in graph if type(graph[key]) in targ_type]
     if not layers:
         raise ValueError('quantize_mixed: the graph has no {} layer'.format(tuple(targ_type)))
     if cost not in ('mse', 'nsr'):
         raise ValueError("quantize_mixed: cost must be 'mse' or 'nsr', got {!r}".format(cost))
+    if rounding not in ('nearest', 'squant'):
+        raise ValueError("quantize_mixed: rounding must be 'nearest' or 'squant', got {!r}".format(rounding))
+    squant = rounding == 'squant'
     if cost == 'nsr' and bottoms is None:
         raise ValueError("quantize_mixed: cost='nsr' reads the BatchNorms in front of every layer and needs `bottoms`")
     with torch.no_grad():
@@ -1579,9 +1654,9 @@ def quantize_mixed(graph, widths=(2, 3, 4, 6, 8), avg_bits=None, budget_bits=Non
         stage.prefetch([w for _, w in layers] + proxies)
         bufs = {key: stage.bind(w) for key, w in layers}
         lay = _MixedLayout('quantize_mixed', layers, lambda key, w: bufs[key].data_ptr(), 1, widths, avg_bits, budget_bits, per_channel,
-                           signed, sensitivity, pin, None, True, stage.device, clip, alpha_min)
+                           signed, sensitivity, pin, None, not squant, stage.device, clip, alpha_min)
         bases = (ctypes.c_void_p * 1)(bufs[layers[0][0]].data_ptr())
-        plan, nsr, nlay = ctypes.c_void_p(), ctypes.c_void_p(), None
+        plan, nsr, nlay, sq, flips = ctypes.c_void_p(), ctypes.c_void_p(), None, ctypes.c_void_p(), None
         try:
             if cost == 'nsr':
                 sources, ranges_of = _nsr_sources(graph, bottoms, targ_type, bn_type, lambda t: stage.bind(t).data_ptr())
@@ -1593,12 +1668,24 @@ def quantize_mixed(graph, widths=(2, 3, 4, 6, 8), avg_bits=None, budget_bits=Non
             _ffi.check(lay.create(lib, bases, 1, plan))
             if nlay is not None:
                 _ffi.check(lib.dfq_batch_mixed_plan_set_costs(plan, nlay.cost_block.data_ptr()))
-            _ffi.check(lib.dfq_batch_mixed_plan_run(plan, _ffi.stream_arg()))
+            if squant and lay.clip is not None:
+                _ffi.check(lib.dfq_batch_mixed_plan_run_stages(plan, _ffi.MIXED_ALLOCATE | _ffi.MIXED_CLAMP, _ffi.stream_arg()))
+            else:
+                _ffi.check(lib.dfq_batch_mixed_plan_run(plan, _ffi.stream_arg()))
+            if squant:
+                sl = _squant_at_widths(lib, layers, bufs, bases, lay, sq)
             _ffi.synchronize()
             bits, errors, ranges = lay.bits(0), lay.errors(0), lay.ranges(0)
+            if squant:
+                if int(sl.status_block[0].cpu()):
+                    raise RuntimeError('quantize_mixed: the allocation left a width that is no width (status {})'.format(
+                        int(sl.status_block[0].cpu())))
+                ranges, flips = sl.ranges(0), sl.stats(0)
             costs = nlay.costs(0) if nlay is not None else None
             chosen = {key: v.cpu().numpy().copy() for key, v in lay.clip_chosen(0).items()} if lay.clip is not None else None
         finally:
+            if sq:
+                lib.dfq_batch_squant_plan_destroy(sq)
             if plan:
                 lib.dfq_batch_mixed_plan_destroy(plan)
             if nsr:
@@ -1612,7 +1699,22 @@ def quantize_mixed(graph, widths=(2, 3, 4, 6, 8), avg_bits=None, budget_bits=Non
     if chosen is not None:
         for key in lay.keys:
             out[key]['chosen'] = chosen[key][..., lay.widths.index(bits[key])]
+    if flips is not None:
+        for key in lay.keys:
+            out[key]['flips'] = int(flips[key][:, 1].sum().cpu())
     return out
+
+
+def _squant_at_widths(lib, layers, bufs, bases, lay, sq):
+    """quantize_mixed(rounding='squant'): the adaptive-rounding plan of one network at the widths ``lay.bits_block`` holds on the
+    device, created into ``sq`` and enqueued.  Returns its _SquantLayout, whose blocks are written once the stream has run."""
+    sl = _SquantLayout('quantize_mixed', layers, lambda key, w: bufs[key].data_ptr(), 1, lambda key: lay.widths[-1], lay.per_channel,
+                       lay.signed, None, lay.bits_block.device)
+    _ffi.check(lib.dfq_batch_squant_plan_create(*sl.tables(), bases, 1, *sl.block_args(), ctypes.byref(sq)))
+    index = (ctypes.c_int32 * sl.n_tensors)(*range(sl.n_tensors))
+    _ffi.check(lib.dfq_batch_squant_plan_set_widths(sq, lay.bits_block.data_ptr(), lay.n_tensors, index, sl.status_block.data_ptr()))
+    _ffi.check(lib.dfq_batch_squant_plan_run(sq, _ffi.stream_arg()))
+    return sl
 
 
 # ------------------------------------------------------------------------------------------------

@@ -506,6 +506,28 @@ int dfq_batch_squant_plan_run(dfq_batch_squant_plan* plan, void* stream);
 void dfq_batch_squant_plan_destroy(dfq_batch_squant_plan* plan);
 /* kernel launches per run (1 to 3: per-tensor ranges, rows of a wave or less, rows of a workgroup) */
 int32_t dfq_batch_squant_plan_launches(const dfq_batch_squant_plan* plan);
+/* A width per (network, tensor), read on the device (extension; the widths a dfq_batch_mixed_plan allocation leaves in its
+ * `bits` block, so that nothing goes to the host between the allocation and the adaptive rounding).
+ * DEFINITION.  With `widths` set -- int32 on the device, [n_nets, width_stride] -- every later run treats tensor t of network n
+ * exactly as "Adaptive rounding" above defines it with num_bits = widths[n * width_stride + width_index[t]]: the QParams and so
+ * t, P, stage K, stage C, the fallback, the stored weight, the code and the stats are, bit for bit, what a plan created with
+ * that num_bits for that tensor stores.  Ranges do not depend on the width: the range launch of the per-tensor tensors and the
+ * range block are as without widths.  `width_index` is host memory, [n_tensors] of the plan, read by this call only.
+ *   a width that is no width -- outside [2, 16], or above 8 for a tensor that writes one-byte codes -- makes the items of that
+ *            (network, tensor) write nothing: no weight, code, range or stats word of it is touched, and status[n] becomes 2
+ *            (a plain store of the constant; several items may store it).  Every other tensor of that network and every other
+ *            network is processed as usual.  Every run clears `status` -- int32 on the device, [n_nets] -- first, with a memset
+ *            on the stream, so status[n] == 0 after a run says that network n was rounded whole.
+ * The widths are read by the row launches of a run, so whatever writes them (dfq_batch_mixed_plan_run) goes onto the same
+ * stream in front.  The row launches are then other instantiations of the same kernels; dfq_batch_squant_plan_launches is
+ * unchanged (the memset is no launch).  NULL `widths`, the default: the table's widths again, every result bit for bit that of
+ * a plan that never had widths; `status` is then not touched.  A call with `widths` set synchronises (it replaces the index
+ * a run may still read); a NULL call changes host fields only and does not.
+ * DFQ_ERR_ARG for a null plan, widths without width_index or status, an index that is negative or >= width_stride. */
+int dfq_batch_squant_plan_set_widths(dfq_batch_squant_plan* plan,
+                                     const int32_t* widths /* device int32 [n_nets, width_stride], or NULL */, int64_t width_stride,
+                                     const int32_t* width_index /* host [n_tensors], read here only */,
+                                     int32_t* status /* device int32 [n_nets] */);
 
 /* Bias absorption and weight clipping of a whole batch of networks of one architecture (extension; bias_absorption,
  * dfq.py:121-164, followed by clip_weight, dfq.py:167-170, for every network of a batch at once).  The tables describe the
