@@ -142,6 +142,25 @@ class DfqBatchUnpackTensor(Structure):
                 ('range_offset', c_int64), ('num_bits', c_int32), ('width_index', c_int32), ('symmetric', c_int32), ('per_row', c_int32)]
 
 
+class DfqBatchMxTensor(Structure):
+    _fields_ = [('data', c_void_p), ('rows', c_int64), ('row_len', c_int64), ('code_offset', c_int64), ('scale_offset', c_int64)]
+
+
+class DfqBatchMxConfig(Structure):
+    _fields_ = [('widths', c_int32 * 3), ('n_widths', c_int32), ('format6', c_int32), ('format8', c_int32), ('search', c_int32),
+                ('apply', c_int32), ('num_bits', c_int32), ('pad', c_int32)]
+
+
+class DfqBatchMxDecodeTensor(Structure):
+    _fields_ = [('data', c_void_p), ('rows', c_int64), ('row_len', c_int64), ('code_offset', c_int64), ('scale_offset', c_int64),
+                ('num_bits', c_int32), ('width_index', c_int32)]
+
+
+MX_E2M1, MX_E2M3, MX_E3M2, MX_E4M3, MX_E5M2 = 0, 1, 2, 3, 4     # DFQ_MX_* of include/dfq_hip.h
+MX_BLOCK = 32
+MX_ERRORS, MX_QUANTISE = 1, 2
+
+
 class DfqBatchActResult(Structure):
     _fields_ = [('step_begin', c_int32), ('step_count', c_int32)]
 
@@ -321,6 +340,20 @@ SIGNATURES = {
     'dfq_batch_unpack_plan_run': (c_int32, [c_void_p, c_void_p]),
     'dfq_batch_unpack_plan_destroy': (None, [c_void_p]),
     'dfq_batch_unpack_plan_launches': (c_int32, [c_void_p]),
+    'dfq_mx_rows': (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dfq_batch_mx_plan_create': (c_int32, [POINTER(DfqBatchMxTensor), c_int32, POINTER(DfqBatchMxConfig), POINTER(c_void_p), c_int32,
+                                           c_void_p, c_void_p, c_int64, c_void_p, c_int64, POINTER(c_void_p)]),
+    'dfq_batch_mx_plan_run': (c_int32, [c_void_p, c_void_p]),
+    'dfq_batch_mx_plan_run_stages': (c_int32, [c_void_p, c_int32, c_void_p]),
+    'dfq_batch_mx_plan_set_widths': (c_int32, [c_void_p, c_void_p, c_int64, POINTER(c_int32), c_void_p]),
+    'dfq_batch_mx_plan_destroy': (None, [c_void_p]),
+    'dfq_batch_mx_plan_launches': (c_int32, [c_void_p]),
+    'dfq_batch_mx_decode_plan_create': (c_int32, [POINTER(DfqBatchMxDecodeTensor), c_int32, POINTER(c_void_p), c_int32, c_void_p, c_int64,
+                                                  c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p,
+                                                  POINTER(c_void_p)]),
+    'dfq_batch_mx_decode_plan_run': (c_int32, [c_void_p, c_void_p]),
+    'dfq_batch_mx_decode_plan_destroy': (None, [c_void_p]),
+    'dfq_batch_mx_decode_plan_launches': (c_int32, [c_void_p]),
     'dfq_batch_act_plan_create': (c_int32, [POINTER(DfqBatchActResult), c_int32, POINTER(DfqBatchActStep), c_int32,
                                             POINTER(DfqBatchActSource), c_int32, POINTER(c_void_p), c_int32, c_float, c_float,
                                             c_void_p, c_int64, POINTER(c_void_p)]),

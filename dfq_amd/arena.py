@@ -504,7 +504,9 @@ class NetworkBatch:
         ``costs``: a BatchNsrPlan of this batch with the same ``widths``, ``per_channel`` and ``signed`` (ValueError otherwise).
         The allocation then weighs ``sensitivity[key]`` times the layer's summed noise-to-signal ratio (``nsr_plan``) in place of
         its sum e^2, read on the device from that plan's ``cost_block`` -- run it first, on the same stream; ``errors(n)`` is
-        still the sum e^2, ``cost(n)`` the sum of the weighed costs at the chosen widths.
+        still the sum e^2, ``cost(n)`` the sum of the weighed costs at the chosen widths.  A BatchMxPlan of this batch is taken
+        the same way -- its ``cost_block`` holds the MX sum e^2 of every layer at every width --, and only its ``widths`` tuple is
+        compared: an MX grid has no ``per_channel`` or ``signed`` (``mx_plan``, ``quantize_mx``).
 
         ``clip``: None for the plan above through its own entry point, or K, an int in [1, 64]: the clip-aware plan
         (dfq_batch_mixed_plan_create_clipped).  The MSE-optimal clip of every unit -- a tensor, or an output row with
@@ -655,6 +657,65 @@ class NetworkBatch:
             for plan in plans + first:
                 plan.close()
 
+    def mx_plan(self, widths=(4, 6, 8), bit_weight=4, fp6='e2m3', fp8='e4m3', search=True, apply=True, codes=True):
+        """One plan (BatchMxPlan) that turns the ``targ_type`` weights of the whole batch into the OCP MX block-scaled formats
+        the f8f6f4 matrix units of the MI355X multiply natively ("MX block-scaled" in include/dfq_hip.h holds the definition):
+        32 consecutive weights of a row share one power-of-two scale (an E8M0 byte), a weight becomes the nearest FP4 (E2M1),
+        FP6 (``fp6``: 'e2m3' or 'e3m2') or FP8 (``fp8``: 'e4m3' or 'e5m2') code, ties to the even code, saturating.  ``widths``:
+        the candidate widths, a rising subset of (4, 6, 8); the ERRORS stage leaves every layer's sum of squared errors at every
+        one of them in ``error_block`` from one read of the weights.  ``search``: per block, the exponent of the OCP floor rule or
+        the one above it, whichever gives the block the smaller sum e^2.  ``apply``: ``run()`` also quantises in place at
+        ``bit_weight`` (one of ``widths``), or at the widths ``set_widths`` names on the device; ``codes``: keep the one-byte
+        codes in ``code_block``.  The plan exposes ``codes(n)``, ``scales(n)``, ``errors(n)``, ``status(n)``, ``set_widths`` and
+        ``run(stages)``; ``pack_plan`` packs its codes, ``mixed_plan(costs=)`` allocates on its errors.  Weights only: there is
+        no single-network ``quantize_mx`` drop-in, bias correction keeps modelling integer grids, adaptive rounding is not
+        defined on these grids, activations are not touched and nothing here multiplies matrices."""
+        self._ready('mx_plan')
+        return BatchMxPlan(self, widths, bit_weight, fp6, fp8, search, apply, codes)
+
+    def quantize_mx(self, widths=(4, 6, 8), avg_bits=None, budget_bits=None, pin=None, sensitivity=None, search=True, bit_weight=None,
+                    fp6='e2m3', fp8='e4m3'):
+        """mx_plan, an allocation if a budget is given, run + synchronise: returns (codes, scales, bits, errors), each a list of
+        one dict per network -- uint8 codes shaped like the weight, uint8 scale bytes [rows, ceil(row_len / 32)], the width the
+        layer got, float64 [len(widths)] sum e^2 at every candidate width.
+
+        With one width, or without ``avg_bits`` / ``budget_bits``, this is the plan at ``bit_weight`` (default: the first width).
+        With a budget every layer of every network gets a width of its own out of ``widths``: the mx plan's ERRORS stage,
+        ``mixed_plan(widths, avg_bits, budget_bits, sensitivity=, pin=, apply=False, costs=that plan).run()`` -- the greedy walk
+        of dfq_batch_mixed_plan on the MX errors --, and the QUANTISE stage at the widths the walk left on the device go onto the
+        stream back to back (``set_widths`` is called before the first of them: it enqueues nothing); nothing is copied to the
+        host in between.
+
+        The budget counts ELEMENT bits.  The scales come on top: 8 bits per block, 0.25 bit per weight on full blocks and more on
+        short rows (a depthwise row of 9 weights carries 8 / 9 bit per weight)."""
+        self._ready('quantize_mx')
+        widths = tuple(widths)
+        budgeted = len(widths) > 1 and (avg_bits is not None or budget_bits is not None)
+        mx = BatchMxPlan(self, widths, widths[0] if bit_weight is None else bit_weight, fp6, fp8, search, True, True)
+        plans = [mx]
+        try:
+            n = len(self.nets)
+            if budgeted:
+                mixed = BatchMixedPlan(self, widths, avg_bits, budget_bits, False, False, sensitivity, pin, None, False, mx)
+                plans.append(mixed)
+                mx.set_widths(mixed)
+                mx.run(BatchMxPlan.ERRORS)
+                mixed.run()
+                mx.run(BatchMxPlan.QUANTISE)
+            else:
+                mx.run()
+            _ffi.synchronize()
+            if bool(mx.status_block.any()):
+                raise RuntimeError('quantize_mx: the allocation left a width that is no width (status {})'.format(
+                    mx.status_block.cpu().tolist()))
+            bits = [dict(mixed.bits(i)) for i in range(n)] if budgeted else [{k: mx.bit_weight for k in mx.keys} for _ in range(n)]
+            return ([OrderedDict((k, v.clone()) for k, v in mx.codes(i).items()) for i in range(n)],
+                    [OrderedDict((k, v.clone()) for k, v in mx.scales(i).items()) for i in range(n)], bits,
+                    [mx.errors(i) for i in range(n)])
+        finally:
+            for plan in plans:
+                plan.close()
+
     def pack_plan(self, source, word_stride=None):
         """One plan (BatchPackPlan) that packs the integer codes of ``source`` -- a BatchQuantPlan, BatchSquantPlan or
         BatchMixedPlan of this batch created with ``codes`` -- densely, every weight of every network at its own width: the
@@ -665,7 +726,11 @@ class NetworkBatch:
         have one width.  ``word_stride``: uint32 words per network of the packed block; by default the exact size for one width, and
         ceil(budget / 32) + 5 T rounded up to 4 for a mixed plan -- enough whenever ``used <= budget``; ``status(n) == 1`` says so when it is
         not.  ValueError for a source without codes, a mixed plan without ``apply``, a closed source, a source of another
-        batch."""
+        batch.
+
+        A BatchMxPlan is a source too: its one-byte codes (sign | exponent | mantissa) are packed as unsigned codes at the plan's
+        own width, or at the widths of the block its ``set_widths`` named, with the default ``word_stride`` of a layered source;
+        the scale bytes stay the source's ``scale_block`` (``save_packed`` writes them out)."""
         self.check()
         return BatchPackPlan(self, source, word_stride)
 
@@ -675,7 +740,11 @@ class NetworkBatch:
         for bit what the quantiser stored (up to the sign of a zero: "zero's sign" in include/dfq_hip.h), and / or to the
         integer codes in a block of the plan (``codes``: None, 'int32' or 'int8', as in ``quant_plan``).  One launch.
         ValueError for ``weights=False`` without ``codes``, 'int8' with a width above 8, keys or shapes that are not this
-        batch's."""
+        batch's.
+
+        Words packed from a BatchMxPlan take two launches: the same unpack launch to one-byte codes (``code_block``, always
+        kept; ``codes`` is None or 'int8'), then one decode launch (dfq_batch_mx_decode_plan) from the codes and the scale bytes
+        to the weights, bit for bit what the quantiser stored, zero signs included -- the sign lives in the code."""
         self._ready('unpack_plan')
         return BatchUnpackPlan(self, packed, weights, codes)
 
@@ -686,7 +755,12 @@ class NetworkBatch:
         tensor, or per row with ``per_channel``), ``keys``, ``shapes`` int64 [T, 8] (padded with zeros), ``per_channel``,
         ``signed``, ``version``, and the biases as float32 (``bias_keys``, ``biases`` [n_nets, B] concatenated in that
         order).  ``source`` must have run.  RuntimeError if a network did not pack (status != 0).  Returns the closed pack
-        plan, whose blocks stay readable."""
+        plan, whose blocks stay readable.
+
+        An MX source (``mx_plan``) writes format ``version`` 2: no ``ranges``, but ``mx_scales`` uint8 [n_nets, S] (the scale
+        bytes in the order of ``keys``), ``mx_format6``, ``mx_format8`` (the DFQ_MX_* ids of the 6- and 8-bit codes) and
+        ``mx_block`` (32).  Files of the other sources keep version 1 and their keys; ``load_packed`` reads both and refuses
+        every other version."""
         plan = self.pack_plan(source)
         try:
             plan.run()
@@ -699,14 +773,20 @@ class NetworkBatch:
                 next(n for n, s in enumerate(status) if s), next(s for s in status if s)))
         offsets = plan.offset_block.cpu().numpy()
         words = plan.packed_block.cpu().numpy().view(np.uint32)
-        out = {'version': np.int64(_PACKED_VERSION), 'keys': np.array(plan.keys, dtype=np.str_), 'offsets': offsets,
-               'widths': plan.widths_array(), 'per_channel': np.bool_(plan.per_channel), 'signed': np.bool_(plan.signed)}
+        out = {'version': np.int64(_PACKED_VERSION if plan.mx is None else _PACKED_MX_VERSION), 'keys': np.array(plan.keys, dtype=np.str_),
+               'offsets': offsets, 'widths': plan.widths_array(), 'per_channel': np.bool_(plan.per_channel), 'signed': np.bool_(plan.signed)}
         shapes = np.zeros((len(plan.keys), 8), dtype=np.int64)
         for i, (_, _, shape) in enumerate(plan._views):
             shapes[i, :len(shape)] = shape
         out['shapes'] = shapes
-        rng = plan.range_block.cpu().numpy()
-        out['ranges'] = np.concatenate([rng[:, off:off + _range_floats(shape)] for (_, off, shape) in plan._range_views], axis=1)
+        if plan.mx is None:
+            rng = plan.range_block.cpu().numpy()
+            out['ranges'] = np.concatenate([rng[:, off:off + _range_floats(shape)] for (_, off, shape) in plan._range_views], axis=1)
+        else:                                               # (an MX file: the scale bytes in the order of `keys`, no ranges)
+            sc = plan.mx.scale_block.cpu().numpy()
+            out['mx_scales'] = np.concatenate([sc[:, off:off + n_blk] for (_, off, n_blk, _) in plan.mx.views], axis=1)
+            out['mx_format6'], out['mx_format8'] = np.int64(_MX_FP6[plan.mx.fp6]), np.int64(_MX_FP8[plan.mx.fp8])
+            out['mx_block'] = np.int64(_ffi.MX_BLOCK)
         for n in range(plan.n_nets):
             out['words_{}'.format(n)] = words[n, :int(offsets[n, -1])].copy()
         bias_keys = [k for k in plan.keys if self.nets[0][0][k].bias is not None]
@@ -731,7 +811,7 @@ class NetworkBatch:
             _ffi.synchronize()
         finally:
             plan.close()
-        status = plan.status_block.cpu().tolist()
+        status = plan.statuses()
         if any(status):
             raise ValueError('load_packed: the offsets of network {} do not fit its widths (status {})'.format(
                 next(n for n, s in enumerate(status) if s), next(s for s in status if s)))
@@ -1239,13 +1319,16 @@ class BatchMixedPlan(_BatchPlan):
         if not layers:
             raise ValueError('mixed_plan: the batch has no {} layer'.format(tt))
         if costs is not None:
-            if not isinstance(costs, BatchNsrPlan) or costs._batch is not batch:
-                raise ValueError('mixed_plan: costs must be a BatchNsrPlan of this batch')
+            if not isinstance(costs, (BatchNsrPlan, BatchMxPlan)) or costs._batch is not batch:
+                raise ValueError('mixed_plan: costs must be a BatchNsrPlan (or a BatchMxPlan) of this batch')
             try:
                 same = tuple(widths) == costs.widths
             except TypeError:
                 same = False
-            if not same or bool(per_channel) != costs.per_channel or bool(signed) != costs.signed:
+            if isinstance(costs, BatchMxPlan):                  # (an MX grid has no per_channel / signed: the widths alone)
+                if not same:
+                    raise ValueError('mixed_plan: costs were made for widths {!r}; the plan asks for {!r}'.format(costs.widths, widths))
+            elif not same or bool(per_channel) != costs.per_channel or bool(signed) != costs.signed:
                 raise ValueError('mixed_plan: costs were made for widths {!r}, per_channel {}, signed {}; the plan asks for {!r}, {}, {}'.format(
                     costs.widths, costs.per_channel, costs.signed, widths, bool(per_channel), bool(signed)))
         lay = _dfq._MixedLayout('mixed_plan', layers, lambda key, w: batch._in_slot(key, 'weight', w), len(batch.nets), widths,
@@ -1386,7 +1469,154 @@ class BatchNsrPlan(_BatchPlan):
         return self._lay.moments(n)
 
 
+_MX_FP6 = {'e2m3': _ffi.MX_E2M3, 'e3m2': _ffi.MX_E3M2}
+_MX_FP8 = {'e4m3': _ffi.MX_E4M3, 'e5m2': _ffi.MX_E5M2}
+
+
+def _mx_blocks(shape):
+    """scale bytes of a weight: rows * ceil(row_len / 32)"""
+    rows = int(shape[0])
+    return rows * -(-(int(np.prod(shape)) // rows) // _ffi.MX_BLOCK)
+
+
+class BatchMxPlan(_BatchPlan):
+    """MX block-scaled FP4 / FP6 / FP8 quantisation of the weights of every network of a NetworkBatch (dfq_batch_mx_plan,
+    include/dfq_hip.h, which holds the definition under "MX block-scaled"): network 0's table of ``targ_type`` weights plus the
+    batch's base addresses.  The ERRORS stage (two launches) reads every weight once and writes ``error_block`` float64
+    [n_nets, T, F], the sum of squared errors of every layer at every candidate width; the QUANTISE stage (one launch) writes the
+    weights in place, ``code_block`` uint8 [n_nets, code_stride] (sign | exponent | mantissa in the low bits of a byte, one per
+    weight) and ``scale_block`` uint8 [n_nets, scale_stride] (one E8M0 byte per 32 weights of a row; 255: the block held a NaN
+    or an Inf).  ``run()`` is ERRORS and, with ``apply``, QUANTISE (``launches`` of them); ``run(stages)`` any of the two.
+    ``cost_block`` is ``error_block``: what ``mixed_plan(costs=)`` allocates on.  The blocks are torch tensors that outlive
+    ``close()``.  Two runs give bit-equal blocks, and a network's part does not depend on the others."""
+    _c = 'dfq_batch_mx_plan'
+    ERRORS, QUANTISE = _ffi.MX_ERRORS, _ffi.MX_QUANTISE
+
+    def __init__(self, batch, widths, bit_weight, fp6, fp8, search, apply, codes):
+        try:
+            widths = tuple(widths)
+        except TypeError:
+            raise ValueError('mx_plan: widths must be a rising subset of (4, 6, 8), got {!r}'.format(widths)) from None
+        if (not widths or any(isinstance(b, bool) or not isinstance(b, (int, np.integer)) or b not in (4, 6, 8) for b in widths)
+                or any(b <= a for a, b in zip(widths, widths[1:]))):
+            raise ValueError('mx_plan: widths must be a rising subset of (4, 6, 8), got {!r}'.format(widths))
+        if fp6 not in _MX_FP6:
+            raise ValueError("mx_plan: fp6 must be 'e2m3' or 'e3m2', got {!r}".format(fp6))
+        if fp8 not in _MX_FP8:
+            raise ValueError("mx_plan: fp8 must be 'e4m3' or 'e5m2', got {!r}".format(fp8))
+        if apply and (isinstance(bit_weight, bool) or not isinstance(bit_weight, (int, np.integer)) or bit_weight not in widths):
+            raise ValueError('mx_plan: bit_weight {!r} is none of the widths {!r}'.format(bit_weight, widths))
+        g0 = batch.nets[0][0]
+        tt = tuple(batch.targ_type)
+        layers = [(key, layer.weight) for key, layer in g0.items() if type(layer) in tt]
+        if not layers:
+            raise ValueError('mx_plan: the batch has no {} layer'.format(tt))
+        super().__init__(batch)
+        self.widths, self.fp6, self.fp8, self.search, self.apply = tuple(int(b) for b in widths), fp6, fp8, bool(search), bool(apply)
+        self.bit_weight = int(bit_weight) if apply else self.widths[0]
+        self.per_channel, self.signed = False, False        # (what pack_plan asks of a source: one-byte unsigned codes)
+        self.range_block, self._range_views = None, []
+        n_nets, dev = len(batch.nets), batch.stage.device
+        self.keys, self.n_nets, self.n_tensors = [key for key, _ in layers], n_nets, len(layers)
+        self._sizes = OrderedDict((key, w.numel()) for key, w in layers)
+        self.elements = sum(self._sizes.values())
+        entries, self._code_views, self._scale_views = [], [], []
+        code_stride = scale_stride = 0
+        for key, w in layers:
+            rows = int(w.shape[0])
+            c_off = -1
+            if codes:
+                c_off = code_stride
+                self._code_views.append((key, c_off, w.numel(), tuple(w.shape)))
+                code_stride += -(-w.numel() // 64) * 64
+            n_blk = _mx_blocks(w.shape)
+            self._scale_views.append((key, scale_stride, n_blk, (rows, n_blk // rows)))
+            entries.append(_ffi.DfqBatchMxTensor(batch._in_slot(key, 'weight', w), rows, w.numel() // rows, c_off, scale_stride))
+            scale_stride += -(-n_blk // 16) * 16
+        F = len(self.widths)
+        self.error_block = torch.zeros((n_nets, self.n_tensors, F), dtype=torch.float64, device=dev)
+        self.cost_block = self.error_block
+        self.code_dtype = torch.uint8 if codes else None
+        self.code_block = torch.zeros((n_nets, code_stride), dtype=torch.uint8, device=dev) if codes else None
+        self.scale_block = torch.zeros((n_nets, scale_stride), dtype=torch.uint8, device=dev)
+        self.status_block = torch.zeros((n_nets,), dtype=torch.int32, device=dev)
+        self.bits_block, self.budget, self._mixed = None, self.elements * self.bit_weight, None
+        cfg = _ffi.DfqBatchMxConfig((ctypes.c_int32 * 3)(*(list(self.widths) + [0] * (3 - F))), F, _MX_FP6[fp6], _MX_FP8[fp8],
+                                    int(self.search), int(self.apply), self.bit_weight, 0)
+        arr = (_ffi.DfqBatchMxTensor * len(entries))(*entries)
+        self._create((arr, len(entries), ctypes.byref(cfg)), self.error_block.data_ptr(),
+                     None if self.code_block is None else self.code_block.data_ptr(), code_stride, self.scale_block.data_ptr(), scale_stride)
+
+    def run(self, stages=None):
+        """Enqueue the plan on the current stream.  ``stages=None``: ERRORS and, with ``apply``, QUANTISE.  Else
+        ``BatchMxPlan.ERRORS``, ``QUANTISE`` or their sum (dfq_batch_mx_plan_run_stages), whatever ``apply`` says."""
+        if stages is None:
+            return super().run()
+        if self._batch.storage is None:
+            raise RuntimeError('NetworkBatch: the batch has been released')
+        if not self._plan:
+            raise RuntimeError('BatchMxPlan: the plan has been closed')
+        _ffi.check(_ffi.lib().dfq_batch_mx_plan_run_stages(self._plan, int(stages), _ffi.stream_arg()))
+
+    def set_widths(self, mixed):
+        """Quantise every layer of every network at the width read on the device by every later QUANTISE
+        (dfq_batch_mx_plan_set_widths): ``mixed`` is a BatchMixedPlan of this batch whose widths are all candidates of this plan
+        -- its ``bits_block`` is read --, or an int32 tensor [n_nets, T] on the batch's device in the order of ``keys``.  A width
+        that is no candidate leaves that layer of that network untouched and makes ``status(n)`` 2.  None: at ``bit_weight``
+        again.  The call synchronises; a ``pack_plan`` made of this plan before it refuses to run."""
+        if not self._plan:
+            raise RuntimeError('BatchMxPlan: the plan has been closed')
+        lib = _ffi.lib()
+        if mixed is None:
+            _ffi.check(lib.dfq_batch_mx_plan_set_widths(self._plan, None, 0, None, None))
+            self.bits_block, self.budget, self._mixed = None, self.elements * self.bit_weight, None
+            return
+        if isinstance(mixed, BatchMixedPlan):
+            if mixed._batch is not self._batch:
+                raise ValueError('mx_plan: set_widths got a mixed_plan of another batch')
+            if not set(mixed.widths) <= set(self.widths):
+                raise ValueError('mx_plan: the widths {!r} of the mixed_plan are not all among {!r}'.format(mixed.widths, self.widths))
+            if list(mixed.keys) != self.keys:               # (pack_plan reads column i of the block for tensor i of this plan)
+                raise ValueError('mx_plan: the layers of the mixed_plan are not this plan\'s, in its order')
+            order, block, budget = list(range(self.n_tensors)), mixed.bits_block, mixed.budget
+        elif isinstance(mixed, torch.Tensor):
+            if mixed.dtype != torch.int32 or tuple(mixed.shape) != (self.n_nets, self.n_tensors) or not mixed.is_contiguous() \
+                    or mixed.device != self.status_block.device:
+                raise ValueError('mx_plan: a width block must be a contiguous int32 tensor [{}, {}] on {}'.format(
+                    self.n_nets, self.n_tensors, self.status_block.device))
+            order, block, budget = list(range(self.n_tensors)), mixed, self.elements * self.widths[-1]
+        else:
+            raise ValueError('mx_plan: set_widths takes a mixed_plan of this batch, an int32 tensor or None, got {!r}'.format(
+                type(mixed).__name__))
+        index = (ctypes.c_int32 * self.n_tensors)(*order)
+        _ffi.check(lib.dfq_batch_mx_plan_set_widths(self._plan, block.data_ptr(), block.shape[1], index, self.status_block.data_ptr()))
+        self.bits_block, self.budget, self._mixed = block, budget, mixed       # (kept alive while the plan reads it)
+
+    def status(self, n):
+        """0, or 2: a width network n's row of the device block held at the last QUANTISE was none of ``widths``, and that layer
+        was left as it was; always 0 without device widths"""
+        return int(self.status_block[n].cpu())
+
+    def codes(self, n):
+        """{graph key: uint8 codes of network n's weight, shaped like it} -- views of the code block; {} without codes"""
+        if self.code_block is None:
+            return {}
+        row = self.code_block[n]
+        return OrderedDict((key, row[off:off + numel].view(shape)) for (key, off, numel, shape) in self._code_views)
+
+    def scales(self, n):
+        """{graph key: uint8 [rows, ceil(row_len / 32)]}: the scale bytes of network n's weight -- views of the scale block"""
+        row = self.scale_block[n]
+        return OrderedDict((key, row[off:off + n_blk].view(shape)) for (key, off, n_blk, shape) in self._scale_views)
+
+    def errors(self, n):
+        """``OrderedDict[graph key -> float64 numpy [F]]``: sum e^2 of network n's weight at every width of ``widths``"""
+        e = self.error_block[n].cpu().numpy()
+        return OrderedDict((key, e[i].copy()) for i, key in enumerate(self.keys))
+
+
 _PACKED_VERSION = 1            # of the file save_packed writes
+_PACKED_MX_VERSION = 2         # of the file save_packed writes for an MX source (mx_scales, mx_format6, mx_format8, mx_block)
 _PACK_MAX_BITS = 16
 
 
@@ -1401,11 +1631,21 @@ def _extent_words(numel, bits):
     return -(-words // 4) * 4
 
 
+class _MxScales:
+    """What MX-packed words need besides themselves: ``scale_block`` uint8 [n_nets, scale_stride], its views
+    [(key, offset, blocks, (rows, blocks per row))] and the formats of the 6- and 8-bit codes ('e2m3' / 'e3m2', 'e4m3' / 'e5m2')"""
+
+    def __init__(self, scale_block, views, fp6, fp8):
+        self.scale_block, self.views, self.fp6, self.fp8 = scale_block, list(views), fp6, fp8
+
+
 class _Packed:
     """What a BatchPackPlan and a loaded PackedBatch share -- the packed words of a batch and what unpacking them needs:
     ``packed_block`` int32 [n_nets, word_stride] (the raw uint32 words), ``offset_block`` int64 [n_nets, T + 1],
     ``status_block`` int32 [n_nets], ``range_block`` float32 [n_nets, range_stride], the widths -- one for all (``bits``), or
-    ``bits_block`` int32 [n_nets, T] on the device (``bits == 0``) --, ``keys``, ``per_channel`` and ``signed``."""
+    ``bits_block`` int32 [n_nets, T] on the device (``bits == 0``) --, ``keys``, ``per_channel`` and ``signed``.  ``mx``: None,
+    or the _MxScales of words that hold MX codes (``range_block`` is then None)."""
+    mx = None
 
     def words(self, n):
         """``OrderedDict[graph key -> int32 view]`` of network n's packed words, tensor by tensor (one device-to-host copy of
@@ -1439,8 +1679,9 @@ class BatchPackPlan(_BatchPlan, _Packed):
     _c = 'dfq_batch_pack_plan'
 
     def __init__(self, batch, source, word_stride):
-        if not isinstance(source, (BatchQuantPlan, BatchSquantPlan, BatchMixedPlan)):
-            raise ValueError('pack_plan: the source must be a quant_plan, squant_plan or mixed_plan, got {!r}'.format(type(source).__name__))
+        if not isinstance(source, (BatchQuantPlan, BatchSquantPlan, BatchMixedPlan, BatchMxPlan)):
+            raise ValueError('pack_plan: the source must be a quant_plan, squant_plan, mixed_plan or mx_plan, got {!r}'.format(
+                type(source).__name__))
         if source._batch is not batch:
             raise ValueError('pack_plan: the source is a plan of another batch')
         if not source._plan:
@@ -1464,6 +1705,8 @@ class BatchPackPlan(_BatchPlan, _Packed):
         self.per_channel, self.signed = source.per_channel, source.signed
         self.range_block, self.code_block, self.code_dtype = source.range_block, source.code_block, source.code_dtype
         self.n_nets, self.n_tensors = len(batch.nets), len(views)
+        # an MX source: the scale bytes and the two format ids travel with the words (unpack_plan decodes with them)
+        self.mx = _MxScales(source.scale_block, source._scale_views, source.fp6, source.fp8) if isinstance(source, BatchMxPlan) else None
         self.bits = 0 if layered else int(source.bit_weight)
         self.bits_block = source.bits_block if layered else None
         if not layered and not 1 <= self.bits <= _PACK_MAX_BITS:
@@ -1500,10 +1743,12 @@ class PackedBatch(_Packed):
 
     def __init__(self, batch, path):
         with np.load(path, allow_pickle=False) as f:
-            if 'version' not in f.files or int(f['version']) != _PACKED_VERSION:
-                raise ValueError('load_packed: {} has format version {}, this library reads version {}'.format(
-                    path, int(f['version']) if 'version' in f.files else None, _PACKED_VERSION))
-            need = ['keys', 'shapes', 'offsets', 'widths', 'ranges', 'per_channel', 'signed', 'bias_keys', 'biases']
+            if 'version' not in f.files or int(f['version']) not in (_PACKED_VERSION, _PACKED_MX_VERSION):
+                raise ValueError('load_packed: {} has format version {}, this library reads versions {} and {} (MX)'.format(
+                    path, int(f['version']) if 'version' in f.files else None, _PACKED_VERSION, _PACKED_MX_VERSION))
+            is_mx = int(f['version']) == _PACKED_MX_VERSION
+            need = ['keys', 'shapes', 'offsets', 'widths', 'per_channel', 'signed', 'bias_keys', 'biases']
+            need += ['mx_scales', 'mx_format6', 'mx_format8', 'mx_block'] if is_mx else ['ranges']
             need += ['words_{}'.format(n) for n in range(len(batch.nets))]
             missing = [k for k in need if k not in f.files]
             if missing:
@@ -1524,13 +1769,30 @@ class PackedBatch(_Packed):
         self._views = [(k, int(np.prod(s)), s) for k, s in zip(keys, shapes)]
         self.per_channel, self.signed = bool(data['per_channel']), bool(data['signed'])
         self._range_views, at = [], 0
-        for k, s in zip(keys, shapes):
-            shape = (s[0], 2) if self.per_channel else (2,)
-            self._range_views.append((k, at, shape))
-            at += _range_floats(shape)
-        ranges = np.ascontiguousarray(data['ranges'], dtype=np.float32)
-        if ranges.shape != (n_nets, at):
-            raise ValueError('load_packed: {} holds {} range values per network, the batch needs {}'.format(path, ranges.shape[-1], at))
+        dev = batch.stage.device
+        if is_mx:
+            fp6 = {v: k for k, v in _MX_FP6.items()}.get(int(data['mx_format6']))
+            fp8 = {v: k for k, v in _MX_FP8.items()}.get(int(data['mx_format8']))
+            if int(data['mx_block']) != _ffi.MX_BLOCK or fp6 is None or fp8 is None:
+                raise ValueError('load_packed: {}: MX block length {} or format ids ({}, {}) this library does not read'.format(
+                    path, int(data['mx_block']), int(data['mx_format6']), int(data['mx_format8'])))
+            views = []
+            for k, s in zip(keys, shapes):
+                views.append((k, at, _mx_blocks(s), (s[0], _mx_blocks(s) // s[0])))
+                at += _mx_blocks(s)
+            scales = np.ascontiguousarray(data['mx_scales'], dtype=np.uint8)
+            if scales.shape != (n_nets, at):
+                raise ValueError('load_packed: {} holds {} scale bytes per network, the batch needs {}'.format(path, scales.shape[-1], at))
+            self.mx = _MxScales(torch.from_numpy(scales).to(dev), views, fp6, fp8)
+            ranges = None
+        else:
+            for k, s in zip(keys, shapes):
+                shape = (s[0], 2) if self.per_channel else (2,)
+                self._range_views.append((k, at, shape))
+                at += _range_floats(shape)
+            ranges = np.ascontiguousarray(data['ranges'], dtype=np.float32)
+            if ranges.shape != (n_nets, at):
+                raise ValueError('load_packed: {} holds {} range values per network, the batch needs {}'.format(path, ranges.shape[-1], at))
         words = [np.ascontiguousarray(data['words_{}'.format(n)]).view(np.uint32) for n in range(n_nets)]
         if any(len(w) != int(offsets[n, -1]) for n, w in enumerate(words)):
             raise ValueError('load_packed: {}: a network\'s words are not as many as its offsets say'.format(path))
@@ -1538,11 +1800,10 @@ class PackedBatch(_Packed):
         host = np.zeros((n_nets, self.word_stride), dtype=np.uint32)
         for n, w in enumerate(words):
             host[n, :len(w)] = w
-        dev = batch.stage.device
         self.packed_block = torch.from_numpy(host.view(np.int32)).to(dev)
         self.offset_block = torch.from_numpy(offsets).to(dev)
         self.status_block = torch.zeros((n_nets,), dtype=torch.int32, device=dev)
-        self.range_block = torch.from_numpy(ranges).to(dev)
+        self.range_block = None if ranges is None else torch.from_numpy(ranges).to(dev)
         self.bits, self.bits_block = 0, torch.from_numpy(widths).to(dev)
         self._bias_keys = [str(k) for k in data['bias_keys']]
         self._biases = np.ascontiguousarray(data['biases'], dtype=np.float32)
@@ -1576,6 +1837,12 @@ class BatchUnpackPlan(_BatchPlan):
         self._packed = packed
         self.keys, self.n_nets, self.n_tensors = list(packed.keys), len(batch.nets), len(packed.keys)
         self.per_channel, self.signed = packed.per_channel, packed.signed
+        self._decode = self.decode_status_block = None
+        if packed.mx is not None:
+            if codes == 'int32':
+                raise ValueError("unpack_plan: MX codes are one byte wide (codes=None or 'int8')")
+            self._init_mx(batch, packed, weights, g0)
+            return
         dev = batch.stage.device
         rng = {key: off for (key, off, _) in packed._range_views}
         entries, self._code_views, code_stride = [], [], 0
@@ -1598,6 +1865,58 @@ class BatchUnpackPlan(_BatchPlan):
                      None if self.code_block is None else self.code_block.data_ptr(), 1 if codes == 'int8' else 4, code_stride,
                      self.status_block.data_ptr())
 
+    def _init_mx(self, batch, packed, weights, g0):
+        """MX-packed words: the unpack launch to one-byte codes in ``code_block`` (always kept: the decode reads them), then, with
+        ``weights``, one decode launch (dfq_batch_mx_decode_plan) from the codes and the scale bytes to the weights in place.
+        ``decode_status_block`` is the second launch's status.  The decode launch is gated on ``status_block``: a network the
+        unpack launch skipped is not decoded, its weights stay as they were, as on the integer path."""
+        dev, lib = batch.stage.device, _ffi.lib()
+        P, D = _ffi.DfqBatchUnpackTensor, _ffi.DfqBatchMxDecodeTensor
+        scale_at = {key: off for (key, off, _, _) in packed.mx.views}
+        entries, decode, self._code_views, code_stride = [], [], [], 0
+        for i, (key, numel, shape) in enumerate(packed._views):
+            rows = int(shape[0])
+            entries.append(P(None, rows, numel // rows, code_stride, numel, -1, packed.bits, i, 0, 0))
+            if weights:
+                decode.append(D(batch._in_slot(key, 'weight', g0[key].weight), rows, numel // rows, code_stride, scale_at[key], packed.bits, i))
+            self._code_views.append((key, code_stride, numel, tuple(shape)))
+            code_stride += -(-numel // 64) * 64
+        self.code_dtype = torch.uint8
+        self.code_block = torch.zeros((self.n_nets, code_stride), dtype=torch.uint8, device=dev)
+        self.status_block = torch.zeros((self.n_nets,), dtype=torch.int32, device=dev)
+        self.decode_status_block = torch.zeros((self.n_nets,), dtype=torch.int32, device=dev)
+        widths = None if packed.bits_block is None else packed.bits_block.data_ptr()
+        arr = (P * len(entries))(*entries)
+        self._create((arr, len(entries)), packed.packed_block.data_ptr(), packed.packed_block.shape[1], packed.offset_block.data_ptr(),
+                     widths, self.n_tensors, None, 0, self.code_block.data_ptr(), 1, code_stride, self.status_block.data_ptr())
+        if weights:
+            darr = (D * len(decode))(*decode)
+            handle = ctypes.c_void_p()
+            scales = packed.mx.scale_block
+            try:
+                _ffi.check(lib.dfq_batch_mx_decode_plan_create(darr, len(decode), batch.bases.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)),
+                                                               self.n_nets, self.code_block.data_ptr(), code_stride, scales.data_ptr(),
+                                                               scales.shape[1], widths, self.n_tensors, _MX_FP6[packed.mx.fp6],
+                                                               _MX_FP8[packed.mx.fp8], self.status_block.data_ptr(),
+                                                               self.decode_status_block.data_ptr(), ctypes.byref(handle)))
+            except Exception:
+                self.close()                                # (the unpack plan made above)
+                raise
+            self._decode = handle
+            self.launches += int(lib.dfq_batch_mx_decode_plan_launches(handle))
+
+    def run(self):
+        """Enqueue the unpack launch and, for MX-packed words with ``weights``, the decode launch behind it."""
+        super().run()
+        if self._decode:
+            _ffi.check(_ffi.lib().dfq_batch_mx_decode_plan_run(self._decode, _ffi.stream_arg()))
+
+    def close(self):
+        if getattr(self, '_decode', None):
+            _ffi.lib().dfq_batch_mx_decode_plan_destroy(self._decode)
+            self._decode = None
+        super().close()
+
     def codes(self, n):
         """{graph key: integer codes of network n's weight, shaped like it} -- views of the code block; {} without codes"""
         if self.code_block is None:
@@ -1605,9 +1924,16 @@ class BatchUnpackPlan(_BatchPlan):
         row = self.code_block[n]
         return OrderedDict((key, row[off:off + numel].view(shape)) for (key, off, numel, shape) in self._code_views)
 
+    def statuses(self):
+        """[n_nets] ints, one device-to-host copy: ``status(n)`` of every network"""
+        block = self.status_block
+        if self.decode_status_block is not None:            # (MX-packed words: the decode launch has a status of its own)
+            block = torch.maximum(block, self.decode_status_block)
+        return block.cpu().tolist()
+
     def status(self, n):
         """0, or 1 / 2: network n was skipped (its offsets do not fit its widths / a width on the device is no width)"""
-        return int(self.status_block[n].cpu())
+        return self.statuses()[n]
 
 
 def _kernel_len(w):

@@ -148,6 +148,33 @@ def squant_rows(x, kernel_len=1, num_bits=8, min_values=None, max_values=None, s
         return res[0] if len(res) == 1 else tuple(res)
 
 
+MX_FORMATS = {'e2m1': _ffi.MX_E2M1, 'e2m3': _ffi.MX_E2M3, 'e3m2': _ffi.MX_E3M2, 'e4m3': _ffi.MX_E4M3, 'e5m2': _ffi.MX_E5M2}
+
+
+def mx_rows(x, format='e2m1', search=True):
+    """MX block-scaled quantisation (dfq_mx_rows, "MX block-scaled" in include/dfq_hip.h) of the rows of `x` (first dimension):
+    every run of 32 consecutive elements of a row -- the last one of a row may be short -- shares one power-of-two scale, and
+    an element becomes the nearest code of `format` ('e2m1', 'e2m3', 'e3m2', 'e4m3' or 'e5m2'; ties to the even code,
+    saturating).  ``search`` chooses between the floor exponent and the one above it by the block's own sum of squared errors.
+    Returns (the stored weights shaped like `x`, uint8 codes shaped like `x`, uint8 scale bytes [rows, ceil(row_len / 32)],
+    float64 block errors of the same shape).  One launch."""
+    if format not in MX_FORMATS:
+        raise ValueError('mx_rows: format must be one of {}, got {!r}'.format(sorted(MX_FORMATS), format))
+    lib = _ffi.lib()
+    with torch.no_grad():
+        stage = _ffi.Stage()
+        xx = stage.bind(x)
+        rows, row_len = xx.shape[0], xx[0].numel()
+        bpr = -(-row_len // _ffi.MX_BLOCK)
+        y = stage.new(xx.shape)
+        codes = stage.new(xx.shape, dtype=torch.uint8)
+        scales = stage.new((rows, bpr), dtype=torch.uint8)
+        err = stage.new((rows, bpr), dtype=torch.float64)
+        _ffi.check(lib.dfq_mx_rows(_ffi.ptr(xx), _ffi.ptr(y), rows, row_len, MX_FORMATS[format], int(bool(search)), _ffi.ptr(codes),
+                                   _ffi.ptr(scales), _ffi.ptr(err), _ffi.stream_arg()))
+        return tuple(stage.out_like(x, t) for t in (y, codes, scales, err))
+
+
 def zeroq_quant_rows(x, num_bits=8, min_values=None, max_values=None, return_codes=False):
     """ZeroQ's per-output-channel asymmetric quantiser (quant_utils.py:85-135 via quant_modules.py:161-171)."""
     lib = _ffi.lib()

@@ -1076,6 +1076,144 @@ void dfq_batch_unpack_plan_destroy(dfq_batch_unpack_plan* plan);
 /* kernel launches per run (1) */
 int32_t dfq_batch_unpack_plan_launches(const dfq_batch_unpack_plan* plan);
 
+/* MX block-scaled FP4 / FP6 / FP8 weights (extension; the OCP Microscaling formats the block-scaled f8f6f4 MFMA of gfx950
+ * multiplies natively: 32 elements share one E8M0 scale).  Weights only; no activation, no matmul, no bias correction or adaptive
+ * rounding on these grids.
+ * DEFINITION.
+ *   formats     id, bits, exponent / mantissa bits, bias, largest magnitude, emax:
+ *                 DFQ_MX_E2M1 = 0: 4 bits, 2 / 1, bias  1, largest 6,                          emax  2
+ *                 DFQ_MX_E2M3 = 1: 6 bits, 2 / 3, bias  1, largest 7.5,                        emax  2
+ *                 DFQ_MX_E3M2 = 2: 6 bits, 3 / 2, bias  3, largest 28,                         emax  4
+ *                 DFQ_MX_E4M3 = 3: 8 bits, 4 / 3, bias  7, largest 448   = magnitude code 126, emax  8
+ *                 DFQ_MX_E5M2 = 4: 8 bits, 5 / 2, bias 15, largest 57344 = magnitude code 123, emax 15
+ *               A code is sign bit | exponent | mantissa in the low `bits` bits of a byte.  Subnormals (exponent field 0) are
+ *               kept: value(k) = m 2^(1 - bias - M) for exponent field 0, (2^M + m) 2^(x - bias - M) for field x > 0 (M mantissa
+ *               bits).  The magnitude codes 0..cmax are monotone in value.  No Inf or NaN code is ever written: conversion
+ *               saturates to cmax (the OCP specification leaves overflow implementation-defined for E5M2; this is the choice).
+ *   blocks      A tensor is [rows, row_len].  Row r is cut into bpr = ceil(row_len / 32) blocks of DFQ_MX_BLOCK = 32 consecutive
+ *               elements; the last block of a row may be short, no block crosses a row.  Block (r, j) has scale byte
+ *               s[r * bpr + j].
+ *   exponent    amax = max |w| over the block.  E = the unbiased exponent field of amax as a float32, -127 for a zero or
+ *               subnormal amax.  e0 = max(E - emax, -127).  search = 0: e = e0.  search = 1: e is the one of {e0, e0 + 1}
+ *               with the smaller block error S(e); e0 on a tie or if either S is NaN.  S(e) = sum d^2 with
+ *               d = (double)stored - (double)w: one float64 subtraction and one float64 multiplication per element, added as a
+ *               balanced binary tree over the element's index in the block -- level m pairs index i with i xor m, for
+ *               m = 1, 2, 4, 8, 16, absent elements counting as +0.0 -- so the choice is a pure function of the block.
+ *               Scale byte s = e + 127, in [0, 254].
+ *   element     v = w 2^(-e) in real arithmetic (|v| < 2^(emax + 1)).  The magnitude code is the code nearest to |v|, a tie going
+ *               to the even code (IEEE round to nearest even); everything at or above the largest magnitude goes to cmax.  The
+ *               sign bit is w's, so -0.0 and negative values that round to zero keep it.
+ *   stored      stored = +-value(code) 2^e, exact in float32 for every format and every e >= -127 down to 2^-143: subnormal
+ *               float32 results are exact and no flush mode is relied on (the conversion is integer arithmetic on the bit
+ *               pattern).  One corner is not representable: amax in the top binade under e0 + 1 can round up to 2^128; the stored
+ *               value is then +-Inf, S(e0 + 1) = Inf, and the search keeps e0 -- no Inf is ever stored.
+ *   non-finite  A block holding any NaN or +-Inf gets scale byte 255; its codes are 0, its stored weights all the quiet NaN
+ *               0x7fc00000, and its tensor's errors NaN at every format.  No other block or tensor is affected.
+ *   errors      E[n][t][f] = sum d^2 over tensor t of network n for candidate format f, float64 -- all candidates from ONE read
+ *               of the weight.  The order is the plan's own: a workgroup adds the S of its DFQ_MX_BLOCK-blocks (64 consecutive
+ *               ones of one tensor) in a fixed order into one partial sum, a second launch adds a tensor's partial sums in a
+ *               fixed order.  It depends on the tensor's shape alone and uses no floating-point atomic: two runs are bit-equal,
+ *               and network n's values depend neither on n_nets nor on n's place in the batch.
+ *   decode      codes, scale bytes and a width give the stored weights by `stored` above; s = 255 makes the block the quiet NaN.
+ *               Magnitude codes above cmax, which the quantiser never writes, decode by the same formula.
+ * dfq_mx_rows: one tensor, one launch.  y (float32 [rows, row_len], may be x), codes (uint8, one per element), scales (uint8
+ * [rows * bpr]) and err (float64 [rows * bpr]: the S(e) of every block, by the tree above, NaN for a non-finite block) are each
+ * written unless NULL.  DFQ_ERR_ARG for a null x, an x that is not 4-byte aligned, rows or row_len <= 0, row_len above 2^31 - 1, more than 2^29 blocks, an
+ * unknown format.
+ * The batch plan, in the shape of dfq_batch_squant_plan and dfq_batch_mixed_plan: the table describes network 0, network n's copy
+ * of a tensor lies bases[n] - bases[0] bytes further.  The blocks are the caller's: errors float64 [n_nets, n_tensors, F]
+ * (F = n_widths), codes uint8 [n_nets, code_stride], scales uint8 [n_nets, scale_stride], status int32 [n_nets].
+ *   config      widths: the candidates, a rising subset of (4, 6, 8); width 4 is E2M1, widths 6 and 8 are format6 (E2M3 or E3M2)
+ *               and format8 (E4M3 or E5M2); `search` as above; `num_bits`: the width to quantise at when no device widths are
+ *               set, one of the candidates (read with `apply` only).
+ *   stages      DFQ_MX_ERRORS reads every weight once and writes nothing but `errors` (and the plan's own partial sums): two
+ *               launches.  DFQ_MX_QUANTISE reads every weight once and writes the stored weight in place, the code byte and the
+ *               block's scale byte: one launch.  dfq_batch_mx_plan_run is ERRORS, followed by QUANTISE with `apply`;
+ *               dfq_batch_mx_plan_launches counts those (2 or 3).  dfq_batch_mx_plan_run_stages runs any of the two, whatever
+ *               `apply` says; the stages keep no state in the plan.
+ *   set_widths  dfq_batch_squant_plan_set_widths' contract: with `widths` set -- int32 on the device, [n_nets, width_stride] --
+ *               every later QUANTISE treats tensor t of network n at widths[n * width_stride + width_index[t]], bit for bit as a
+ *               plan with that num_bits.  A width that is none of the plan's candidates makes the items of that (network, tensor)
+ *               write nothing -- no weight, code or scale byte of it is touched -- and status[n] becomes 2; every QUANTISE with
+ *               widths set clears `status` first with a memset on the stream.  NULL restores `num_bits`; `status` is then not
+ *               touched.  A call with `widths` set synchronises.  DFQ_ERR_ARG for a null plan, widths without width_index or
+ *               status, an index that is negative or >= width_stride.
+ * No workgroup waits for another; half a wave takes a block, a lane an element.  create: DFQ_ERR_ARG (and dfq_last_error) for
+ * null or empty tables, a null configuration, widths that are no rising subset of (4, 6, 8), a format id that does not match
+ * its width, `apply` with a num_bits that is no candidate, rows or row_len <= 0, row_len above 2^31 - 1, a weight that is null or
+ * not 4-byte aligned, offsets outside their strides, a null errors block (it is what ERRORS writes), a null code or scale block
+ * that a tensor's offset >= 0 points into, null bases, networks that are not 16-byte aligned to network 0.  run_stages: a null
+ * plan, stages that are 0 or hold an unknown bit.  Synchronises (create only); run is asynchronous on `stream`. */
+#define DFQ_MX_E2M1 0
+#define DFQ_MX_E2M3 1
+#define DFQ_MX_E3M2 2
+#define DFQ_MX_E4M3 3
+#define DFQ_MX_E5M2 4
+#define DFQ_MX_BLOCK 32
+#define DFQ_MX_ERRORS 1
+#define DFQ_MX_QUANTISE 2
+int dfq_mx_rows(const float* x, float* y, int64_t rows, int64_t row_len, int32_t format, int32_t search, uint8_t* codes, uint8_t* scales,
+                double* err, void* stream);
+
+typedef struct dfq_batch_mx_plan dfq_batch_mx_plan;
+typedef struct dfq_batch_mx_tensor {
+    float* data;            /* device, inside network 0's slot; [rows, row_len], quantised in place                  */
+    int64_t rows;
+    int64_t row_len;
+    int64_t code_offset;    /* bytes into a network's code row (one per element), or -1                              */
+    int64_t scale_offset;   /* bytes into a network's scale row (rows * ceil(row_len / 32) of them), or -1           */
+} dfq_batch_mx_tensor;
+typedef struct dfq_batch_mx_config {
+    int32_t widths[3];      /* the candidates: a rising subset of (4, 6, 8)                                          */
+    int32_t n_widths;       /* F                                                                                     */
+    int32_t format6;        /* DFQ_MX_E2M3 or DFQ_MX_E3M2                                                            */
+    int32_t format8;        /* DFQ_MX_E4M3 or DFQ_MX_E5M2                                                            */
+    int32_t search;
+    int32_t apply;          /* run: QUANTISE behind ERRORS                                                           */
+    int32_t num_bits;       /* the width QUANTISE works at without device widths                                     */
+    int32_t pad;
+} dfq_batch_mx_config;
+int dfq_batch_mx_plan_create(const dfq_batch_mx_tensor* tensors, int32_t n_tensors, const dfq_batch_mx_config* config,
+                             const void* const* bases, int32_t n_nets, double* errors, uint8_t* codes, int64_t code_stride,
+                             uint8_t* scales, int64_t scale_stride, dfq_batch_mx_plan** out_plan);
+int dfq_batch_mx_plan_run(dfq_batch_mx_plan* plan, void* stream);
+int dfq_batch_mx_plan_run_stages(dfq_batch_mx_plan* plan, int32_t stages, void* stream);
+int dfq_batch_mx_plan_set_widths(dfq_batch_mx_plan* plan, const int32_t* widths /* device int32 [n_nets, width_stride], or NULL */,
+                                 int64_t width_stride, const int32_t* width_index /* host [n_tensors], read here only */,
+                                 int32_t* status /* device int32 [n_nets] */);
+void dfq_batch_mx_plan_destroy(dfq_batch_mx_plan* plan);
+int32_t dfq_batch_mx_plan_launches(const dfq_batch_mx_plan* plan);
+
+/* The way back: ONE launch that turns one-byte codes and scale bytes into the stored weights, in place in the batch (`decode`
+ * above).  Per tensor `num_bits` is 4, 6 or 8, or 0 and the width is read on the device from `widths` [n_nets, width_stride] at
+ * width_index.  A device width other than 4, 6 or 8 leaves that (network, tensor) untouched and stores status[n] = 2; with any
+ * num_bits = 0 every run clears `status` (int32 [n_nets]) first with a memset on the stream, otherwise `status` may be NULL and
+ * is not touched.  `gate`: NULL, or int32 on the device, [n_nets]: a network whose word is not 0 when the launch runs is left
+ * untouched, weights and status -- the status block of the unpack launch in front, so that a network unpack skipped is not
+ * decoded from codes nobody wrote.  It reads no weight.  create: DFQ_ERR_ARG for null or empty tables, a null code or scale block, a num_bits
+ * outside {0, 4, 6, 8}, num_bits = 0 with a null width or status block, a width_index outside width_stride, a format id that
+ * does not match its width, rows or row_len <= 0, row_len above 2^31 - 1, a weight that is null or not 4-byte aligned, offsets
+ * outside their strides, null bases, networks that are not 16-byte aligned to network 0. */
+typedef struct dfq_batch_mx_decode_plan dfq_batch_mx_decode_plan;
+typedef struct dfq_batch_mx_decode_tensor {
+    float* data;            /* the weight in network 0, [rows, row_len], written in place                            */
+    int64_t rows;
+    int64_t row_len;
+    int64_t code_offset;    /* bytes into a network's code row                                                       */
+    int64_t scale_offset;   /* bytes into a network's scale row                                                      */
+    int32_t num_bits;       /* 4, 6, 8, or 0: read the width block                                                   */
+    int32_t width_index;
+} dfq_batch_mx_decode_tensor;
+int dfq_batch_mx_decode_plan_create(const dfq_batch_mx_decode_tensor* tensors, int32_t n_tensors, const void* const* bases,
+                                    int32_t n_nets, const uint8_t* codes, int64_t code_stride, const uint8_t* scales,
+                                    int64_t scale_stride, const int32_t* widths, int64_t width_stride, int32_t format6,
+                                    int32_t format8, const int32_t* gate /* device int32 [n_nets], or NULL */, int32_t* status,
+                                    dfq_batch_mx_decode_plan** out_plan);
+int dfq_batch_mx_decode_plan_run(dfq_batch_mx_decode_plan* plan, void* stream);
+void dfq_batch_mx_decode_plan_destroy(dfq_batch_mx_decode_plan* plan);
+/* kernel launches per run (1) */
+int32_t dfq_batch_mx_decode_plan_launches(const dfq_batch_mx_decode_plan* plan);
+
 /* Analytic activation ranges of a whole batch of networks of one architecture (extension; set_quant_minmax,
  * utils/layer_transform.py:347-609, main_cls.py:188, for every network of a batch at once).  The caller walks the graph of
  * the FIRST network once (find_prev_bn, :299-344, and the branch grouping of :476-580) and hands over what the walk found
