@@ -341,6 +341,7 @@ SIGNATURES = {
     'dfq_batch_unpack_plan_destroy': (None, [c_void_p]),
     'dfq_batch_unpack_plan_launches': (c_int32, [c_void_p]),
     'dfq_mx_rows': (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dfq_mx_axis': (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dfq_batch_mx_plan_create': (c_int32, [POINTER(DfqBatchMxTensor), c_int32, POINTER(DfqBatchMxConfig), POINTER(c_void_p), c_int32,
                                            c_void_p, c_void_p, c_int64, c_void_p, c_int64, POINTER(c_void_p)]),
     'dfq_batch_mx_plan_run': (c_int32, [c_void_p, c_void_p]),

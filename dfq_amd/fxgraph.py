@@ -163,7 +163,7 @@ def _trace(model, key_style='name'):
 TENSOR_OPS = ('add', 'cat', 'mean', 'interpolate', 'softmax')
 
 
-def quantize_tensor_ops(model, ops=TENSOR_OPS, num_bits=8, momentum=0.1, key_style='name'):
+def quantize_tensor_ops(model, ops=TENSOR_OPS, num_bits=8, momentum=0.1, key_style='name', quant_cls=None):
     """Activation quantisers on the inputs of tensor ops -- what the reference's ``switch_layers(quant_op=True)``
     + ``replace_op`` achieve by monkey-patching ``torch.Tensor.__add__`` / ``torch.cat`` / ``torch.mean`` /
     ``F.interpolate`` / ``F.softmax`` and routing their inputs through a ``CustomTensorOP`` container
@@ -174,8 +174,11 @@ def quantize_tensor_ops(model, ops=TENSOR_OPS, num_bits=8, momentum=0.1, key_sty
     ``trace(model)`` (the quantisers live on the edges, they are no graph nodes, as in the reference);
     ``tensor_op_quant`` maps the graph key of each rewritten op to its quantisers in input order and is what
     ``set_quant_minmax(..., tensor_op_quant=...)`` fills.  The GraphModule shares all layers with ``model``.
+    ``quant_cls``: the quantiser's class, called as ``quant_cls(num_bits=, momentum=)`` (default QuantMeasure; MXQuantMeasure
+    puts the tensor ops' inputs on the MX block-scaled grid).
     """
     from .utils.quantize import QuantMeasure
+    quant_cls = quant_cls or QuantMeasure
     graph, bottoms, fx_graph, alias = _trace(model, key_style)
     holder = nn.ModuleList()
     tensor_op_quant = OrderedDict()
@@ -197,7 +200,7 @@ def quantize_tensor_ops(model, ops=TENSOR_OPS, num_bits=8, momentum=0.1, key_sty
         for inp in ins:
             if inp in replaced:                 # x + x: one quantiser per distinct edge
                 continue
-            qm = QuantMeasure(num_bits=num_bits, momentum=momentum)
+            qm = quant_cls(num_bits=num_bits, momentum=momentum)
             holder.append(qm)
             with fx_graph.inserting_before(n):
                 qn = fx_graph.call_module('tensor_op_quant.{}'.format(len(holder) - 1), (inp,))

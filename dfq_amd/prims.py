@@ -175,6 +175,46 @@ def mx_rows(x, format='e2m1', search=True):
         return tuple(stage.out_like(x, t) for t in (y, codes, scales, err))
 
 
+def _mx_axis_geometry(who, x, axis, format):
+    """(format id, axis >= 0, outer, len, inner) of `x` cut along `axis`, or the ValueError"""
+    if format not in MX_FORMATS:
+        raise ValueError('{}: format must be one of {}, got {!r}'.format(who, sorted(MX_FORMATS), format))
+    if not isinstance(axis, int) or isinstance(axis, bool) or not -x.dim() <= axis < x.dim():
+        raise ValueError('{}: axis {!r} is outside a tensor of {} dimensions'.format(who, axis, x.dim()))
+    axis %= x.dim()
+    outer = 1
+    for n in x.shape[:axis]:
+        outer *= int(n)
+    inner = 1
+    for n in x.shape[axis + 1:]:
+        inner *= int(n)
+    return MX_FORMATS[format], axis, outer, int(x.shape[axis]), inner
+
+
+def mx_axis(x, axis=1, format='e4m3', search=False, outputs=('y', 'codes', 'scales', 'err')):
+    """MX block-scaled quantisation (dfq_mx_axis, "MX block-scaled" in include/dfq_hip.h) of `x` along `axis` (negative axes
+    count from the end): every run of 32 consecutive elements along that axis -- the last run may be short -- shares one
+    power-of-two scale, all other indices fixed.  Channel blocks of an NCHW activation are ``axis=1``; a 2-D tensor with
+    ``axis=1`` (or any tensor with the last axis) is the row case of mx_rows.  The result is exactly mx_rows on the tensor with
+    the axis moved last, moved back, without the two transposes.  ``search`` as in mx_rows (activations: off by default).
+    Returns (the stored values shaped like `x`, uint8 codes shaped like `x`, uint8 scale bytes and float64 block errors shaped
+    like `x` with `axis` reduced to ceil(len / 32)).  ``outputs`` names the ones that are wanted; the others are not computed
+    and come back as None.  A non-contiguous `x` is made contiguous first.  One launch."""
+    fmt, axis, outer, length, inner = _mx_axis_geometry('mx_axis', x, axis, format)
+    lib = _ffi.lib()
+    with torch.no_grad():
+        stage = _ffi.Stage()
+        xx = stage.bind(x)
+        small = tuple(xx.shape[:axis]) + (-(-length // _ffi.MX_BLOCK),) + tuple(xx.shape[axis + 1:])
+        y = stage.new(xx.shape) if 'y' in outputs else None
+        codes = stage.new(xx.shape, dtype=torch.uint8) if 'codes' in outputs else None
+        scales = stage.new(small, dtype=torch.uint8) if 'scales' in outputs else None
+        err = stage.new(small, dtype=torch.float64) if 'err' in outputs else None
+        _ffi.check(lib.dfq_mx_axis(_ffi.ptr(xx), _ffi.ptr(y), outer, length, inner, fmt, int(bool(search)), _ffi.ptr(codes),
+                                   _ffi.ptr(scales), _ffi.ptr(err), _ffi.stream_arg()))
+        return tuple(None if t is None else stage.out_like(x, t) for t in (y, codes, scales, err))
+
+
 def zeroq_quant_rows(x, num_bits=8, min_values=None, max_values=None, return_codes=False):
     """ZeroQ's per-output-channel asymmetric quantiser (quant_utils.py:85-135 via quant_modules.py:161-171)."""
     lib = _ffi.lib()

@@ -243,6 +243,58 @@ class QuantMeasure(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------
+# MX block-scaled activations and weights (extension: the reference has no such quantiser)
+# ------------------------------------------------------------------------------------------------
+class MXQuantize(torch.autograd.Function):
+    """Straight-through MX block-scaled quantiser: forward on the HIP engine (dfq_mx_axis, the stored values alone -- no codes,
+    no scale bytes, no block errors), backward the identity on the input, as for UniformQuantize."""
+
+    @staticmethod
+    def forward(ctx, input, format, axis, search):
+        from ..prims import mx_axis
+        return mx_axis(input, axis, format, search, outputs=('y',))[0]
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        return grad_output, None, None, None
+
+
+def mx_quantize(x, format='e4m3', axis=1, search=False):
+    """`x` with every block of 32 elements along `axis` on the grid of the OCP MX `format` ('e2m1', 'e2m3', 'e3m2', 'e4m3',
+    'e5m2') under the block's own power-of-two scale: prims.mx_axis(x, axis, format, search)[0], straight-through."""
+    return MXQuantize.apply(x, format, axis, search)
+
+
+class MXQuantMeasure(QuantMeasure):
+    """QuantMeasure's place in a layer, filled by the MX block-scaled quantiser: forward is mx_quantize of the input along
+    `axis` (1: the channels of an NCHW activation, the features of a Linear input).  A block's scale comes from the block
+    itself, so there is no range to track: ``running_min`` / ``running_max``, ``num_bits``, ``momentum`` and ``update_stat``
+    exist, so that every driver step that walks QuantMeasure instances (set_update_stat, update_quant_range, set_quant_minmax,
+    clip_quant_range) runs unchanged over a switched model, and are ignored -- none of them changes an output."""
+
+    def __init__(self, format='e4m3', axis=1, search=False, update_stat=False, num_bits=8, momentum=0.1):
+        super().__init__(update_stat=update_stat, num_bits=num_bits, momentum=momentum)
+        from ..prims import MX_FORMATS
+        if format not in MX_FORMATS:
+            raise ValueError('MXQuantMeasure: format must be one of {}, got {!r}'.format(sorted(MX_FORMATS), format))
+        self.format = format
+        self.axis = axis
+        self.search = search
+
+    def forward(self, input):
+        return mx_quantize(input, self.format, self.axis, self.search)
+
+    def extra_repr(self):
+        return 'format={}, axis={}, search={}'.format(self.format, self.axis, self.search)
+
+
+def _mx_weight(weight, mx):
+    """The weight as NetworkBatch.mx_plan stores it at mx = (format, search): blocks of 32 along each output row."""
+    fmt, search = mx
+    return mx_quantize(weight.reshape(weight.shape[0], -1), fmt, 1, search).reshape(weight.shape)
+
+
+# ------------------------------------------------------------------------------------------------
 # layers
 # ------------------------------------------------------------------------------------------------
 def _quant_weight(weight, num_bits):
@@ -306,7 +358,8 @@ class QConv2d(nn.Conv2d, _ScaleMixin):
             sweight = self.merge_scale_prev(sweight, self.scale_prev)
         if getattr(self, 'scale', None) is not None:
             sweight, sbias = self.merge_scale(sweight, sbias, self.scale)
-        qweight = _quant_weight(sweight, self.num_bits)
+        mx = getattr(self, 'mx_weight', None)
+        qweight = _quant_weight(sweight, self.num_bits) if mx is None else _mx_weight(sweight, mx)
         qbias = quantize(sbias, num_bits=self.num_bits_bias) if sbias is not None else None
         return F.conv2d(input, qweight, qbias, self.stride, self.padding, self.dilation, self.groups)
 
@@ -321,7 +374,8 @@ class QuantConv2d(nn.Conv2d):
 
     def forward(self, input):
         input = self.quant(input)
-        qweight = _quant_weight(self.weight, self.num_bits)
+        mx = getattr(self, 'mx_weight', None)
+        qweight = _quant_weight(self.weight, self.num_bits) if mx is None else _mx_weight(self.weight, mx)
         qbias = quantize(self.bias, num_bits=self.num_bits_bias) if self.bias is not None else None
         return F.conv2d(input, qweight, qbias, self.stride, self.padding, self.dilation, self.groups)
 
@@ -361,7 +415,8 @@ class QLinear(nn.Linear, _ScaleMixin):
             sweight = self.merge_scale_prev(sweight, self.scale_prev)
         if getattr(self, 'scale', None) is not None:
             sweight, sbias = self.merge_scale(sweight, sbias, self.scale)
-        qweight = _quant_weight(sweight, self.num_bits)
+        mx = getattr(self, 'mx_weight', None)
+        qweight = _quant_weight(sweight, self.num_bits) if mx is None else _mx_weight(sweight, mx)
         qbias = quantize(sbias, num_bits=self.num_bits_bias) if sbias is not None else None
         return F.linear(input, qweight, qbias)
 
@@ -376,7 +431,8 @@ class QuantLinear(nn.Linear):
 
     def forward(self, input):
         input = self.quant(input)
-        qweight = _quant_weight(self.weight, self.num_bits)
+        mx = getattr(self, 'mx_weight', None)
+        qweight = _quant_weight(self.weight, self.num_bits) if mx is None else _mx_weight(self.weight, mx)
         qbias = quantize(self.bias, num_bits=self.num_bits_bias) if self.bias is not None else None
         return F.linear(input, qweight, qbias)
 
@@ -402,3 +458,29 @@ def set_layer_bits(graph, bits_weight=8, bits_activation=8, bits_bias=16, targ_t
                 graph[idx].num_bits = bits_weight
             if hasattr(graph[idx], 'num_bits_bias'):
                 graph[idx].num_bits_bias = bits_bias
+
+
+def set_mx_format(graph_or_model, act_format='e4m3', weight_format=None, axis=1, weight_search=True, targ_type=None):
+    """Switch the activation quantiser of every target layer to the MX block-scaled formats: each layer's ``.quant`` becomes an
+    MXQuantMeasure(act_format, axis).  With ``weight_format`` the layer also gets ``mx_weight = (weight_format, weight_search)``,
+    which QConv2d / QuantConv2d / QLinear / QuantLinear read in forward: the weight is then quantised in blocks of 32 along each
+    output row, bit for bit what NetworkBatch.mx_plan stores for it at that format and search, in place of the integer grid.
+    Biases keep their integer quantiser.  ``graph_or_model``: the graph dict of the other set_* helpers, or a module (its
+    submodules are walked).  ``targ_type``: the layer classes to switch; None takes every layer that has a ``.quant``."""
+    from ..prims import MX_FORMATS
+    for what, fmt in (('act_format', act_format), ('weight_format', weight_format)):
+        if fmt not in MX_FORMATS and not (what == 'weight_format' and fmt is None):
+            raise ValueError('set_mx_format: {} must be one of {}, got {!r}'.format(what, sorted(MX_FORMATS), fmt))
+    layers = graph_or_model.modules() if isinstance(graph_or_model, nn.Module) else graph_or_model.values()
+    switched = 0
+    for layer in layers:
+        if not isinstance(layer, nn.Module) or not isinstance(getattr(layer, 'quant', None), QuantMeasure):
+            continue
+        if targ_type is not None and type(layer) not in targ_type:
+            continue
+        weight = getattr(layer, 'weight', None)
+        layer.quant = MXQuantMeasure(act_format, axis).to(layer.quant.running_min.device if weight is None else weight.device)
+        if weight_format is not None:
+            layer.mx_weight = (weight_format, bool(weight_search))
+        switched += 1
+    return switched

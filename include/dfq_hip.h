@@ -1076,9 +1076,9 @@ void dfq_batch_unpack_plan_destroy(dfq_batch_unpack_plan* plan);
 /* kernel launches per run (1) */
 int32_t dfq_batch_unpack_plan_launches(const dfq_batch_unpack_plan* plan);
 
-/* MX block-scaled FP4 / FP6 / FP8 weights (extension; the OCP Microscaling formats the block-scaled f8f6f4 MFMA of gfx950
- * multiplies natively: 32 elements share one E8M0 scale).  Weights only; no activation, no matmul, no bias correction or adaptive
- * rounding on these grids.
+/* MX block-scaled FP4 / FP6 / FP8 (extension; the OCP Microscaling formats the block-scaled f8f6f4 MFMA of gfx950 multiplies
+ * natively: 32 elements share one E8M0 scale).  Weights of a batch (the plans), and any tensor along any axis (dfq_mx_axis: the
+ * activations); no matmul, and no bias correction or adaptive rounding on these grids.
  * DEFINITION.
  *   formats     id, bits, exponent / mantissa bits, bias, largest magnitude, emax:
  *                 DFQ_MX_E2M1 = 0: 4 bits, 2 / 1, bias  1, largest 6,                          emax  2
@@ -1120,6 +1120,16 @@ int32_t dfq_batch_unpack_plan_launches(const dfq_batch_unpack_plan* plan);
  * [rows * bpr]) and err (float64 [rows * bpr]: the S(e) of every block, by the tree above, NaN for a non-finite block) are each
  * written unless NULL.  DFQ_ERR_ARG for a null x, an x that is not 4-byte aligned, rows or row_len <= 0, row_len above 2^31 - 1, more than 2^29 blocks, an
  * unknown format.
+ * dfq_mx_axis: the same along any axis, one launch.  x is float32 [outer, len, inner], contiguous, and the blocks run along len:
+ * block (o, j, i) holds x[o, 32 j + t, i], t = 0..31; the last block j = bpa - 1 of an (o, i) is short when len % 32 != 0
+ * (bpa = ceil(len / 32)); no block crosses an o or an i.  y (float32, may be x), codes (uint8, one per element, in x's layout),
+ * scales (uint8 [outer, bpa, inner]) and err (float64 [outer, bpa, inner]: each block's S(e)) are each written unless NULL.
+ * `exponent`, `element`, `stored` and `non-finite` above apply word for word; the index in the tree of S(e) is t, absent elements
+ * count as +0.0.  EQUIVALENCE: the result is exactly dfq_mx_rows on the tensor with len moved last ([outer * inner, len]), moved
+ * back -- stored values, codes, scale bytes and block errors, bit for bit.  inner == 1 IS the row case and takes dfq_mx_rows'
+ * launch (rows = outer, row_len = len); otherwise a lane owns a block and no lane waits for another.  DFQ_ERR_ARG for a null x, an
+ * x that is not 4-byte aligned, outer, len or inner <= 0, len above 2^31 - 1, more than 2^29 blocks, an unknown format.
+ * Asynchronous on `stream`.
  * The batch plan, in the shape of dfq_batch_squant_plan and dfq_batch_mixed_plan: the table describes network 0, network n's copy
  * of a tensor lies bases[n] - bases[0] bytes further.  The blocks are the caller's: errors float64 [n_nets, n_tensors, F]
  * (F = n_widths), codes uint8 [n_nets, code_stride], scales uint8 [n_nets, scale_stride], status int32 [n_nets].
@@ -1154,6 +1164,8 @@ int32_t dfq_batch_unpack_plan_launches(const dfq_batch_unpack_plan* plan);
 #define DFQ_MX_QUANTISE 2
 int dfq_mx_rows(const float* x, float* y, int64_t rows, int64_t row_len, int32_t format, int32_t search, uint8_t* codes, uint8_t* scales,
                 double* err, void* stream);
+int dfq_mx_axis(const float* x, float* y, int64_t outer, int64_t len, int64_t inner, int32_t format, int32_t search,
+                uint8_t* codes, uint8_t* scales, double* err, void* stream);
 
 typedef struct dfq_batch_mx_plan dfq_batch_mx_plan;
 typedef struct dfq_batch_mx_tensor {
