@@ -228,6 +228,7 @@ SIGNATURES = {
     'dfq_le_plan_ro_elements': (c_int64, [c_void_p]),
     'dfq_le_plan_deferred_elements': (c_int64, [c_void_p]),
     'dfq_le_plan_defer_depth': (c_int32, [c_void_p]),
+    'dfq_le_plan_store_depth': (c_int32, [c_void_p]),
     'dfq_le_plan_lazy': (c_int32, [c_void_p]),
     'dfq_le_plan_lazy_stats': (c_int32, [c_void_p, c_void_p, c_void_p]),
     'dfq_le_plan_set_ctl_stage': (c_int32, [c_void_p, c_int32]),

@@ -49,8 +49,16 @@
 // through the remembered factors of the skipped sweeps one rounding at a time -- the very float32 operations the
 // reference performs, in its order, so every value and every |dW| term is bit-identical; sweep k % D == D-1 replays the
 // same way and stores.  4 (D + 1) / D bytes per element and sweep instead of 8.  A loop that ends between two stores
-// leaves up to D-1 pending factors: le_flush_kernel applies them (launched at the end of every enqueue call, gated per
+// leaves pending factors: le_flush_kernel applies them (launched at the end of every enqueue call, gated per
 // network on its sweep count) and le_hold_reset_kernel sets the remembered factors back to 1.
+// D is the window within which such a layer is READ (below: a lazy plan reads it once per window, and every verdict is built on
+// that).  The STORE period S is a number of its own (dfq_le_plan::store, LevelArgs::store; DFQ_LE_STORE_DEPTH = 4, 8 or 16,
+// default 8): a multiple of D for a lazy plan, D for every other.  The ring of a relation holds 2 (S - 1) o1 remembered factors,
+// sweep k's in slot k & (S - 1); the tile of sweep k has pend = k & (S - 1) factors to replay -- all of them one rounded
+// multiply each, in order, the last k & (D - 1) of them with their |dW| terms for the window arrays (the older ones were summed
+// by the reading sweep that closed their window) -- and stores when pend = S - 1.  The factors wait in LDS, one table per
+// pending sweep strided by the tile's own entry count (kHoldWide floats: the statistics and 1/s words a deferred tile never
+// uses); a plan whose widest deferred tile cannot hold S - 1 tables gets the largest S that fits.
 //
 // Lazy sweeps (batched plans with D > 1; DFQ_LE_LAZY_DW=0: off).  Between two stores a deferred layer is still read every sweep,
 // only for its |dW| term of that sweep's verdict.  A lazy sweep does not read it: its tiles do their per-channel duties only
@@ -67,8 +75,10 @@
 // resolve_network), decides exactly, and the network reads in every later sweep of the run.  Nothing is launched behind the
 // convergence launch: a sweep is the level launch and the convergence launch (plus the lean launch at the start of a group).
 // Where an enqueue call ends le_resolve_kernel -- the same resolve_network, one workgroup per network, all but those with
-// unresolved sweeps leave at once -- resolves the networks' lazy sweeps before le_flush_kernel stores.  4 (D + 1) / D -> 8 / D
-// bytes per deferred element and sweep, every value and the loop state bit-identical.
+// unresolved sweeps leave at once -- resolves the networks' lazy sweeps before le_flush_kernel stores.  4 (D + 1) / D -> 4 / D
+// + 4 / S bytes per deferred element and sweep (read once per window, stored once per store period), every value and the loop
+// state bit-identical.  Batch of 64 MobileNetV2 (profiles/store_depth_ab.txt, store_depth_trace.txt): S = 4 / 8 / 16 ->
+// 2.210 / 2.261 / 2.235e10 weights/s; at 16 the replay of up to 15 factors in the storing sweep costs more than the store saved.
 //
 // Convergence (dfq.py:105-115): every element is written exactly once per sweep, by a pass that has
 // its pre-sweep value in a register, so each tile leaves float64 partials of sum|W - W_prev|; they are
@@ -100,7 +110,12 @@ constexpr int kRowTileColsMax = 128;   // positions of a row tile (x2 for float4
 constexpr int kColTileLanes = 64;      // vector positions of a col tile (one wave per row at most)
 constexpr int kSlotMax = 1024;         // LDS table entries of a tile (stat slots / 1/s table)
 constexpr int kShortChunk = 9;          // taps a thread-per-row tile keeps in flight (one 3x3 kernel)
-constexpr int kHoldMax = 3;             // remembered factors per channel: deferred stores of depth <= 4
+constexpr int kHoldMax = 3;             // sweeps of a window before its last: the read / verdict window is 4 sweeps at most
+constexpr int kStoreMax = 16;           // store period of the deferred layers at most: kStoreMax - 1 remembered factors per channel
+constexpr int kStoreDefault = 8;        // ... of a lazy plan with kStoreMinElems deferred elements or more, unless DFQ_LE_STORE_DEPTH says otherwise
+constexpr int64_t kStoreMinElems = (int64_t)8 << 20;   // 32 MiB of deferred floats: what the eight L2s hold (see the plan)
+constexpr int kHoldPre = 4;             // table entries of remembered factors a thread requests ahead of its elements
+constexpr int kHoldWide = 3 * kSlotMax; // floats of remembered-factor tables in le_level_kernel (statistics words + 1/s words)
 constexpr int kBootTc = 256;           // channels per bootstrap tile (1 KB of a pointwise second layer's row)
 #ifndef DFQ_BOOT_ABLATE
 #define DFQ_BOOT_ABLATE 0
@@ -277,6 +292,8 @@ struct LeDep {
     unsigned long long* err_;
     int32_t sweep;
     int32_t naps_, limit_;
+    int32_t store_;                        // store period of the deferred layers (here: the window, LeParams::defer)
+    __device__ __forceinline__ int store() const { return store_; }
     __device__ __forceinline__ unsigned long long* counters() const { return (unsigned long long*)counters_; }
     __device__ __forceinline__ unsigned long long* err() const { return err_; }
     __device__ __forceinline__ int naps() const { return naps_; }
@@ -367,6 +384,7 @@ __device__ __forceinline__ void vstore(gfloat* p, const float (&x)[VEC]) {
 // the skipped sweeps of its window -- one per wave and skipped sweep, in the per-phase window arrays.  NoWin: nowhere (le_sweep_kernel,
 // plans without lazy sweeps).
 struct NoWin {
+    static constexpr bool kWide = false;    // the remembered-factor tables lie where a store period of kHoldMax + 1 put them
     __device__ __forceinline__ void clear(int) const {}
     __device__ __forceinline__ void add(int, double) const {}
     __device__ __forceinline__ void emit(int) const {}
@@ -442,12 +460,20 @@ __device__ __forceinline__ double row_tile(const LeRelDev& R, const LeParams& p,
     const bool local = VEC == 4 && R.local_r1 != 0;
     // deferred store (plan: never together with `fused` or `emit`): `phase` skipped sweeps precede this one since the
     // last store; their factors were written by earlier launches and are requested before everything else
+    // `pend` of them since the last store (dep.store() sweeps apart), the last `phase` of which belong to this sweep's window
+    // (p.defer sweeps): a table of nr factors per pending sweep, entry i = sweep i / nr, row i % nr
     const bool defer = (R.defer & 1) != 0;
+    const int pend = defer ? (dep.sweep & (dep.store() - 1)) : 0;
     const int phase = defer ? (dep.sweep & (p.defer - 1)) : 0;
-    const bool keep = defer && phase != p.defer - 1;           // this sweep does not store either
-    float hv[kHoldMax];
+    const bool keep = defer && pend != dep.store() - 1;            // this sweep does not store either
+    float* const htab = Win::kWide ? (float*)sh_slot : sh_pinv;        // (a deferred layer emits nothing and is not interior)
+    const int n_tab = (defer && !lazy) ? pend * nr : 0;
+    auto held = [&](int i) { const int j = small_div(i, nr); return R.hold[(int64_t)(2 * j) * R.o1 + r0 + (i - j * nr)]; };
+    // (requested ahead of the elements in le_level_kernel only: le_sweep_kernel has no registers to hold them across its waits)
+    constexpr int kPre = Win::kWide ? kHoldPre : 0;
+    float hq[kHoldPre];
 #pragma unroll
-    for (int j = 0; j < kHoldMax; ++j) hv[j] = (j < phase && tid < nr) ? R.hold[(int64_t)(2 * j) * R.o1 + r0 + tid] : 1.0f;
+    for (int q = 0; q < kPre; ++q) hq[q] = (tid + q * kBlock < n_tab) ? held(tid + q * kBlock) : 1.0f;
 
     // ---- load order.  No dependency: the four statistics words of this thread's row go first -- they are back long
     //      before the data and the scale solve then overlaps the data's flight instead of queueing behind it (memory
@@ -578,11 +604,7 @@ __device__ __forceinline__ double row_tile(const LeRelDev& R, const LeParams& p,
         scale_from_words(p, wa0, wa1, wb0, wb1, s, inv, mn1, mx1, mn2, mx2);
         sh_s[tid] = s;
         if (emit) sh_g[tid] = (small_div(c, R.pc_go) - g0) * nci;
-        if (defer) {
-#pragma unroll
-            for (int j = 0; j < kHoldMax; ++j) if (j < phase) sh_pinv[j * kTileRowsMax + tid] = hv[j];
-            if (own && keep) R.hold[(int64_t)(2 * phase) * R.o1 + c] = s;
-        }
+        if (own && keep) R.hold[(int64_t)(2 * pend) * R.o1 + c] = s;
         if (own) {
             R.s_cum[c] = o_cum * s;                       // relation.py:20-24
             if (R.bnw) R.bnw[c] = o_bnw * s;              // dfq.py:64-65
@@ -595,6 +617,11 @@ __device__ __forceinline__ double row_tile(const LeRelDev& R, const LeParams& p,
             }
         }
     }
+    if (n_tab > 0) {
+#pragma unroll
+        for (int q = 0; q < kPre; ++q) if (tid + q * kBlock < n_tab) htab[tid + q * kBlock] = hq[q];
+        for (int i = tid + kPre * kBlock; i < n_tab; i += kBlock) htab[i] = held(i);
+    }
     stamp(tr, 3);
     __syncthreads();
     stamp(tr, 4);
@@ -602,6 +629,38 @@ __device__ __forceinline__ double row_tile(const LeRelDev& R, const LeParams& p,
     double acc = 0.0;
     const bool wsum = defer && (R.defer & kDeferWin) != 0;     // the window's earlier sweeps (lazy plans), see below
     if (wsum) win.clear(phase);
+    if (n_tab > 0) {
+        // the stored value is `pend` sweeps old: take it through the remembered factors in order (one rounding each, as the
+        // skipped stores would have).  Each of those roundings is the one sweep j performed: its |dW| term is |t' - t|, which a
+        // lazy plan collects here for the window's sweeps that read nothing -- the last `phase` of them; the older ones were
+        // summed by the reading sweep that closed their window.  (Sweep by sweep, slot by slot: per window sweep the terms
+        // are added in slot order, as replay_oneway adds them.)
+        const int old = wsum ? pend - phase : pend;
+        auto replay = [&](int j, bool sum) {
+            const float* const tab = htab + j * nr;
+            double wj = 0.0;
+#pragma unroll
+            for (int u = 0; u < NV; ++u) {
+                if (u >= n_max) continue;
+                const float h = tab[min(jl + u * JL, nr - 1)];
+                float tn[VEC];
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) tn[k] = v[u][k] * h;
+                if (sum) wj += slot_abs_diff<VEC>(u < n_own, tn, v[u]);
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) v[u][k] = tn[k];
+            }
+            if (sum) win.add(j - old, wj);
+        };
+        // (le_sweep_kernel -- kHoldMax factors at most, no window sums -- replays slot by slot below instead: updating the
+        // registers its caller requested for it in place costs it spills)
+        if (Win::kWide) {
+#pragma unroll 1
+            for (int j = 0; j < old; ++j) replay(j, false);
+#pragma unroll 1
+            for (int j = old; j < pend; ++j) replay(j, true);
+        }
+    }
     int ci[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; ++k) ci[k] = emit ? (small_div(pos + k, R.khkw1) - i0) : 0;
@@ -626,40 +685,26 @@ __device__ __forceinline__ double row_tile(const LeRelDev& R, const LeParams& p,
 #pragma unroll
             for (int k = 0; k < VEC; ++k) pin[k] = sh_pinv[g + ci[k]];
         }
-        float nv[VEC];
-        if (!defer) {
+        float nv[VEC], t[VEC];
 #pragma unroll
-            for (int k = 0; k < VEC; ++k) {
-                const float t = v[u][k] * pin[k];               // dfq.py:73 of the previous relation (rounded), then
-                nv[k] = t * s;                                  // dfq.py:62 of this one
-            }
-            if (ok) vstore<VEC>(w + r * R.row_len, nv);
-            if (!(kAblate & 2)) acc += slot_abs_diff<VEC>(ok, nv, v[u]);
-        } else {
-            // the stored value is `phase` sweeps old: take it through the remembered factors (one rounding each, as the
-            // skipped stores would have), then this sweep's
-            // (each of those roundings is the one sweep j of the window performed: its |dW| term is |t' - t|, which a lazy plan
-            // collects here for the sweeps that read nothing)
-            float t[VEC];
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) t[k] = v[u][k];
+        for (int k = 0; k < VEC; ++k) t[k] = v[u][k];           // (a deferred layer in le_level_kernel: up to date with the sweep before)
+        if (!Win::kWide && n_tab > 0) {
 #pragma unroll
             for (int j = 0; j < kHoldMax; ++j) {
-                if (j < phase) {
-                    const float h = sh_pinv[j * kTileRowsMax + r];
-                    float tn[VEC];
+                if (j < pend) {
+                    const float h = htab[j * nr + r];
 #pragma unroll
-                    for (int k = 0; k < VEC; ++k) tn[k] = t[k] * h;
-                    if (wsum) win.add(j, slot_abs_diff<VEC>(ok, tn, t));
-#pragma unroll
-                    for (int k = 0; k < VEC; ++k) t[k] = tn[k];
+                    for (int k = 0; k < VEC; ++k) t[k] = t[k] * h;
                 }
             }
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) nv[k] = t[k] * s;
-            if (ok && !keep) vstore<VEC>(w + r * R.row_len, nv);
-            if (!(kAblate & 2)) acc += slot_abs_diff<VEC>(ok, nv, t);
         }
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            const float tp = t[k] * pin[k];                     // dfq.py:73 of the previous relation (rounded), then
+            nv[k] = tp * s;                                     // dfq.py:62 of this one
+        }
+        if (ok && !keep) vstore<VEC>(w + r * R.row_len, nv);
+        if (!(kAblate & 2)) acc += slot_abs_diff<VEC>(ok, nv, t);
         if (emit && ok) {
             if (g != cur_g) {
                 if (cur_g >= 0) {
@@ -753,8 +798,9 @@ __device__ __forceinline__ double col_tile(const LeRelDev& R, const LeParams& p,
     // deferred store (plan: never with `stat_only` or `emit`), see row_tile: the remembered 1/s of the skipped sweeps, one
     // table per skipped sweep laid out like sh_inv (the first in sh_hold, the others in the unused row-statistics words)
     const bool defer = (R.defer & 2) != 0;
+    const int pend = defer ? (dep.sweep & (dep.store() - 1)) : 0;
     const int phase = defer ? (dep.sweep & (p.defer - 1)) : 0;
-    const bool keep = defer && phase != p.defer - 1;
+    const bool keep = defer && pend != dep.store() - 1;
     if ((kAblate & 16) && defer) {
         // tuning builds only: what a deferred chain-end column tile would cost with its factors handed to it (no wait, no
         // statistics words, no solve, no table, no barrier) -- results WRONG by construction
@@ -777,10 +823,24 @@ __device__ __forceinline__ double col_tile(const LeRelDev& R, const LeParams& p,
         }
         return a;
     }
-    auto hold_tab = [&](int j) { return j == 0 ? sh_hold : (float*)sh_row + (j - 1) * kSlotMax; };
-    float hv[kHoldMax];
+    // one table of ne = g_n * nci factors per pending sweep.  le_level_kernel: table after table from the row-statistics words
+    // on into sh_hold, which follows them there; elsewhere (kHoldMax tables at most) the first in sh_hold, the others in
+    // the row-statistics words, kSlotMax apart
+    const int ne = g_n * nci;
+    auto hold_tab = [&](int j) {
+        return Win::kWide ? (float*)sh_row + j * ne : j == 0 ? sh_hold : (float*)sh_row + (j - 1) * kSlotMax;
+    };
+    const int n_tab = (defer && !lazy) ? pend * ne : 0;
+    auto held = [&](int i, int& j, int& idx) {          // entry i of the tables: sweep j, entry idx of its table
+        j = small_div(i, ne);
+        idx = i - j * ne;
+        const int gq = small_div(idx, nci);
+        return R.hold[(int64_t)(2 * j + 1) * R.o1 + (g_lo + gq) * R.gi + i0 + (idx - gq * nci)];
+    };
+    constexpr int kPre = Win::kWide ? kHoldPre : 0;         // (see row_tile)
+    float hq[kHoldPre];
 #pragma unroll
-    for (int j = 0; j < kHoldMax; ++j) hv[j] = (j < phase && has_entry) ? R.hold[(int64_t)(2 * j + 1) * R.o1 + e_c] : 1.0f;
+    for (int q = 0; q < kPre; ++q) { int j, idx; hq[q] = (tid + q * kBlock < n_tab) ? held(tid + q * kBlock, j, idx) : 1.0f; }
     if (!waits && has_entry) { wa0 = ld_stat(st_a); wa1 = ld_stat(st_a + 1); wb0 = st_b[0]; wb1 = st_b[1]; }
     if (!PRE) {
 #pragma unroll
@@ -813,12 +873,17 @@ __device__ __forceinline__ double col_tile(const LeRelDev& R, const LeParams& p,
             f[0] = ~enc_ord(mn2 * inv);
             f[1] = enc_ord(mx2 * inv);
         }
-        if (defer) {
+        if (keep && first_row) R.hold[(int64_t)(2 * pend + 1) * R.o1 + c] = inv;
+    }
+    if (n_tab > 0) {
 #pragma unroll
-            for (int j = 0; j < kHoldMax; ++j)
-                if (j < phase) hold_tab(j)[idx] = (idx == tid) ? hv[j] : R.hold[(int64_t)(2 * j + 1) * R.o1 + c];
-            if (keep && first_row) R.hold[(int64_t)(2 * phase + 1) * R.o1 + c] = inv;
+        for (int q = 0; q < kPre; ++q) {
+            if (tid + q * kBlock < n_tab) {
+                const int j = small_div(tid + q * kBlock, ne);
+                hold_tab(j)[tid + q * kBlock - j * ne] = hq[q];
+            }
         }
+        for (int i = tid + kPre * kBlock; i < n_tab; i += kBlock) { int j, idx; const float h = held(i, j, idx); hold_tab(j)[idx] = h; }
     }
     if (tid < nr) sh_tab[tid] = (small_div(r0 + tid, R.go) - g_lo) * nci;
     stamp(tr, 3);
@@ -831,6 +896,44 @@ __device__ __forceinline__ double col_tile(const LeRelDev& R, const LeParams& p,
     double acc = 0.0;
     const bool wsum = defer && (R.defer & kDeferWin) != 0;     // the window's earlier sweeps (lazy plans, see row_tile)
     if (wsum) win.clear(phase);
+    if (n_tab > 0) {
+        // the `pend` remembered factors in order, the last `phase` of them with their |dW| terms: see row_tile.  A tile whose
+        // rows share one group (every ungrouped layer) meets the same factors in every row: one table read per sweep
+        const int old = wsum ? pend - phase : pend;
+        const bool flat = g_n == 1;
+        auto replay = [&](int j, bool sum) {
+            const float* const tab = hold_tab(j);
+            float h[VEC];
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) h[k] = tab[ci[k]];
+            double wj = 0.0;
+#pragma unroll
+            for (int u = 0; u < NV; ++u) {
+                if (u >= n_max) continue;
+                const int r_raw = grp + u * n_rowslots;
+                if (!flat) {
+                    const int t0 = sh_tab[min(r_raw, nr - 1)];
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k) h[k] = tab[t0 + ci[k]];
+                }
+                float tn[VEC];
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) tn[k] = v[u][k] * h[k];
+                if (sum) wj += slot_abs_diff<VEC>(lane_on && r_raw < nr, tn, v[u]);
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) v[u][k] = tn[k];
+            }
+            if (sum) win.add(j - old, wj);
+        };
+        // (le_sweep_kernel -- kHoldMax factors at most, no window sums -- replays slot by slot below instead: updating the
+        // registers its caller requested for it in place costs it spills)
+        if (Win::kWide) {
+#pragma unroll 1
+            for (int j = 0; j < old; ++j) replay(j, false);
+#pragma unroll 1
+            for (int j = old; j < pend; ++j) replay(j, true);
+        }
+    }
 #pragma unroll
     for (int u = 0; u < NV; ++u) {
         if (u >= n_max) continue;
@@ -838,36 +941,26 @@ __device__ __forceinline__ double col_tile(const LeRelDev& R, const LeParams& p,
         const int r = min(r_raw, nr - 1);
         const bool ok = lane_on && r_raw < nr;
         const int t0 = sh_tab[r];
-        float nv[VEC];
-        if (!defer) {
+        float nv[VEC], t[VEC];
 #pragma unroll
-            for (int k = 0; k < VEC; ++k) nv[k] = v[u][k] * sh_inv[t0 + ci[k]];      // dfq.py:73
-            if (!stat_only) {
-                if (ok) vstore<VEC>(w + r * row_len2, nv);
-                if (!(kAblate & 2)) acc += slot_abs_diff<VEC>(ok, nv, v[u]);
-            }
-        } else {
-            float t[VEC];
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) t[k] = v[u][k];
+        for (int k = 0; k < VEC; ++k) t[k] = v[u][k];           // (a deferred layer in le_level_kernel: up to date with the sweep before)
+        if (!Win::kWide && n_tab > 0) {
 #pragma unroll
             for (int j = 0; j < kHoldMax; ++j) {
-                if (j < phase) {
+                if (j < pend) {
                     const float* tab = hold_tab(j) + t0;
-                    float tn[VEC];
 #pragma unroll
-                    for (int k = 0; k < VEC; ++k) tn[k] = t[k] * tab[ci[k]];
-                    if (wsum) win.add(j, slot_abs_diff<VEC>(ok, tn, t));
-#pragma unroll
-                    for (int k = 0; k < VEC; ++k) t[k] = tn[k];
+                    for (int k = 0; k < VEC; ++k) t[k] = t[k] * tab[ci[k]];
                 }
             }
+        }
 #pragma unroll
-            for (int k = 0; k < VEC; ++k) nv[k] = t[k] * sh_inv[t0 + ci[k]];
+        for (int k = 0; k < VEC; ++k) nv[k] = t[k] * sh_inv[t0 + ci[k]];         // dfq.py:73
+        if (!stat_only) {
             if (ok && !keep) vstore<VEC>(w + r * row_len2, nv);
             if (!(kAblate & 2)) acc += slot_abs_diff<VEC>(ok, nv, t);
         }
-        if (emit) {                                        // block-uniform: every lane reaches the shuffles
+        if (emit) {                                       // block-uniform: every lane reaches the shuffles
             float rmn = INFINITY, rmx = -INFINITY;
             if (ok) {
 #pragma unroll
@@ -1026,6 +1119,7 @@ __device__ __forceinline__ uint32_t fetch_words(const void* base, int n_words, i
 
 constexpr size_t kLevelSmem = sizeof(float) * (2 * kSlotMax + 2 * kSlotMax + kTileRowsMax + 2 * kTileRowsMax + 2) +   // le_level_kernel's shared memory
                               sizeof(double) * kHoldMax * kBlock;
+static_assert(kLevelSmem <= 160 * 1024 / 6, "six workgroups of le_level_kernel share a CU's LDS");
 constexpr int kDescWords = (int)(sizeof(LeRelDev) / 4);
 static_assert(sizeof(LeRelDev) % 4 == 0 && kDescWords + 2 <= kWave, "descriptor and two state words must fit one wave-wide load");
 
@@ -1065,7 +1159,7 @@ struct LevelArgs {
     const LeBlockRef* blocks;
     LeParams p;
     int32_t sweep;
-    int32_t pad;
+    int32_t store;          // store period of the deferred layers: p.defer (the read / verdict window) or a multiple of it
     const LeState* state;
     double* partials;
     unsigned long long* dep_counters;
@@ -1087,6 +1181,7 @@ __device__ __forceinline__ const LevelArgs& cold(const LevelArgs& a) { return a;
 struct LeDepCold {
     const LevelArgs& a;
     int32_t sweep;
+    __device__ __forceinline__ int store() const { return cold(a).store; }
     __device__ __forceinline__ unsigned long long* counters() const { return cold(a).dep_counters; }
     __device__ __forceinline__ unsigned long long* err() const { return cold(a).err; }
     __device__ __forceinline__ int naps() const { return cold(a).p.poll_naps; }
@@ -1097,6 +1192,7 @@ struct LeDepCold {
 // Each thread keeps its running sums in LDS words of its own (sh[j kBlock + tid], no barrier): next to the tile's registers three
 // more float64 accumulators took le_level_kernel past its register budget.
 struct LevelWin {
+    static constexpr bool kWide = true;     // le_level_kernel: the tables run on from the statistics words into the 1/s words
     const LevelArgs& a;
     const int32_t& base;    // the relation's partial_base
     const int32_t& tile;    // the tile's index in the relation (row tiles first)
@@ -1126,9 +1222,10 @@ __global__ __launch_bounds__(kBlock, DFQ_LE_MIN_WAVES) void le_level_kernel(Leve
     // gives every workgroup of a concurrent launch a buffer of its own only for dynamic shared memory)
     DFQ_DYN_SMEM(smem);
     float* const sh_f = (float*)smem;                           // [kSlotMax] row tile: scales; col tile: 1/s table
-    uint32_t* const sh_u = (uint32_t*)(sh_f + kSlotMax);        // [2 kSlotMax] row tile: column-stat slots; col tile: row stats
-    int* const sh_g = (int*)(sh_u + 2 * kSlotMax);              // [kTileRowsMax] per-row table offsets
-    float* const sh_p = (float*)(sh_g + kTileRowsMax);          // [kSlotMax] row tile of an interior layer: 1/s of the previous relation
+    int* const sh_g = (int*)(sh_f + kSlotMax);                  // [kTileRowsMax] per-row table offsets
+    uint32_t* const sh_u = (uint32_t*)(sh_g + kTileRowsMax);    // [2 kSlotMax] row tile: column-stat slots; col tile: row stats
+    float* const sh_p = (float*)(sh_u + 2 * kSlotMax);          // [kSlotMax] row tile of an interior layer: 1/s of the previous relation
+    // (sh_u and sh_p back to back: the kHoldWide floats of a deferred tile's remembered-factor tables, LevelWin::kWide)
     uint32_t* const sh_rs = (uint32_t*)(sh_p + kSlotMax);       // [2 kTileRowsMax] row tile that takes its rows' statistics itself (local_r1)
     int& sh_flag = *(int*)(sh_rs + 2 * kTileRowsMax);           // outcome of the dependency wait
     double* const sh_w = (double*)(sh_rs + 2 * kTileRowsMax + 2);  // [kHoldMax][kBlock] a deferred tile's window sums (LevelWin)
@@ -1316,7 +1413,7 @@ __global__ __launch_bounds__(kBlock, DFQ_LE_SWEEP_MIN_WAVES) void le_sweep_kerne
     const int lane = tid % kWave;
     const int G = (int)gridDim.x;
     const int cur = sweep & 1;
-    const LeDep dep{dep_counters, err, sweep, p.poll_naps, p.spin_limit};
+    const LeDep dep{dep_counters, err, sweep, p.poll_naps, p.spin_limit, p.defer};
 
     // which networks have stopped (the flags only change between launches)
     for (int n = tid; n < n_nets; n += kBlock) sh_done[n] = state[n].done != 0;
@@ -1640,7 +1737,10 @@ __device__ __forceinline__ int wave_uniform(int x) {
     return x;
 #endif
 }
-__device__ __forceinline__ void replay_oneway(const LeRelDev* __restrict__ rels, const LeOneway* __restrict__ ow, int n_ow, int last,
+// `old_last` = kHoldMax + 1 times `old` plus `last` (one scalar register held across the replay, not two).  `old`: remembered
+// factors of sweeps before the window (the store period is longer than the window): the stored elements go through them first,
+// without sums -- the reading sweep that closed their window summed those terms.
+__device__ __forceinline__ void replay_oneway(const LeRelDev* __restrict__ rels, const LeOneway* __restrict__ ow, int n_ow, int old_last,
                               double* __restrict__ win, int64_t part_stride) {
     constexpr int NV = kSlotsVec4;
     const int wave0 = wave_uniform((int)threadIdx.x / kWave) * kWave;       // first thread of this wave
@@ -1657,8 +1757,10 @@ __device__ __forceinline__ void replay_oneway(const LeRelDev* __restrict__ rels,
         const int rstride = col ? R.i2g * R.khkw : R.row_len;
         const float* wbase = col ? R.w2 : R.w1;
         const float* hold = col ? R.hold + R.o1 : R.hold;
+        int n_old = old_last / (kHoldMax + 1);
+        const float* hold_win = hold + (int64_t)(2 * n_old) * R.o1;                     // the window's first factor
 #if defined(__HIP_DEVICE_COMPILE__)
-        asm volatile("" : "+v"(wbase), "+v"(hold), "+v"(win), "+v"(part_stride));      // (only vector instructions use them)
+        asm volatile("" : "+v"(wbase), "+v"(hold), "+v"(hold_win), "+v"(n_old), "+v"(win), "+v"(part_stride));      // (only vector instructions use them)
 #endif
         const int slot0 = (R.partial_base + (col ? R.n_row_tiles : 0)) * (kBlock / kWave);
         for (int it0 = wave0; it0 < n_tiles * kBlock; it0 += kCtlBlock) {
@@ -1710,10 +1812,16 @@ __device__ __forceinline__ void replay_oneway(const LeRelDev* __restrict__ rels,
 #pragma unroll
                 for (int k = 0; k < 4; ++k) t[k] = (k < vec) ? w[(int64_t)r * rstride + k] : 0.0f;
                 const int c = col ? small_div(row0 + r, R.go) * R.gi : row0 + r;
+#pragma unroll 1
+                for (int j = 0, nj = wave_uniform(n_old); j < nj; ++j) {      // (n_old waits in a vector register)
+                    const float* const hj = hold + ((int64_t)(2 * j) * R.o1 + c);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) t[k] = (k < vec) ? t[k] * hj[col ? small_div(pos + k, R.khkw) : 0] : 0.0f;
+                }
 #pragma unroll
                 for (int j = 0; j < kHoldMax; ++j) {
-                    if (j > last) continue;
-                    const float* const hj = hold + ((int64_t)(2 * j) * R.o1 + c);
+                    if (j > old_last % (kHoldMax + 1)) continue;
+                    const float* const hj = hold_win + ((int64_t)(2 * j) * R.o1 + c);
                     float nv[4];
 #pragma unroll
                     for (int k = 0; k < 4; ++k) nv[k] = (k < vec) ? t[k] * hj[col ? small_div(pos + k, R.khkw) : 0] : 0.0f;
@@ -1729,7 +1837,7 @@ __device__ __forceinline__ void replay_oneway(const LeRelDev* __restrict__ rels,
             }
 #pragma unroll
             for (int j = 0; j < kHoldMax; ++j) {
-                if (j > last) continue;
+                if (j > old_last % (kHoldMax + 1)) continue;
                 const double tsum = wave_sum(aw[j]);
                 if (threadIdx.x % kWave == 0) win[(int64_t)j * part_stride + slot] = tsum;
             }
@@ -1760,7 +1868,9 @@ struct LeNetDesc {           // one network of a (possibly batched) plan
 // Lazy sweeps of a plan (see "Lazy sweeps" in the header comment): what the convergence launch and le_resolve_kernel need
 struct LeLazy {
     int32_t on;             // 0: every sweep reads (DFQ_LE_LAZY_DW=0, defer 1, ...)
-    int32_t defer;
+    int32_t defer;          // the read / verdict window
+    int32_t store;          // the store period of the deferred layers (>= defer)
+    int32_t pad_;
     double kappa;           // eager when the predicted bound lb^2 / lb_prev falls to kappa x threshold (0: never predicted)
     double* win;            // [defer - 1] x part_stride partials of the deferred tiles, per phase
     int64_t part_stride;
@@ -1869,7 +1979,8 @@ __device__ __forceinline__ void resolve_network(const LeVerdictArgs& v, const Le
     {
         const auto& c = cold(v);
         const int b0 = c.lz.ow_begin[net], b1 = c.lz.ow_begin[net + 1];
-        replay_oneway(c.lz.rels, c.lz.ow + b0, b1 - b0, (c.states[net].sweeps - 1) & (c.lz.defer - 1), c.lz.win, c.lz.part_stride);
+        const int k = c.states[net].sweeps - 1, last = k & (c.lz.defer - 1);
+        replay_oneway(c.lz.rels, c.lz.ow + b0, b1 - b0, ((k & (c.lz.store - 1)) - last) * (kHoldMax + 1) + last, c.lz.win, c.lz.part_stride);
     }
     __syncthreads();                               // (the window sums: global words of this workgroup, read back by it)
     const auto& c = cold(v);
@@ -2321,6 +2432,7 @@ struct dfq_le_plan {
     // deferred stores: depth (1 = off), elements of the layers concerned (part of rw_total: read every sweep, written every
     // `defer`-th), the remembered factors, the workgroup tables of the flush / reset launches
     int defer = 1;
+    int store = 1;                         // store period of those layers: `defer` (the read / verdict window) or, lazy plans, more
     int64_t deferred_total = 0;
     float* d_hold = nullptr;
     LeFlushRef* d_flush = nullptr;
@@ -2819,20 +2931,57 @@ int dfq_le_plan_create_batch(const dfq_layer* layers, int32_t n_layers, const in
         const char* de = getenv("DFQ_LE_DEFER");
         const int want = de ? atoi(de) : (n_nets > 1 ? 4 : 1);
         p->defer = (want >= 4) ? 4 : (want >= 2) ? 2 : 1;
-        int64_t hold_floats = 0;
-        std::vector<int64_t> hold_off(n_relations, -1);
         for (int r = 0; r < n_relations && p->defer > 1; ++r) {
             LeRelDev& d = h[r];
             if (fr[r]) continue;
             if (!d.w1_interior && d.rt_vec != 0) { d.defer |= 1; p->deferred_total += (int64_t)d.o1 * d.row_len; ld[relations[r].first].oneway = 1; }
             if (!d.w2_interior && d.ct_vec != 0) { d.defer |= 2; p->deferred_total += (int64_t)d.o2 * d.i2g * d.khkw; ld[relations[r].second].oneway = 1; }
-            if (d.defer) { hold_off[r] = hold_floats; hold_floats += (int64_t)2 * (p->defer - 1) * d.o1; }
+        }
+        // The store period S (DFQ_LE_STORE_DEPTH: 4, 8 or 16).  `defer` stays what every verdict is built on: the window after which a
+        // lazy sweep's |dW| terms are read at the latest.  The stores between two windows' ends serve nobody (the elements are
+        // read by their own tile only, which replays the remembered factors), so a LAZY plan stores every S-th sweep only, S a
+        // multiple of the window: 4 B per `defer` sweeps read + 4 B per S sweeps written for a deferred element.  A plan that
+        // reads every sweep would replay the whole ring every sweep: it keeps S = defer.  So does a plan of the persistent-
+        // workgroup variant (DFQ_LE_PERSIST=1: le_sweep_kernel's tables have room for kHoldMax factors and it runs no lazy
+        // sweeps).  A tile holds one table of remembered factors per pending sweep in kHoldWide floats: a plan with a tile whose
+        // tables do not fit S - 1 times gets the largest S that fits (dfq_le_plan_store_depth tells).
+        // Default: 8 where the plan's deferred elements are kStoreMinElems floats or more, else `defer`.  Batches of 64 / 32 / 16
+        // MobileNetV2 (82 / 41 / 20.5 M deferred elements): +2.5 / +1.6 / +1.2 % at S = 8; a batch of 4 (5.1 M, 20 MB -- less than
+        // the L2s hold, so its stores were not what a sweep waits for): 5.757 against 5.748e9 weights/s, nothing -- and then the
+        // shorter ring and the cheaper write-back stay (profiles/store_depth_ab.txt).  DFQ_LE_STORE_DEPTH overrides either way.
+        p->store = p->defer;
+        {
+            const char* se = getenv("DFQ_LE_STORE_DEPTH");
+            const char* lz = getenv("DFQ_LE_LAZY_DW");
+            const char* pe = getenv("DFQ_LE_PERSIST");
+            const int want_s = se ? atoi(se) : (p->deferred_total >= kStoreMinElems ? kStoreDefault : p->defer);
+            bool lazy_plan = n_nets > 1 && p->defer > 1 && !(lz && lz[0] == '0') && !(pe && pe[0] == '1');
+            std::vector<int> layers_of(n_nets, 0);
+            for (int l = 0; l < n_layers; ++l) layers_of[net_of(l)] += 1;
+            for (int n = 0; n < n_nets; ++n) lazy_plan = lazy_plan && layers_of[n] <= 1024;        // (as `small` below)
+            if (lazy_plan) {
+                int s_fit = want_s >= 16 ? 16 : want_s >= 8 ? 8 : 4;
+                for (int r = 0; r < n_relations; ++r) {
+                    const LeRelDev& d = h[r];
+                    const int row_entries = (d.defer & 1) ? d.rt_rows : 0;
+                    const int col_entries = (d.defer & 2) ? (ceil_div(d.ct_rows, d.go) + 1) * (ceil_div(d.ct_cols, d.khkw) + 1) : 0;
+                    while (s_fit > p->defer && (s_fit - 1) * std::max(row_entries, col_entries) > kHoldWide) s_fit /= 2;
+                }
+                p->store = std::max(p->defer, std::min(s_fit, kStoreMax));
+            }
+        }
+        int64_t hold_floats = 0;
+        std::vector<int64_t> hold_off(n_relations, -1);
+        for (int r = 0; r < n_relations && p->defer > 1; ++r) {
+            const LeRelDev& d = h[r];
+            if (d.defer) { hold_off[r] = hold_floats; hold_floats += (int64_t)2 * (p->store - 1) * d.o1; }
         }
         if (hold_floats > 0) {
             if ((e = p->mem.alloc((void**)&p->d_hold, sizeof(float) * hold_floats)) != hipSuccess) return fail_alloc(e);
             for (int r = 0; r < n_relations; ++r) if (hold_off[r] >= 0) h[r].hold = p->d_hold + hold_off[r];
         } else {
             p->defer = 1;
+            p->store = 1;
         }
     }
     std::vector<LeNetDesc> nets(n_nets);
@@ -3216,7 +3365,7 @@ int dfq_le_plan_create_batch(const dfq_layer* layers, int32_t n_layers, const in
                 if ((e = p->mem.alloc((void**)&p->d_hold_rels, sizeof(int32_t) * hold_rels.size())) != hipSuccess) return fail_alloc(e);
                 if ((e = hipMemcpy(p->d_hold_rels, hold_rels.data(), sizeof(int32_t) * hold_rels.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail_alloc(e);
                 hipLaunchKernelGGL(le_hold_reset_kernel, dim3(p->n_hold_rels), dim3(kBlock), 0, nullptr, (const LeRelDev*)p->d_rels,
-                                   (const int32_t*)p->d_hold_rels, (const LeState*)p->d_state, p->defer, 1);
+                                   (const int32_t*)p->d_hold_rels, (const LeState*)p->d_state, p->store, 1);
             }
         }
         // counters: [relation: its column tiles][error word + padding][relation: its row tiles (local_r1)]
@@ -3341,6 +3490,9 @@ int64_t dfq_le_plan_ro_elements(const dfq_le_plan* p) { return p ? p->ro_total :
 // every `depth`-th; depth 1 = every sweep (resident plans, DFQ_LE_DEFER=1)
 int64_t dfq_le_plan_deferred_elements(const dfq_le_plan* p) { return (p && !res_on(p)) ? p->deferred_total : 0; }
 int32_t dfq_le_plan_defer_depth(const dfq_le_plan* p) { return (p && !res_on(p)) ? p->defer : 1; }
+// ... and written every `store_depth`-th: the defer depth, or for a plan that runs lazy sweeps DFQ_LE_STORE_DEPTH (4, 8 or 16)
+// cut down to what the remembered-factor tables of the plan's widest deferred tile hold
+int32_t dfq_le_plan_store_depth(const dfq_le_plan* p) { return (p && !res_on(p)) ? p->store : 1; }
 // lazy sweeps of the deferred layers: 1 when the plan runs them (dfq_le.hip, "Lazy sweeps")
 int32_t dfq_le_plan_lazy(const dfq_le_plan* p) { return (p && lazy_active(p)) ? 1 : 0; }
 int32_t dfq_le_plan_set_ctl_stage(dfq_le_plan* p, int32_t n_partials) {
@@ -3434,7 +3586,7 @@ int32_t dfq_le_plan_level_launches(const dfq_le_plan* p, int32_t level, int64_t*
 
 static LeLazy lazy_args(const dfq_le_plan* p) {
     LeLazy z;
-    z.on = lazy_active(p) ? 1 : 0; z.defer = p->defer; z.kappa = p->lazy_kappa;
+    z.on = lazy_active(p) ? 1 : 0; z.defer = p->defer; z.store = p->store; z.pad_ = 0; z.kappa = p->lazy_kappa;
     z.win = p->d_win; z.part_stride = p->part_stride; z.mean_win = p->d_mean_win; z.n_layers_all = p->n_layers;
     z.rels = (const LeRelDev*)p->d_rels; z.ow = (const LeOneway*)p->d_ow; z.ow_begin = (const int32_t*)p->d_ow_begin;
     return z;
@@ -3476,7 +3628,7 @@ static int le_restart(dfq_le_plan* p, const dfq_le_config* cfg, hipStream_t st) 
     p->sweep_index = 0;
     if (p->defer > 1 && p->n_hold_rels > 0) {
         hipLaunchKernelGGL(le_hold_reset_kernel, dim3(p->n_hold_rels), dim3(kBlock), 0, st, (const LeRelDev*)p->d_rels,
-                           (const int32_t*)p->d_hold_rels, (const LeState*)p->d_state, p->defer, 1);
+                           (const int32_t*)p->d_hold_rels, (const LeState*)p->d_state, p->store, 1);
         DFQ_CHECK_LAUNCH();
     }
     if (p->n_rels > 0) {
@@ -3505,11 +3657,11 @@ static int le_flush(dfq_le_plan* p, hipStream_t st) {
     }
     if (p->n_flush == 0) return DFQ_OK;
     hipLaunchKernelGGL(le_flush_kernel, dim3(p->n_flush), dim3(kBlock), 0, st, (const LeFlushRef*)p->d_flush, (const LeState*)p->d_state,
-                       p->defer, p->cf_group);
+                       p->store, p->cf_group);
     DFQ_CHECK_LAUNCH();
     if (p->n_hold_rels > 0) {
         hipLaunchKernelGGL(le_hold_reset_kernel, dim3(p->n_hold_rels), dim3(kBlock), 0, st, (const LeRelDev*)p->d_rels,
-                           (const int32_t*)p->d_hold_rels, (const LeState*)p->d_state, p->defer, 0);
+                           (const int32_t*)p->d_hold_rels, (const LeState*)p->d_state, p->store, 0);
         DFQ_CHECK_LAUNCH();
     }
     if (p->cf_group > 1) {
@@ -3607,7 +3759,7 @@ static int le_launch_level(dfq_le_plan* p, int launch, const LeParams& q, hipStr
         return DFQ_OK;
     }
     LevelArgs la;
-    la.table = (const LeRelDev*)p->d_rels; la.blocks = table; la.p = q; la.sweep = (int32_t)p->sweep_index; la.pad = 0;
+    la.table = (const LeRelDev*)p->d_rels; la.blocks = table; la.p = q; la.sweep = (int32_t)p->sweep_index; la.store = p->store;
     la.state = (const LeState*)p->d_state; la.partials = sweep_partials(p); la.dep_counters = p->d_dep;
     la.err = p->d_dep + (size_t)p->n_rels * kDepStride; la.tr = tr; la.lean = (const LeLeanRef*)p->d_lean; la.part_stride = p->part_stride;
     la.win = lazy_active(p) ? p->d_win : nullptr;

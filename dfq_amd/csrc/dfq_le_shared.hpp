@@ -13,7 +13,8 @@ struct LeParams {
     int32_t hi_gt_lo, signed_range;
     int32_t poll_naps;      // s_sleep(8) units between two polls of a dependency counter
     int32_t spin_limit;     // polls after which a workgroup abandons an in-launch wait (DFQ_SPIN_LIMIT; tests force an abandon with 1)
-    int32_t defer;          // streaming engine: one-way-scaled layers are stored every `defer`-th sweep (1, 2 or 4; dfq_le.hip)
+    int32_t defer;          // streaming engine: one-way-scaled layers are read at the latest every `defer`-th sweep (1, 2 or 4; dfq_le.hip) and
+                            // stored every `defer`-th or, lazy plans, every LevelArgs::store-th
 };
 
 struct LeState {

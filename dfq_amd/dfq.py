@@ -188,6 +188,12 @@ class LEPlan:
         return _ffi.lib().dfq_le_plan_defer_depth(self._plan)
 
     @property
+    def store_depth(self):
+        """Sweeps between two stores of the deferred elements: defer_depth, or for a lazy plan DFQ_LE_STORE_DEPTH (4, 8 or
+        16, cut down to what the plan's tiles hold; include/dfq_hip.h)."""
+        return _ffi.lib().dfq_le_plan_store_depth(self._plan)
+
+    @property
     def free_running_elements(self):
         """Elements (NOT part of rw_elements) of layers whose every statistic is closed-form: the streaming engine reads and
         writes them once per `free_running_group` sweeps, in a lean launch of its own (dfq_le_cf.hpp, include/dfq_hip.h)."""
@@ -232,10 +238,11 @@ class LEPlan:
     @property
     def sweep_bytes(self):
         """Bytes one sweep moves as executed (averaged over defer_depth sweeps and over a group of the free-running layers).
-        A lazy plan is priced as if every sweep but the storing one were lazy: its deferred elements then move 8 B per
-        defer_depth sweeps (what the always-lazy loop of a forced sweep count does)."""
-        d = self.defer_depth
-        deferred = (8.0 - 8.0 / d) if self.lazy else 4.0 * (d - 1) / d
+        A lazy plan is priced as if every sweep but a window's last were lazy: its deferred elements then move 4 B per
+        defer_depth sweeps read and 4 B per store_depth sweeps written (what the always-lazy loop of a forced sweep count
+        does)."""
+        d, s = self.defer_depth, self.store_depth
+        deferred = (8.0 - 4.0 / d - 4.0 / s) if self.lazy else 4.0 * (d - 1) / d
         return (8 * self.rw_elements + 4 * self.ro_elements - deferred * self.deferred_elements
                 + 8.0 * self.free_running_elements / self.free_running_group)
 
@@ -941,7 +948,7 @@ degraded_runs = {'le': 0, 'bc': 0}
 # every environment switch the library reads while it CREATES a plan (tests/test_errors.py checks this list against the sources)
 _PLAN_ENV = ('DFQ_LE_RESIDENT', 'DFQ_LE_MERGED', 'DFQ_LE_TILE_ELEMS', 'DFQ_LE_ROW_COLS', 'DFQ_LE_COL_COLS', 'DFQ_LE_BOOT_WORK',
              'DFQ_LE_PERSIST', 'DFQ_LE_SWEEP_WGS', 'DFQ_LE_EMIT_COLS', 'DFQ_LE_NO_SHORT', 'DFQ_LE_CHAIN_FIRST', 'DFQ_LE_POLL_NAPS',
-             'DFQ_LE_DEFER', 'DFQ_LE_LAZY_DW', 'DFQ_LE_LAZY_MARGIN', 'DFQ_LE_CF', 'DFQ_LE_CF_GROUP', 'DFQ_LE_CF_BG', 'DFQ_LE_CF_BG_PRIO', 'DFQ_LE_CF_WEAVE', 'DFQ_LE_FUSE', 'DFQ_LE_UNIFORM', 'DFQ_LE_LOCAL_R1', 'DFQ_LE_LOCAL_ROW', 'DFQ_RES_EXACT_GROUPS', 'DFQ_RES_RELAXED', 'DFQ_RES_ORDER', 'DFQ_RES_SPEC', 'DFQ_RES_CKPT',
+             'DFQ_LE_DEFER', 'DFQ_LE_STORE_DEPTH', 'DFQ_LE_LAZY_DW', 'DFQ_LE_LAZY_MARGIN', 'DFQ_LE_CF', 'DFQ_LE_CF_GROUP', 'DFQ_LE_CF_BG', 'DFQ_LE_CF_BG_PRIO', 'DFQ_LE_CF_WEAVE', 'DFQ_LE_FUSE', 'DFQ_LE_UNIFORM', 'DFQ_LE_LOCAL_R1', 'DFQ_LE_LOCAL_ROW', 'DFQ_RES_EXACT_GROUPS', 'DFQ_RES_RELAXED', 'DFQ_RES_ORDER', 'DFQ_RES_SPEC', 'DFQ_RES_CKPT',
              'DFQ_RES_DIRECT', 'DFQ_RES_CF', 'DFQ_RES_SHORT_RPT', 'DFQ_RES_TILE_FLOATS', 'DFQ_BC_TAGGED', 'DFQ_BC_MERGED', 'DFQ_BC_BLOCKS', 'DFQ_BC_EPS', 'DFQ_BC_FOLD', 'DFQ_BC_MM_CHUNK', 'DFQ_BC_ONE_GROUP', 'DFQ_BC_ONE_LAUNCH', 'DFQ_BC_MM_AHEAD', 'DFQ_BC_SKEW',
              'DFQ_GRAPH', 'DFQ_COOPERATIVE', 'DFQ_HIP_LIB')
 # ... and the ones it reads on every RUN (they change no plan)

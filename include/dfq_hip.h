@@ -159,6 +159,13 @@ int64_t dfq_le_plan_ro_elements(const dfq_le_plan* plan);
  * elements: bytes per sweep as executed, averaged over D sweeps = 8 * rw + 4 * ro - 4 * deferred * (D - 1) / D. */
 int64_t dfq_le_plan_deferred_elements(const dfq_le_plan* plan);
 int32_t dfq_le_plan_defer_depth(const dfq_le_plan* plan);
+/* The store period S of those layers.  D above is the window after which their elements are READ at the latest; a plan that
+ * runs lazy sweeps (below) stores them only every S-th sweep, S = DFQ_LE_STORE_DEPTH (4, 8 or 16; default 8 for a plan with
+ * 8 Mi deferred elements or more -- the stores of a smaller one do not reach memory that a sweep waits for -- and D below
+ * that), a multiple of D -- nobody reads the stores in between.  Its deferred elements then move 4 B per D sweeps read + 4 B per S sweeps written.
+ * Every other plan has S = D.  A tile keeps one table of remembered factors per pending sweep in shared memory: a plan with a
+ * deferred tile too wide for S - 1 of them gets the largest S that fits, which is what this returns. */
+int32_t dfq_le_plan_store_depth(const dfq_le_plan* plan);
 /* 1 when the plan runs lazy sweeps: the deferred layers are read only in their storing sweep and in sweeps whose verdict
  * needs their |dW| sums (batched plans with defer > 1; DFQ_LE_LAZY_DW=0 turns them off) */
 int32_t dfq_le_plan_lazy(const dfq_le_plan* plan);
